@@ -6,9 +6,17 @@ ef = 128, k = 10, query batch 1024, embeddings resident in HBM (in-memory provid
 One "step" = one pass of the hot path (isl_search_batch_device) over one batch of queries
 that is already resident in HBM.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W --full
     python bench.py --gpus N ...            (no launcher: starts N ranks itself, before any GPU call)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up (rows, graph, index, query batches), warms up, times the K steps and prints the
+line; nothing else.  --full adds what the headline does not need: exact ground truth and recall@10
+(and the ef sweep when recall misses 0.95), the host-buffer path, roofline.traffic from a child run
+under rocprofv3, the CPU baseline, the neutral-workload side runs and, with N > 1, the replica-mode
+run.  --dump-outputs DIR writes the last timed step's answer (ids, distances, counts) as .npy files;
+the inputs are seeded, so the same arguments give the same inputs on every run.
 
 Multi-GPU (N > 1), mode "shard" (default, the north star's layout): the index is sharded by
 node-id range, every rank searches the whole query batch in its own sub-graph, the
@@ -59,6 +67,29 @@ def algorithmic_bytes(st: dict, d: int, k: int, elem: int = 4) -> float:
     """V*d*s + 4*E + 8*H + 4*d + 12*k per query, summed over a batch."""
     return (st["evals"] * d * elem + 4 * st["edges"] + 8 * st["expansions"] +
             st["queries"] * (4 * d + 12 * k))
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, ids: np.ndarray, dist: np.ndarray, cnt: np.ndarray):
+    """--dump-outputs: the last timed step's answer as DIR/{ids,distances,counts}.npy.  Slots past a query's
+    count are not written by the search; they are set to id -1 and distance +inf so that two builds compare equal
+    whatever those buffers held before.  Above DUMP_LIMIT_BYTES a fixed seeded sample of the query rows."""
+    nq, k = ids.shape
+    valid = np.arange(k)[None, :] < cnt.astype(np.int64)[:, None]
+    out = {"ids": np.where(valid, ids.astype(np.float64), -1.0),
+           "distances": np.where(valid, dist.astype(np.float32), np.float32(np.inf)).astype(np.float32),
+           "counts": cnt.astype(np.float32)}
+    per_row = sum(a.nbytes for a in out.values()) / max(nq, 1)
+    os.makedirs(out_dir, exist_ok=True)
+    if nq * per_row > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(20240601).choice(nq, int(DUMP_LIMIT_BYTES // (per_row + 8)), replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out["query_rows"] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{n} {a.shape}" for n, a in out.items()))
 
 
 def host_cpu_info() -> dict:
@@ -216,7 +247,8 @@ def measure_neutral(args, graph):
 
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--dataset", "M", "--graph", graph, "--nodes", "1000000", "--dim", str(args.dim), "--nq", str(args.nq),
-           "--k", str(args.k), "--ef", str(args.ef), "--no-traffic", "--no-cpu-baseline", "--no-host-path", "--no-neutral-side"]
+           "--k", str(args.k), "--ef", str(args.ef), "--full", "--no-traffic", "--no-cpu-baseline", "--no-host-path",
+           "--no-neutral-side"]
     t0 = time.time()
     pr = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     line = [l for l in pr.stdout.decode(errors="replace").splitlines() if l.startswith("{")]
@@ -341,7 +373,21 @@ def main():
     ap.add_argument("--pipeline", type=int, default=0,
                     help="searches kept in flight (isl_search_batch_device_async); 1 = synchronous; default 16 on "
                          "one GPU, 12 per rank in multi-GPU runs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: exact ground truth and recall@10 (on every query "
+                         "batch up to 128 of them, on 128 evenly spaced ones beyond; with the ef sweep when it misses "
+                         "0.95), the host-buffer path, roofline.traffic under rocprofv3, the CPU "
+                         "baseline, the neutral-workload side runs and, with several GPUs, the replica-mode run (the "
+                         "--no-* options above leave parts of it out).  Without it a run sets up, warms up, times the "
+                         "steps and prints the line; recall_at_10 is then null")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/ids.npy "
+                         "(float64), DIR/distances.npy (float32) and DIR/counts.npy (float32); slots past a query's "
+                         "count hold id -1 and distance +inf.  Over 64 MB in all, a fixed seeded sample of the query "
+                         "rows is written instead, their indices in DIR/query_rows.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # this process stays off the GPU
@@ -466,22 +512,34 @@ def main():
 
         nb_batches = args.steps + args.warmup if args.distinct_batches <= 0 else \
             max(1, min(args.distinct_batches, args.steps + args.warmup))
-        qsets, truths = [], []
+        qsets, truths = [], {}
+        # --full: exact truth of every batch up to 128 of them, of every truth_stride-th batch beyond (the brute force
+        # over all rows takes up to about 0.1 s per batch at 10M rows); recall@10 is the mean over the timed steps on those batches
+        truth_stride = -(-nb_batches // 128)
+        # replica mode: every rank answers its own batches; shard mode: same batch on all ranks
+        qbase = (rank * nb_batches if (world > 1 and not shard_mode) else 0) * nq
+        q_all = None
+        if args.dataset == "G":
+            # batch b = rows [qbase + b * nq, qbase + (b + 1) * nq) of the query stream; a row's value depends on its
+            # position in the stream only, so one call makes the same batches as one call per batch, with the
+            # mixture's centres and every 65536-row chunk of noise made once instead of once per batch
+            q_all = synth.make_rows(N, d, qbase, nb_batches * nq, per_cluster=args.per_cluster, device=dev,
+                                    query=True, distinct_leaves=args.distinct_leaves)
         for b in range(nb_batches):
-            # replica mode: every rank answers its own batches; shard mode: same batch on all ranks
-            qoff = (b + (rank * nb_batches if (world > 1 and not shard_mode) else 0)) * nq
+            qoff = qbase + b * nq
             if args.dataset == "U":
                 q = synth.make_uniform(nq, d, 43 + qoff, device=dev)
             elif args.dataset == "M":  # out-of-sample points of the same density (their own seed stream)
                 q = synth.make_manifold(nq, d, 4300 + qoff // max(nq, 1), device=dev, latent=args.latent)
             else:
-                q = synth.make_rows(N, d, qoff, nq, per_cluster=args.per_cluster, device=dev, query=True,
-                                    distinct_leaves=args.distinct_leaves)
+                q = q_all[b * nq:(b + 1) * nq]
             if args.row_dtype == "bf16":  # config 5: the queries are bf16 values too (their exact f32 images)
                 q = q.to(torch.bfloat16).to(torch.float32)
             qsets.append(q.contiguous())
-            ti, td = synth.brute_force_topk_native(x, q, k)  # exact truth: float32 MFMA brute force
-            truths.append((ti + (lo if shard_mode else 0), td))  # (a rehearsed shard answers in local ids)
+            if args.full and b % truth_stride == 0:
+                ti, td = synth.brute_force_topk_native(x, q, k)  # exact truth: float32 MFMA brute force
+                truths[b] = (ti + (lo if shard_mode else 0), td)  # (a rehearsed shard answers in local ids)
+        del q_all  # f32 batches are views of it; bf16 batches are copies, which must not keep it in HBM twice
         torch.cuda.synchronize()
 
         # one output set per search in flight
@@ -498,9 +556,9 @@ def main():
             searcher = ShardedSearcher(N, index=idx, device=dev, depth=depth,
                                        transport="rccl" if backend == "nccl" else "host").prepare(nq, k, ef)
             comm_info.update(searcher.shard_group.info())
-            # exact global truth = merge of the per-shard exact top-k (same collective + merge)
-            g_truth = []
-            for (ti, td) in truths:
+            # exact global truth = merge of the per-shard exact top-k (same collective + merge; --full only)
+            g_truth = {}
+            for b, (ti, td) in sorted(truths.items()):
                 gi_all = torch.zeros((world * nq, k), dtype=ti.dtype, device=dev)
                 gd_all = torch.zeros((world * nq, k), dtype=td.dtype, device=dev)
                 all_gather_rows(gi_all, ti.contiguous())
@@ -508,7 +566,7 @@ def main():
                 ci = gi_all.view(world, nq, k).permute(1, 0, 2).reshape(nq, world * k)
                 cd = gd_all.view(world, nq, k).permute(1, 0, 2).reshape(nq, world * k)
                 sel = torch.topk(cd, k, dim=1, largest=False).indices
-                g_truth.append(torch.gather(ci, 1, sel))
+                g_truth[b] = torch.gather(ci, 1, sel)
 
         def enqueue(b):
             """One step = one pass of the hot path over one resident query batch."""
@@ -520,12 +578,12 @@ def main():
                                                  o[1].data_ptr(), o[2].data_ptr())
 
         def finish(b, token):
+            """-> (counters, (ids, distances, counts)): what the caller of step b receives."""
             if shard_mode:
                 (m_ids, m_dist, m_src, m_cnt), st = searcher.result(token, with_stats=True)
-                return st, (m_ids, m_cnt)
+                return st, (m_ids, m_dist, m_cnt)
             st = idx.wait_stats(token)  # the counters of exactly this call
-            o = outs[b % depth]
-            return st, (o[0], o[2])
+            return st, outs[b % depth]
 
         def barrier():
             if world > 1:
@@ -533,11 +591,14 @@ def main():
             torch.cuda.synchronize()
 
         def run(first, count, collect):
-            """Runs steps [first, first+count) with `depth` searches in flight."""
+            """Runs steps [first, first+count) with `depth` searches in flight.  collect: copies of every
+            step's ids and counts for the recall check (--full).  Also returns the last step's own output
+            buffers (valid until the next search is submitted)."""
             agg = {"queries": 0, "expansions": 0, "edges": 0, "evals": 0, "pushes": 0,
                    "exact_path": 0, "replayed": 0, "kernel_ms": 0.0, "allocations": 0}
             kept = []
             pending = []
+            res = None
             for s in range(first, first + count):
                 pending.append((s, enqueue(s)))
                 if len(pending) >= depth:
@@ -548,7 +609,7 @@ def main():
                     for f in agg:
                         agg[f] += st[f]
                     if collect and len(kept) < nb_batches:
-                        kept.append((b % nb_batches, res[0].clone(), res[1].clone()))
+                        kept.append((b % nb_batches, res[0].clone(), res[2].clone()))
             while pending:
                 b, tok = pending.pop(0)
                 st, res = finish(b, tok)
@@ -557,8 +618,8 @@ def main():
                 for f in agg:
                     agg[f] += st[f]
                 if collect and len(kept) < nb_batches:
-                    kept.append((b % nb_batches, res[0].clone(), res[1].clone()))
-            return agg, kept
+                    kept.append((b % nb_batches, res[0].clone(), res[2].clone()))
+            return agg, kept, res
 
         trace = None
         # The interpreter's cyclic garbage collector stays out of the timed regions: with torch imported a
@@ -573,15 +634,17 @@ def main():
         # (shard.hip), so every rank gets here; what happened is then agreed on with one all-reduce of a
         # per-rank ok flag instead of assumed.
         failure = None
-        agg, recalls, elapsed = None, [], float("inf")
+        agg, recalls, last, elapsed = None, [], None, float("inf")
         try:
             run(0, args.warmup, False)
             barrier()
             trace = [] if os.environ.get("ISL_BENCH_TRACE") else None  # completion times of the timed steps -> stderr
             t0 = time.perf_counter()
-            agg, recalls = run(args.warmup, args.steps, True)
+            agg, recalls, last = run(args.warmup, args.steps, args.full)
             barrier()
             elapsed = time.perf_counter() - t0
+            # what the caller of the last timed step received, to the host before anything reuses its buffers
+            last = tuple(t.cpu().numpy() for t in last) if args.dump_outputs else None
         except Exception as e:  # noqa: BLE001
             failure = e
         finally:
@@ -613,9 +676,11 @@ def main():
         ref_ids = {b: ids_b for (b, ids_b, cnt_b) in recalls} if not shard_mode else {}
         rec = []
         for (b, ids_b, cnt_b) in recalls:
+            if b not in truths:
+                continue
             truth = g_truth[b] if shard_mode else truths[b][0]
             rec.append(synth.recall_at_k(ids_b, cnt_b, truth))
-        recall = float(np.mean(rec)) if rec else 0.0
+        recall = (float(np.mean(rec)) if rec else 0.0) if args.full else None
         if shard_mode:
             searcher.close()  # communicator, side stream and slots go before the next measurement
 
@@ -644,7 +709,8 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
-            "recall_at_10": round(recall, 4),
+            "full": bool(args.full),
+            "recall_at_10": round(recall, 4) if recall is not None else None,
             "config": {
                 "workload": f"{n_local if args.rehearse_shard else N} x {d} {args.row_dtype} rows resident in HBM (in-memory provider), "
                             + ("hierarchical Gaussian mixture" if args.dataset == "G" else
@@ -685,7 +751,7 @@ def main():
                 "algorithmic_bytes_per_launch": round(bytes_per_launch, 0),
             },
         }
-        if world == 1 and recall < 0.95 and not args.traffic_child and args.ef_sweep:
+        if args.full and world == 1 and recall < 0.95 and not args.traffic_child and args.ef_sweep:
             # "if < 0.95 at ef=128 report the ef that reaches 0.95 and the QPS there" -- one batch
             # per ef, synchronous, up to the traversal kernel's limit (ef <= 512)
             sweep = []
@@ -708,7 +774,7 @@ def main():
                 if r2 >= 0.95:
                     break
             result["ef_sweep"] = sweep
-        if world == 1 and not args.no_host_path and not args.traffic_child:
+        if args.full and world == 1 and not args.no_host_path and not args.traffic_child:
             # QPS by SURVEY 8(d): host buffers in, host buffers out (the caller contract of
             # search.rs:150-181 / indexer/service.rs:781-785), `depth` calls in flight through
             # isl_search_batch_async -- H2D of the queries and D2H of the answers inside the timed
@@ -752,21 +818,23 @@ def main():
                 "ids_equal_device_resident_path": same,
                 "note": "isl_search_batch_async: pageable host queries in, pageable host results out, "
                         "PCIe both ways inside the timed region (SURVEY 8d's QPS definition)"}
-        return result, (x, offsets, neighbours, entry, qsets)
+        return result, (x, offsets, neighbours, entry, qsets), last
 
-    result, (x, offsets, neighbours, entry, qsets) = measure(args.mode)
-    if world > 1 and args.mode == "shard" and not args.no_replica:
+    result, (x, offsets, neighbours, entry, qsets), last = measure(args.mode)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, *last)
+    if args.full and world > 1 and args.mode == "shard" and not args.no_replica:
         # The 10M x 768 index also fits every GPU whole (30.7 GB of 288 GB): the query-parallel
         # deployment (full index per GPU, the batches split across ranks, no collective) is
         # measured next to the sharded one the north star names.
         del x, offsets, neighbours, qsets
         torch.cuda.empty_cache()
-        rep, _ = measure("replica")
+        rep, _, _ = measure("replica")
         result["replica_mode"] = {k_: rep[k_] for k_ in ("value", "unit", "ms_per_step", "scaling", "recall_at_10")}
         result["replica_mode"]["parallelism"] = rep["config"]["parallelism"]
         result["replica_mode"]["roofline_frac_per_gpu"] = rep["roofline"]["frac"]
         x = offsets = neighbours = entry = qsets = None
-    if rank == 0 and world == 1 and not args.no_traffic and not args.traffic_child:
+    if args.full and rank == 0 and world == 1 and not args.no_traffic and not args.traffic_child:
         # HBM bytes per launch of the dominant kernel: this same configuration once more, as a child
         # process under `rocprofv3 --pmc FETCH_SIZE` (its own pass, kernel trace only), one launch
         # in flight so that a dispatch's counter is that launch's.  Failure of any kind -> null.
@@ -777,13 +845,14 @@ def main():
         except Exception as e:
             result["roofline"]["traffic"] = None
             result["roofline"]["traffic_source"] = f"not measured: {e!r}"[:300]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.traffic_child:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.traffic_child:
         try:
             result["cpu_baseline"] = cpu_baseline(x, offsets, neighbours, entry, qsets, k, ef)
         except Exception as e:  # the baseline must never take the measured number down with it
             result["cpu_baseline"] = {"value": None, "unit": "queries/s", "cores": 0,
                                       "kind": "port", "sample": f"failed: {e!r}"}
-    if (rank == 0 and world == 1 and not args.no_neutral_side and not args.traffic_child and args.dataset == "G"
+    if (args.full and rank == 0 and world == 1 and not args.no_neutral_side and not args.traffic_child
+            and args.dataset == "G"
             and args.graph == "harness" and not args.rehearse_shard and args.row_dtype == "f32"):
         # The headline's rows and graph come from one harness (a tree of clusters and a graph built from that
         # tree).  Beside it, in the same line: rows nobody designed a graph for and the graph anybody would build

@@ -42,7 +42,7 @@ def test_gpus_flag_launches_the_ranks_itself_dry_run():
 @pytest.mark.timeout(1200)
 def test_two_ranks_on_one_card_without_a_launcher():
     res = _run(["--gpus", "2", "--nodes", "80000", "--nq", "64", "--steps", "4", "--warmup", "2", "--pipeline", "3",
-                "--no-cpu-baseline", "--no-replica", "--no-traffic"], {"ISL_BENCH_BACKEND": "gloo"})
+                "--full", "--no-cpu-baseline", "--no-replica", "--no-traffic"], {"ISL_BENCH_BACKEND": "gloo"})
     assert res["n_gpus"] == 2
     ex = res["config"]["exchange"]
     assert ex["world"] == 2 and ex["comm_ranks"] == 2 and ex["ranks_completed"] == 2 and ex["rccl"] is False
