@@ -127,6 +127,48 @@ isl_status isl_index_from_device_csr(const isl_leann_config* cfg, int32_t device
 isl_status isl_index_build(const isl_leann_config* cfg, const float* vectors, uint64_t n, uint64_t d,
                            const uint64_t* levels, uint64_t batch, int32_t mem, int32_t device,
                            isl_index** out);
+
+/* ---- extension: a second neighbour-selection rule for the builder ----
+ * ISL_SELECT_REFERENCE is the rule above.  ISL_SELECT_DIVERSE is the occlusion rule (HNSW "select
+ * neighbours by heuristic", Vamana robust prune).  select(b, C, M): walk the candidates C in
+ * ascending d(b, c), ties in their given order; c is occluded iff some s kept before it has
+ * alpha * d(s, c) <= d(b, c) (f32 multiply, then compare; a NaN occludes nothing; d(s, c) =
+ * Distance::calculate(vec[s], vec[c]) in the index's metric); an occluded c goes to `dropped`, any
+ * other to `kept`; stop at M kept.  With keep_pruned, `dropped` then fills the row up to M in its
+ * order.  The row is `kept` followed by the fillers.  The build is otherwise the one above: the new
+ * node i gets select(i, search result, m0) with the search's distances; every selected s that does
+ * not hold i yet gets it appended, and a row that reaches m0 + 1 ids is replaced by select(s, the
+ * row stable-sorted by d(s, .), m0).  high_degree_pruning / hub_percentile are ignored under this
+ * rule.  The rule is not recorded in the index: isl_leann_config and its bytes stay the
+ * reference's, and the result is an ordinary flat CsrGraph. */
+enum { ISL_SELECT_REFERENCE = 0, ISL_SELECT_DIVERSE = 1 };
+typedef struct isl_build_options {
+  uint32_t struct_size; /* sizeof(isl_build_options), for later growth */
+  uint32_t select_rule; /* ISL_SELECT_* */
+  float alpha;          /* finite and >= 1, DIVERSE only */
+  uint32_t keep_pruned; /* 0 / 1, DIVERSE only */
+  uint64_t batch;       /* as isl_index_build's */
+} isl_build_options;
+void isl_build_options_default(isl_build_options* o); /* REFERENCE, 1.0, 1, batch 1 */
+/* isl_index_build with options (NULL = the defaults; isl_index_build is this call with the
+ * default options and its `batch`).  Checked before any device call: struct_size too small or an
+ * unknown rule -> ISL_ERR_INVALID_ARGUMENT; DIVERSE with alpha not finite or < 1 ->
+ * ISL_ERR_INVALID_CONFIG. */
+isl_status isl_index_build_ex(const isl_leann_config* cfg, const isl_build_options* opts,
+                              const float* vectors, uint64_t n, uint64_t d, const uint64_t* levels,
+                              int32_t mem, int32_t device, isl_index** out);
+/* select() of ISL_SELECT_DIVERSE for nb base nodes of an index whose f32 rows are on the device
+ * (bf16 rows or a recompute provider -> ISL_ERR_UNSUPPORTED): cand_ids is [nb][pitch] in any order
+ * (the call computes d(base, c) and stable-sorts), cand_cnt[i] <= min(pitch, 512), cap <= 128;
+ * out_ids [nb][cap], out_cnt [nb].  Host buffers.  The device routine is the builder's.  The call
+ * does not look for the base id or for repeated ids among the candidates: a repeated id is a
+ * second entry at distance 0 from the first.  An id >= the number of rows ->
+ * ISL_ERR_NODE_NOT_FOUND.  opts->select_rule and opts->batch are not used. */
+isl_status isl_select_neighbors(const isl_index* idx, const isl_build_options* opts,
+                                const uint64_t* base_ids, uint64_t nb, const uint64_t* cand_ids,
+                                uint64_t pitch, const uint32_t* cand_cnt, uint64_t cap,
+                                uint64_t* out_ids, uint32_t* out_cnt);
+
 /* LeannIndex::from_bytes / to_bytes, leann.rs:1059-1066 (bincode 1.x default layout). */
 isl_status isl_index_from_bytes(const uint8_t* bytes, size_t len, isl_index** out);
 isl_status isl_index_to_bytes(const isl_index* idx, uint8_t** out, size_t* len);

@@ -133,6 +133,29 @@ class LeannIndex {
     check(isl_index_from_bytes(bytes.data(), bytes.size(), &idx.h_));
     return idx;
   }
+  // LeannIndex::build (leann.rs:560-630) on the device with build options: `vectors` is n rows of
+  // d floats; opts.select_rule = ISL_SELECT_DIVERSE takes the occlusion rule (islands_amd.h).
+  static isl_build_options build_options() {
+    isl_build_options o;
+    isl_build_options_default(&o);
+    return o;
+  }
+  static LeannIndex build(const std::vector<float>& vectors, uint64_t n, uint64_t d, const LeannConfig& cfg,
+                          const isl_build_options& opts = build_options(), const uint64_t* levels = nullptr,
+                          int32_t device = 0) {
+    LeannIndex idx(nullptr);
+    check(isl_index_build_ex(&cfg, &opts, vectors.data(), n, d, levels, ISL_MEM_HOST, device, &idx.h_));
+    return idx;
+  }
+  // select() of the diverse rule for one base node over candidates in any order (isl_select_neighbors)
+  std::vector<uint64_t> select_neighbors(uint64_t base, const std::vector<uint64_t>& candidates, uint64_t cap,
+                                         const isl_build_options& opts = build_options()) const {
+    std::vector<uint64_t> out(cap ? cap : 1);
+    uint32_t cnt = (uint32_t)candidates.size(), n = 0;
+    check(isl_select_neighbors(h_, &opts, &base, 1, candidates.data(), candidates.size(), &cnt, cap, out.data(), &n));
+    out.resize(n);
+    return out;
+  }
   std::vector<uint8_t> to_bytes() const {  // leann.rs:1059
     uint8_t* p = nullptr;
     size_t n = 0;

@@ -16,7 +16,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _ffi
-from ._ffi import BertConfigC, IndexMetadataC, LeannConfigC, SearchStatsC
+from ._ffi import BertConfigC, BuildOptionsC, IndexMetadataC, LeannConfigC, SearchStatsC
 
 __all__ = [
     "CoreError", "DistanceMetric", "PruningStrategy", "LeannConfig", "CsrGraph",
@@ -28,6 +28,8 @@ __all__ = [
 ]
 
 MEM_HOST, MEM_DEVICE = 0, 1
+SELECT_REFERENCE, SELECT_DIVERSE = 0, 1  # ISL_SELECT_*
+_SELECT_RULES = {"reference": SELECT_REFERENCE, "diverse": SELECT_DIVERSE}
 
 
 class CoreError(Exception):
@@ -332,21 +334,64 @@ class LeannIndex:
             0 if dimension is None else 1, dimension or 0, C.byref(h)))
         return cls(_handle=h)
 
+    @staticmethod
+    def _build_options(select, alpha: float, keep_pruned: bool, batch: int = 1) -> BuildOptionsC:
+        """isl_build_options from the keywords of build() / select_neighbors().  `select`: a rule
+        name, an ISL_SELECT_* value, or None = the ISL_BUILD_SELECT variable (default reference)."""
+        if select is None:
+            select = os.environ.get("ISL_BUILD_SELECT") or "reference"
+        if isinstance(select, str):
+            if select.lower() not in _SELECT_RULES:
+                raise ValueError(f"select must be one of {sorted(_SELECT_RULES)}, not {select!r}")
+            select = _SELECT_RULES[select.lower()]
+        o = BuildOptionsC()
+        _ffi.lib().isl_build_options_default(C.byref(o))
+        o.select_rule, o.alpha, o.keep_pruned, o.batch = int(select), float(alpha), int(bool(keep_pruned)), batch
+        return o
+
     @classmethod
     def build(cls, vectors, config: LeannConfig | None = None, levels=None, batch: int = 1,
-              device: int = 0) -> "LeannIndex":
+              device: int = 0, select=None, alpha: float = 1.0, keep_pruned: bool = True) -> "LeannIndex":
         """LeannIndex::build (leann.rs:560-630) on the device; `levels` replaces random_level
         (thread_rng); batch = 1 is the reference's sequential insertion, larger batches insert
-        that many nodes per step.  The vectors become the in-memory provider."""
+        that many nodes per step.  The vectors become the in-memory provider.
+
+        select = "reference" keeps the m0 closest candidates (the reference's rule); "diverse" is
+        the occlusion rule of isl_index_build_ex: a candidate c of base b is dropped when a
+        neighbour s kept before it has alpha * d(s, c) <= d(b, c), and with keep_pruned the
+        dropped ones fill a row that stays short.  None reads ISL_BUILD_SELECT (default
+        "reference").  The rule is not stored in the index or its bytes."""
         v = _f32(vectors)
         n, d = v.shape if v.ndim == 2 else (0, 0)
         c = (config or LeannConfig())._to_c()
         lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint64)
+        o = cls._build_options(select, alpha, keep_pruned, batch)
         h = C.c_void_p()
-        _check(_ffi.lib().isl_index_build(C.byref(c), _ptr(v) if n else None, n, d,
-                                          None if lv is None else _ptr(lv), batch, MEM_HOST, device,
-                                          C.byref(h)))
+        _check(_ffi.lib().isl_index_build_ex(C.byref(c), C.byref(o), _ptr(v) if n else None, n, d,
+                                             None if lv is None else _ptr(lv), MEM_HOST, device,
+                                             C.byref(h)))
         return cls(_handle=h)
+
+    def select_neighbors(self, base_ids, candidates, cap: int, alpha: float = 1.0,
+                         keep_pruned: bool = True, counts=None):
+        """isl_select_neighbors: the diverse rule's select() for every base node over its row of
+        `candidates` ([nb, pitch] ids in any order, `counts[i]` of them used; default all).
+        Returns (ids [nb, cap] u64, count [nb] u32).  Needs float32 rows on the device."""
+        base = np.ascontiguousarray(base_ids, dtype=np.uint64).ravel()
+        cand = np.ascontiguousarray(candidates, dtype=np.uint64)
+        if cand.ndim == 1:
+            cand = cand.reshape(1, -1)
+        nb, pitch = cand.shape
+        if base.size != nb:
+            raise ValueError("one row of candidates per base id")
+        cnt = (np.full(nb, pitch, dtype=np.uint32) if counts is None
+               else np.ascontiguousarray(counts, dtype=np.uint32))
+        o = self._build_options(SELECT_DIVERSE, alpha, keep_pruned)
+        out = np.zeros((nb, max(cap, 1)), dtype=np.uint64)
+        ocnt = np.zeros(nb, dtype=np.uint32)
+        _check(_ffi.lib().isl_select_neighbors(self._h, C.byref(o), _ptr(base), nb, _ptr(cand), pitch,
+                                               _ptr(cnt), cap, _ptr(out), _ptr(ocnt)))
+        return out[:, :cap], ocnt
 
     @classmethod
     def from_device_csr(cls, d_offsets_ptr: int, d_neighbors_ptr: int, num_nodes: int,

@@ -51,6 +51,12 @@ class SearchStatsC(C.Structure):
                 ("encoded_nodes", u64), ("recompute_rounds", u64), ("allocations", u64)]
 
 
+class BuildOptionsC(C.Structure):
+    """isl_build_options: the builder's selection rule and its parameters."""
+    _fields_ = [("struct_size", u32), ("select_rule", u32), ("alpha", f32), ("keep_pruned", u32),
+                ("batch", u64)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/islands_amd.h
 SIGNATURES = {
     "isl_last_error_message": (C.c_char_p, []),
@@ -152,6 +158,11 @@ SIGNATURES = {
                              C.c_void_p]),
     "isl_index_build": (i32, [P(LeannConfigC), C.c_void_p, u64, u64, C.c_void_p, u64, i32, i32,
                               P(C.c_void_p)]),
+    "isl_build_options_default": (None, [P(BuildOptionsC)]),
+    "isl_index_build_ex": (i32, [P(LeannConfigC), P(BuildOptionsC), C.c_void_p, u64, u64, C.c_void_p, i32, i32,
+                                 P(C.c_void_p)]),
+    "isl_select_neighbors": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, C.c_void_p, u64, C.c_void_p,
+                                   u64, C.c_void_p, C.c_void_p]),
     "isl_index_metadata_new": (None, [u64, u64, C.c_int64, P(IndexMetadataC)]),
     "isl_storage_write_metadata": (i32, [P(IndexMetadataC), P(C.c_void_p), P(C.c_size_t)]),
     "isl_storage_read_metadata": (i32, [C.c_void_p, C.c_size_t, P(IndexMetadataC), P(C.c_size_t)]),

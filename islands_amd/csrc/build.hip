@@ -9,9 +9,14 @@
 // an input because random_level draws from thread_rng, :549-554); with larger batches the
 // searches of a step see the graph as of the step's start and the links of a step are applied
 // under per-row locks in an unspecified order -- a throughput mode, same rules, no parity claim.
+//
+// ISL_SELECT_DIVERSE (isl_index_build_ex) swaps the two selections of that loop -- the new node's
+// row and the re-selection of a row that outgrew m0 -- for the occlusion rule defined in
+// include/islands_amd.h; everything else (order, construction search, locks, step ramp) is shared.
 #include "device_common.hip.h"
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 namespace {
@@ -38,7 +43,111 @@ struct BuildParams {
   float hub_percentile;
   uint32_t high_degree;  // LeannConfig::high_degree_pruning
   uint32_t locking;      // batch > 1
+  float alpha;           // ISL_SELECT_DIVERSE: occlusion factor
+  uint32_t keep_pruned;  // ISL_SELECT_DIVERSE: occluded candidates fill a short row
 };
+
+// ---------------------------------------------------------------- ISL_SELECT_DIVERSE
+// What a selection reads besides its lists: the rows and the rule's two parameters.
+struct SelCtx {
+  const float* emb;
+  const float* norm2;
+  uint64_t stride;
+  uint32_t d;
+  float alpha;
+  uint32_t keep_pruned;
+};
+
+// LDS lists of one selection over up to `nmax` candidates, laid out behind the query.
+struct SelState {
+  uint32_t* cid;   // [nmax] candidate ids in ascending d(b, c), ties in their given order
+  float* cd;       // [nmax] d(b, c)
+  uint32_t* lst;   // [nmax] positions still undecided, ascending
+  uint32_t* kept;  // [nmax] 1 = kept
+  uint32_t* out;   // [M] the row: kept, then the fillers
+};
+__device__ __forceinline__ uint32_t query_floats(uint32_t d) { return (d + 3u) / 4u * 4u + 16u; }
+__device__ __forceinline__ SelState sel_state(float* qs, uint32_t d, uint32_t nmax) {
+  uint32_t* w = reinterpret_cast<uint32_t*>(qs + query_floats(d));
+  SelState s;
+  s.cid = w;
+  s.cd = reinterpret_cast<float*>(w + nmax);
+  s.lst = w + 2 * nmax;
+  s.kept = w + 3 * nmax;
+  s.out = w + 4 * nmax;
+  return s;
+}
+
+// The row of node `id` as the query of the distance routines.  norm_a of cosine_distance
+// (distance.rs:78) is the row's own sum of squares in element order, which the index keeps per row
+// (norm2, the value load_query would add up again over d dependent steps).
+template <int METRIC>
+__device__ __forceinline__ float load_row_query(const SelCtx& c, uint32_t id, float* qs) {
+  const float* q = c.emb + (uint64_t)id * c.stride;
+  for (uint32_t j = threadIdx.x; j < c.d; j += 64) qs[j] = q[j];
+  __syncthreads();
+  return (METRIC == ISL_METRIC_COSINE || METRIC == METRIC_COSINE_PRE) ? c.norm2[id] : 0.0f;
+}
+
+// select(b, C, M) of include/islands_amd.h for one wave, turned inside out: a candidate is kept
+// iff no EARLIER KEPT one occludes it, so the head of the undecided list is always kept, its row
+// becomes the query, and one pass of the exact-order distance routine over the rest of the list
+// strikes what it occludes (ballot + prefix count compact the list in place).  At most M rounds
+// over a shrinking list; a round costs what a hop of the search costs per 16 rows.  d(s, c) is
+// calculate(vec[s], vec[c]) through the same chain as every other distance of the library.
+// In: s.cid / s.cd [n] (written by the caller, not yet synchronised).  Out: s.out, count returned.
+template <int METRIC>
+__device__ __forceinline__ uint32_t diverse_select(const SelCtx& c, uint32_t n, uint32_t M,
+                                                   const SelState& s, float* qs, float* tile) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t below = (1ull << lane) - 1ull;
+  for (uint32_t i = lane; i < n; i += 64) { s.lst[i] = i; s.kept[i] = 0u; }
+  __syncthreads();
+  uint32_t nl = n, nk = 0;
+  while (nl > 0 && nk < M) {
+    const uint32_t a = s.lst[0];
+    const uint32_t aid = s.cid[a];
+    if (lane == 0) { s.out[nk] = aid; s.kept[a] = 1u; }
+    nk += 1;
+    if (nk == M) break;
+    if (nl == 1) { nl = 0; break; }
+    __syncthreads();
+    const float q_norm = load_row_query<METRIC>(c, aid, qs);
+    uint32_t nn = 0;
+    for (uint32_t base = 1; base < nl; base += 64) {
+      const uint32_t cnt = nl - base < 64u ? nl - base : 64u;
+      const bool valid = lane < cnt;
+      const uint32_t pos = valid ? s.lst[base + lane] : 0u;
+      const uint32_t rid = valid ? s.cid[pos] : aid;
+      const float aux = (METRIC == METRIC_COSINE_PRE && valid) ? c.norm2[rid] : 0.0f;
+      const float ds = wave_distances<METRIC>(c.emb, c.stride, c.d, rid, cnt, qs, tile, q_norm, aux);
+      // occluded: alpha * d(s, c) <= d(b, c), separate roundings; false for a NaN on either side
+      const bool stays = valid && !(c.alpha * ds <= s.cd[pos]);
+      const uint64_t m = ballot(stays);
+      // survivors of list slots 1 .. base + lane land at or below slot base + lane - 1, and every
+      // lane has read its slot already: the list is compacted in place
+      if (stays) s.lst[nn + (uint32_t)__popcll(m & below)] = pos;
+      nn += (uint32_t)__popcll(m);
+      __syncthreads();
+    }
+    nl = nn;
+  }
+  if (c.keep_pruned && nk < M) {
+    // the list ran empty, so every candidate is decided: `dropped` is whatever is not kept
+    __syncthreads();
+    for (uint32_t base = 0; base < n && nk < M; base += 64) {
+      const uint32_t i = base + lane;
+      const bool dr = i < n && s.kept[i] == 0u;
+      const uint64_t m = ballot(dr);
+      const uint32_t at = nk + (uint32_t)__popcll(m & below);
+      if (dr && at < M) s.out[at] = s.cid[i];
+      nk += (uint32_t)__popcll(m);
+      nk = nk < M ? nk : M;
+    }
+  }
+  __syncthreads();
+  return nk;
+}
 
 // prune_with_degree_preservation_temp, leann.rs:761-833, for one new node per wave.
 __global__ __launch_bounds__(64) void select_kernel(BuildParams p) {
@@ -104,8 +213,87 @@ __global__ __launch_bounds__(64) void select_kernel(BuildParams p) {
   if (lane == 0) p.sel_cnt[b] = nsel;
 }
 
-// adjacency.push(neighbors) + bidirectional links + prune_neighbors_temp, leann.rs:592-607, 634-658
+__device__ __forceinline__ SelCtx sel_ctx(const BuildParams& p) {
+  return SelCtx{p.emb, p.norm2, p.stride, p.d, p.alpha, p.keep_pruned};
+}
+
+// ISL_SELECT_DIVERSE for one new node per wave: select(node, search result, m0), with the search's
+// distances as d(node, c).
 template <int METRIC_API>
+__global__ __launch_bounds__(64) void select_diverse_kernel(BuildParams p) {
+  constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
+  extern __shared__ __align__(16) unsigned char smem[];
+  float* tile = reinterpret_cast<float*>(smem);
+  float* qs = tile + TILE_ROWS * TILE_LD;
+  const SelState s = sel_state(qs, p.d, p.ef);
+  const uint32_t lane = threadIdx.x, b = blockIdx.x;
+  const uint32_t n = p.cand_cnt[b] < p.ef ? p.cand_cnt[b] : p.ef;
+  const uint64_t* cid = p.cand_ids + (uint64_t)b * p.ef;
+  const float* cdist = p.cand_dist + (uint64_t)b * p.ef;
+  for (uint32_t i = lane; i < n; i += 64) {
+    s.cid[i] = (uint32_t)cid[i];
+    s.cd[i] = cdist[i];
+  }
+  const uint32_t nsel = diverse_select<METRIC>(sel_ctx(p), n, p.m0, s, qs, tile);
+  uint32_t* out = p.sel + (uint64_t)b * p.m0;
+  for (uint32_t i = lane; i < nsel; i += 64) out[i] = s.out[i];
+  if (lane == 0) p.sel_cnt[b] = nsel;
+}
+
+// isl_select_neighbors: d(base, c) for the candidates as given, a stable sort by it (the total
+// order of ordkey: NaN last, -0 == +0), then the builder's routine.
+struct SelectNeighborsParams {
+  SelCtx c;
+  const uint32_t* base_ids;  // [nb]
+  const uint32_t* cand;      // [nb][pitch]
+  const uint32_t* cand_cnt;  // [nb]
+  uint32_t pitch, cap, nmax;
+  uint32_t* out;             // [nb][cap]
+  uint32_t* out_cnt;         // [nb]
+};
+template <int METRIC_API>
+__global__ __launch_bounds__(64) void select_neighbors_kernel(SelectNeighborsParams p) {
+  constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
+  extern __shared__ __align__(16) unsigned char smem[];
+  float* tile = reinterpret_cast<float*>(smem);
+  float* qs = tile + TILE_ROWS * TILE_LD;
+  const SelState s = sel_state(qs, p.c.d, p.nmax);
+  const uint32_t lane = threadIdx.x, b = blockIdx.x;
+  const uint32_t n = p.cand_cnt[b] < p.nmax ? p.cand_cnt[b] : p.nmax;
+  const uint32_t* cand = p.cand + (uint64_t)b * p.pitch;
+  // the two lists the selection initialises itself hold the unsorted entries until then
+  uint32_t* raw_id = s.lst;
+  float* raw_d = reinterpret_cast<float*>(s.kept);
+  const float q_norm = load_row_query<METRIC>(p.c, p.base_ids[b], qs);
+  for (uint32_t base = 0; base < n; base += 64) {
+    const uint32_t cnt = n - base < 64u ? n - base : 64u;
+    const bool valid = lane < cnt;
+    const uint32_t rid = valid ? cand[base + lane] : p.base_ids[b];
+    const float aux = (METRIC == METRIC_COSINE_PRE && valid) ? p.c.norm2[rid] : 0.0f;
+    const float ds = wave_distances<METRIC>(p.c.emb, p.c.stride, p.c.d, rid, cnt, qs, tile, q_norm, aux);
+    if (valid) { raw_id[base + lane] = rid; raw_d[base + lane] = ds; }
+  }
+  __syncthreads();
+  for (uint32_t i = lane; i < n; i += 64) {
+    const uint32_t ki = ordkey(raw_d[i]);
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+      const uint32_t kj = ordkey(raw_d[j]);
+      r += (kj < ki) || (kj == ki && j < i);
+    }
+    s.cid[r] = raw_id[i];
+    s.cd[r] = raw_d[i];
+  }
+  __syncthreads();
+  const uint32_t nsel = diverse_select<METRIC>(p.c, n, p.cap, s, qs, tile);
+  uint32_t* out = p.out + (uint64_t)b * p.cap;
+  for (uint32_t i = lane; i < nsel; i += 64) out[i] = s.out[i];
+  if (lane == 0) p.out_cnt[b] = nsel;
+}
+
+// adjacency.push(neighbors) + bidirectional links + prune_neighbors_temp, leann.rs:592-607, 634-658
+// DIVERSE: a row that outgrew m0 is re-selected by the occlusion rule instead of cut at m0.
+template <int METRIC_API, bool DIVERSE = false>
 __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
   constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -152,7 +340,13 @@ __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
             dist[c] = wave_distances<METRIC>(p.emb, p.stride, p.d, rid[c], cnt, qs, tile, q_norm, aux);
           }
         }
-        // stable sort by distance (`<` only, leann.rs:650): rank of every entry among all dg
+        // stable sort by distance (`<` only, leann.rs:650): rank of every entry among all dg.
+        // The diverse rule scatters by rank, so there the ranks must be a permutation whatever
+        // the values: it compares through ordkey (the same order, with NaN as one greatest value).
+        auto lt = [](float x, float y) {
+          if constexpr (DIVERSE) return ordkey(x) < ordkey(y);
+          else return x < y;
+        };
         uint32_t rank[CH] = {0, 0, 0};
 #pragma unroll
         for (int ci = 0; ci < CH; ++ci) {
@@ -164,15 +358,25 @@ __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
 #pragma unroll
             for (int c = 0; c < CH; ++c) {
               const uint32_t me = 64u * c + lane;
-              rank[c] += (di < dist[c]) || (!(dist[c] < di) && !(di < dist[c]) && i < me);
+              rank[c] += lt(di, dist[c]) || (!lt(dist[c], di) && !lt(di, dist[c]) && i < me);
             }
           }
         }
         __syncthreads();
+        if constexpr (DIVERSE) {
+          const SelState s = sel_state(qs, p.d, p.W);
 #pragma unroll
-        for (int c = 0; c < CH; ++c)
-          if (64u * c + lane < dg && rank[c] < p.m0) row[rank[c]] = rid[c];
-        dg = p.m0;
+          for (int c = 0; c < CH; ++c)
+            if (64u * c + lane < dg) { s.cid[rank[c]] = rid[c]; s.cd[rank[c]] = dist[c]; }
+          const uint32_t nk = diverse_select<METRIC>(sel_ctx(p), dg, p.m0, s, qs, tile);
+          for (uint32_t i = lane; i < nk; i += 64) row[i] = s.out[i];
+          dg = nk;
+        } else {
+#pragma unroll
+          for (int c = 0; c < CH; ++c)
+            if (64u * c + lane < dg && rank[c] < p.m0) row[rank[c]] = rid[c];
+          dg = p.m0;
+        }
       }
       if (lane == 0) *((volatile uint32_t*)&p.ell_deg[nid]) = dg;
     }
@@ -200,22 +404,89 @@ __global__ void gather_rows_kernel(const float* __restrict__ emb, uint64_t strid
   out[i] = emb[(id0 + i / d) * stride + i % d];
 }
 
-void launch_link(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  switch (metric) {
-    case ISL_METRIC_COSINE: hipLaunchKernelGGL(link_kernel<ISL_METRIC_COSINE>, dim3(grid), dim3(64), lds, 0, p); break;
-    case ISL_METRIC_EUCLIDEAN: hipLaunchKernelGGL(link_kernel<ISL_METRIC_EUCLIDEAN>, dim3(grid), dim3(64), lds, 0, p); break;
-    case ISL_METRIC_DOT: hipLaunchKernelGGL(link_kernel<ISL_METRIC_DOT>, dim3(grid), dim3(64), lds, 0, p); break;
-    default: hipLaunchKernelGGL(link_kernel<ISL_METRIC_MANHATTAN>, dim3(grid), dim3(64), lds, 0, p); break;
+// bytes of LDS behind the tile: the query (and its slack) plus the lists of a selection
+size_t sel_lds(uint64_t d, uint32_t nmax, uint32_t M) {
+  return (size_t)TILE_ROWS * TILE_LD * 4 + (size_t)((d + 3) / 4 * 4) * 4 + 64 + (size_t)nmax * 16 + (size_t)M * 4;
+}
+
+#define ISL_LAUNCH_BY_METRIC(metric, K0, K1, K2, K3, ...)               \
+  switch (metric) {                                                     \
+    case ISL_METRIC_COSINE: hipLaunchKernelGGL(K0, __VA_ARGS__); break;    \
+    case ISL_METRIC_EUCLIDEAN: hipLaunchKernelGGL(K1, __VA_ARGS__); break; \
+    case ISL_METRIC_DOT: hipLaunchKernelGGL(K2, __VA_ARGS__); break;       \
+    default: hipLaunchKernelGGL(K3, __VA_ARGS__); break;                   \
   }
+
+void launch_link(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  ISL_LAUNCH_BY_METRIC(metric, link_kernel<ISL_METRIC_COSINE>, link_kernel<ISL_METRIC_EUCLIDEAN>,
+                       link_kernel<ISL_METRIC_DOT>, link_kernel<ISL_METRIC_MANHATTAN>, dim3(grid), dim3(64), lds, 0, p)
+}
+
+void launch_link_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  ISL_LAUNCH_BY_METRIC(metric, (link_kernel<ISL_METRIC_COSINE, true>), (link_kernel<ISL_METRIC_EUCLIDEAN, true>),
+                       (link_kernel<ISL_METRIC_DOT, true>), (link_kernel<ISL_METRIC_MANHATTAN, true>), dim3(grid),
+                       dim3(64), lds, 0, p)
+}
+
+void launch_select_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  ISL_LAUNCH_BY_METRIC(metric, select_diverse_kernel<ISL_METRIC_COSINE>, select_diverse_kernel<ISL_METRIC_EUCLIDEAN>,
+                       select_diverse_kernel<ISL_METRIC_DOT>, select_diverse_kernel<ISL_METRIC_MANHATTAN>, dim3(grid),
+                       dim3(64), lds, 0, p)
+}
+
+void launch_select_neighbors(int metric, uint32_t grid, size_t lds, const SelectNeighborsParams& p) {
+  ISL_LAUNCH_BY_METRIC(metric, select_neighbors_kernel<ISL_METRIC_COSINE>, select_neighbors_kernel<ISL_METRIC_EUCLIDEAN>,
+                       select_neighbors_kernel<ISL_METRIC_DOT>, select_neighbors_kernel<ISL_METRIC_MANHATTAN>, dim3(grid),
+                       dim3(64), lds, 0, p)
+}
+#undef ISL_LAUNCH_BY_METRIC
+
+// struct_size, rule and alpha of caller-supplied options, before any device call
+isl_status check_build_options(const isl_build_options* o, bool need_rule) {
+  using isl::fail;
+  if (o->struct_size < sizeof(isl_build_options))
+    return fail(ISL_ERR_INVALID_ARGUMENT, "isl_build_options.struct_size %u is smaller than %zu", o->struct_size,
+                sizeof(isl_build_options));
+  if (need_rule && o->select_rule != ISL_SELECT_REFERENCE && o->select_rule != ISL_SELECT_DIVERSE)
+    return fail(ISL_ERR_INVALID_ARGUMENT, "unknown selection rule %u", o->select_rule);
+  if ((!need_rule || o->select_rule == ISL_SELECT_DIVERSE) && !(std::isfinite(o->alpha) && o->alpha >= 1.0f))
+    return fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: alpha must be finite and >= 1");
+  return ISL_OK;
 }
 
 }  // namespace
 
-extern "C" isl_status isl_index_build(const isl_leann_config* cfg_in, const float* vectors, uint64_t n,
-                                      uint64_t d, const uint64_t* levels, uint64_t batch, int32_t mem,
-                                      int32_t device, isl_index** out) {
+extern "C" void isl_build_options_default(isl_build_options* o) {
+  if (!o) return;
+  o->struct_size = (uint32_t)sizeof(isl_build_options);
+  o->select_rule = ISL_SELECT_REFERENCE;
+  o->alpha = 1.0f;
+  o->keep_pruned = 1;
+  o->batch = 1;
+}
+
+extern "C" isl_status isl_index_build(const isl_leann_config* cfg, const float* vectors, uint64_t n, uint64_t d,
+                                      const uint64_t* levels, uint64_t batch, int32_t mem, int32_t device,
+                                      isl_index** out) {
+  isl_build_options o;
+  isl_build_options_default(&o);
+  o.batch = batch;
+  return isl_index_build_ex(cfg, &o, vectors, n, d, levels, mem, device, out);
+}
+
+extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg_in, const isl_build_options* opts_in,
+                                         const float* vectors, uint64_t n, uint64_t d, const uint64_t* levels,
+                                         int32_t mem, int32_t device, isl_index** out) {
   using isl::fail;
   if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  isl_build_options opts;
+  isl_build_options_default(&opts);
+  if (opts_in) {
+    ISL_TRY(check_build_options(opts_in, true));
+    opts = *opts_in;
+  }
+  const bool diverse = opts.select_rule == ISL_SELECT_DIVERSE;
+  uint64_t batch = opts.batch;
   isl_leann_config cfg;
   if (cfg_in) cfg = *cfg_in;
   else isl_leann_config_paper_default(&cfg);
@@ -274,6 +545,7 @@ extern "C" isl_status isl_index_build(const isl_leann_config* cfg_in, const floa
   p.ell = ell; p.ell_deg = ell_deg; p.lock = lock; p.W = W; p.m0 = m0; p.ef = ef;
   p.cand_ids = cand_ids; p.cand_dist = cand_dist; p.cand_cnt = cand_cnt; p.sel = sel; p.sel_cnt = sel_cnt;
   p.hub_percentile = cfg.hub_percentile; p.high_degree = cfg.high_degree_pruning;
+  p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
   const size_t link_lds = (size_t)TILE_ROWS * TILE_LD * 4 + (size_t)((d + 3) / 4 * 4) * 4 + 64;
 
   bool has_entry = false;
@@ -298,8 +570,13 @@ extern "C" isl_status isl_index_build(const isl_leann_config* cfg_in, const floa
     p.id0 = id0;
     p.B = (uint32_t)nb;
     p.locking = nb > 1;
-    hipLaunchKernelGGL(select_kernel, dim3((uint32_t)nb), dim3(64), (size_t)ef * 12, 0, p);
-    launch_link((int)cfg.metric, (uint32_t)nb, link_lds, p);
+    if (diverse) {
+      launch_select_diverse((int)cfg.metric, (uint32_t)nb, sel_lds(d, ef, m0), p);
+      launch_link_diverse((int)cfg.metric, (uint32_t)nb, sel_lds(d, W, m0), p);
+    } else {
+      hipLaunchKernelGGL(select_kernel, dim3((uint32_t)nb), dim3(64), (size_t)ef * 12, 0, p);
+      launch_link((int)cfg.metric, (uint32_t)nb, link_lds, p);
+    }
     if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
       return bail2(fail(ISL_ERR_DEVICE, "builder kernels failed"));
     for (uint64_t i = 0; i < nb; ++i) note_level(id0 + i);
@@ -333,4 +610,76 @@ extern "C" isl_status isl_index_build(const isl_leann_config* cfg_in, const floa
   isl_index_free(g);
   *out = res;
   return ISL_OK;
+}
+
+extern "C" isl_status isl_select_neighbors(const isl_index* idx, const isl_build_options* opts_in,
+                                           const uint64_t* base_ids, uint64_t nb, const uint64_t* cand_ids,
+                                           uint64_t pitch, const uint32_t* cand_cnt, uint64_t cap,
+                                           uint64_t* out_ids, uint32_t* out_cnt) {
+  using isl::fail;
+  if (!idx || (nb && (!base_ids || !cand_cnt || !out_ids || !out_cnt || (!cand_ids && pitch))))
+    return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  isl_build_options opts;
+  isl_build_options_default(&opts);
+  if (opts_in) {
+    ISL_TRY(check_build_options(opts_in, false));
+    opts = *opts_in;
+  }
+  if (cap == 0 || cap > 128) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: 1 <= cap <= 128");
+  if (nb == 0) return ISL_OK;
+  if (nb > 0x7FFFFFFFull) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: too many base nodes");
+  if (idx->recompute || idx->d_emb16 || !idx->d_emb || idx->device < 0)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors needs float32 rows resident on the device");
+  uint32_t nmax = 1;
+  for (uint64_t i = 0; i < nb; ++i) {
+    if (cand_cnt[i] > 512 || cand_cnt[i] > pitch)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: cand_cnt <= min(pitch, 512)");
+    nmax = std::max(nmax, cand_cnt[i]);
+  }
+  // ids leave the host as the 32-bit ids of the device tables
+  std::vector<uint32_t> hbase(nb), hcand((size_t)nb * nmax, 0u);
+  for (uint64_t i = 0; i < nb; ++i) {
+    if (base_ids[i] >= idx->nvec) return isl::fail_node(base_ids[i]);
+    hbase[i] = (uint32_t)base_ids[i];
+    for (uint32_t j = 0; j < cand_cnt[i]; ++j) {
+      const uint64_t c = cand_ids[i * pitch + j];
+      if (c >= idx->nvec) return isl::fail_node(c);
+      hcand[(size_t)i * nmax + j] = (uint32_t)c;
+    }
+  }
+  ISL_TRY(isl::use_device(idx->device));
+  std::vector<void*> tmp;
+  auto dalloc = [&](size_t bytes) -> void* {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
+    tmp.push_back(p);
+    return p;
+  };
+  auto done = [&](isl_status s) { for (void* p : tmp) (void)hipFree(p); return s; };
+  uint32_t* d_base = (uint32_t*)dalloc(nb * 4);
+  uint32_t* d_cand = (uint32_t*)dalloc((size_t)nb * nmax * 4);
+  uint32_t* d_cnt = (uint32_t*)dalloc(nb * 4);
+  uint32_t* d_out = (uint32_t*)dalloc((size_t)nb * cap * 4);
+  uint32_t* d_ocnt = (uint32_t*)dalloc(nb * 4);
+  if (!d_base || !d_cand || !d_cnt || !d_out || !d_ocnt)
+    return done(fail(ISL_ERR_DEVICE, "hipMalloc failed for isl_select_neighbors"));
+  if (hipMemcpy(d_base, hbase.data(), nb * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_cand, hcand.data(), (size_t)nb * nmax * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_cnt, cand_cnt, nb * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemset(d_out, 0, (size_t)nb * cap * 4) != hipSuccess)
+    return done(fail(ISL_ERR_DEVICE, "cannot stage the candidates"));
+  SelectNeighborsParams p{};
+  p.c = SelCtx{idx->d_emb, idx->d_norm2, idx->emb_stride, (uint32_t)idx->emb_d, opts.alpha, opts.keep_pruned ? 1u : 0u};
+  p.base_ids = d_base; p.cand = d_cand; p.cand_cnt = d_cnt;
+  p.pitch = nmax; p.cap = (uint32_t)cap; p.nmax = nmax;
+  p.out = d_out; p.out_cnt = d_ocnt;
+  launch_select_neighbors((int)idx->cfg.metric, (uint32_t)nb, sel_lds(idx->emb_d, nmax, (uint32_t)cap), p);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return done(fail(ISL_ERR_DEVICE, "select_neighbors kernel failed"));
+  std::vector<uint32_t> hout((size_t)nb * cap);
+  if (hipMemcpy(hout.data(), d_out, (size_t)nb * cap * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(out_cnt, d_ocnt, nb * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return done(fail(ISL_ERR_DEVICE, "cannot read the selection back"));
+  for (size_t i = 0; i < hout.size(); ++i) out_ids[i] = hout[i];
+  return done(ISL_OK);
 }
