@@ -132,20 +132,10 @@ struct SearchWorkspace {
   uint32_t* uslots = nullptr;    // [miss_cap] slab slots of the round's unique misses
   uint64_t qlist_cap = 0;
   uint32_t* xslot = nullptr;     // [qlist_cap] 1 + pool slot of a query parked in the heap-exact kernel
-  uint32_t* h_xlist = nullptr;   // [64] pinned: the parked queries the next round hands to that kernel directly
-  uint32_t round_x = 0;          // ... how many
-  bool round_xpark = false;      // this call's queries park in the heap-exact kernel (bounded row cache)
-  // the round search_sync is about to enqueue (recompute provider): 0 = an ordinary launch over
-  // all queries; otherwise the RESUME kernel over `round_active` queries, listed in qlist unless
-  // it is the first round
-  uint32_t round_active = 0;
-  uint32_t round_prefetch = 0;  // two-level search: ids a parked query names beyond its misses (0 = none)
-  bool round_listed = false;
+  uint32_t* h_xlist = nullptr;   // [qlist_cap] pinned: the parked queries the next round hands to that kernel directly
   // two-level search: per-query PQ distance tables [nq][m * K]
   float* tl_tables = nullptr;
   uint64_t tl_tables_cap = 0;
-  bool tl_tables_built = false;  // ... of the call in flight (its later rounds / retries reuse them)
-  uint32_t retry_count = 0;      // two-level search: queries re-run alone with a larger queue window (listed in qlist)
   // Asynchronous calls that cannot be split into "enqueue now, finish at wait" -- the rounds of the
   // recompute provider, the two-level search with its per-query retries -- run their synchronous form
   // on a host thread of their own; whoever waits for the token joins it and takes its status and

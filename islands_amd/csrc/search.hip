@@ -22,84 +22,9 @@
 //   * exact kernel: emulates Rust's BinaryHeap push/pop/into_iter byte for byte (candidates in
 //     HBM scratch, results in LDS) for those queries, for ef > 512, for adjacency rows longer
 //     than 64 and for NaN / -0.0 distances.
-#include "search_kernels.hip.h"
+#include "search_geometry.hpp"
 
 namespace {
-
-struct FastGeom {
-  uint32_t hbits;  // the table ef (and a long query) alone give: 1 << hbits entries; what parked queries' state blocks hold
-  size_t lds;
-  uint32_t hcap;   // entries of the table this launch runs with (1 << hbits unless the index's hint enlarged it)
-};
-
-// qbytes = bytes per query element in LDS: 4, or 2 for the instantiation that keeps a bf16-valued
-// query as bf16 (bf16 rows; at d = 4096 the query is what bounds the waves per CU)
-// vhint = distance evaluations per query this index's searches have been making (0 = unknown): every
-// evaluated node is an entry of the visited table.
-FastGeom fast_geometry(uint32_t ef, uint32_t d, uint32_t qbytes = 4, uint32_t vhint = 0) {
-  // visited capacity grows with ef (V is roughly 10-30 x ef); overflow goes to HBM
-  uint32_t hbits = ef <= 64 ? 10 : ef <= 160 ? 11 : ef <= 320 ? 12 : 13;
-  static const int hbits_env = [] { const char* e = getenv("ISL_HBITS"); return e ? atoi(e) : 0; }();
-  // A long query takes most of a wave's LDS (d = 4096: 16 KB as float32, 8 KB as bf16) and the waves
-  // per CU with it; once it is at least as large as the visited table, half a table buys more
-  // through occupancy than it costs through the overflow table in HBM (10M x 4096 bf16 rows,
-  // ef = 128: 0.40 -> 0.45 of the HBM peak).  At d = 768 the full table wins and stays.
-  const size_t qlds = (size_t)d * qbytes;
-  if (qlds >= ((size_t)4 << hbits) && hbits > 9) hbits -= 1;
-  // visited table, merge buffer, query (+ 64 bytes when d is not a multiple of 16: the operand
-  // prefetch of direct_group may touch the rest of the last step)
-  const size_t rest = (size_t)mbuf_entries(ef) * 8 +
-                      (qbytes == 2 ? (size_t)((d + 7) / 8 * 8) * 2 + 64 : (size_t)((d + 3) / 4 * 4) * 4 + ((d & 15) ? 64 : 0));
-  if (hbits_env >= 8 && hbits_env <= 14) hbits = (uint32_t)hbits_env;  // experiments only
-  uint32_t hcap = 1u << hbits;
-  // Round 4: a larger table when the index's queries have been filling it past its 7/8 limit on average.
-  // How many nodes a query evaluates is a property of the graph and the data, not of ef alone (ef = 128: 1226
-  // on the tree-of-clusters rows with the harness graph, 3100-3400 on manifold rows with an exact-kNN graph),
-  // and a query past the limit pays an atomic round trip to its HBM overflow table for every further hop:
-  // measured on the latter rows (1M x 768, 20 steps, profiles/r04_bench_M_knn_1m_hbits{11,12,13}.json)
-  // 2048 entries 558 k queries/s, 4096 entries 686 k (12 -> 7 waves per CU and still +23 %), 8192 entries 602 k.
-  // The table need not be a power of two (hslot_cap): it takes what the average query needs, in steps of 512
-  // entries and at most four times the default, and then whatever else fits beside the same number of waves per CU.
-  static const bool no_hint = getenv("ISL_NO_VISITED_HINT") != nullptr;  // A/B switch for measurements
-  static const int hcap_env = [] { const char* e = getenv("ISL_HCAP"); return e ? atoi(e) : 0; }();  // experiments only
-  if (vhint && !no_hint && hbits_env == 0) {
-    const uint64_t need = ((uint64_t)vhint * 8 + 6) / 7;
-    if (need > hcap) {
-      const uint64_t most = (uint64_t)4 << hbits;  // (2 x until the densest graph of DESIGN section 4: 4096 entries 357 k, 5696 420 k queries/s)
-      uint64_t want = std::min<uint64_t>((need + 511) / 512 * 512, most);
-      auto lds_of = [&](uint64_t cap) { return (cap * 4 + rest + 511) / 512 * 512; };  // (LDS is handed out in 512-byte granules)
-      auto room = [&](size_t waves) -> uint64_t {  // the largest table that leaves `waves` waves per CU
-        const size_t each = (160 * 1024) / waves / 512 * 512;
-        return each > rest ? std::min<uint64_t>((each - rest) / 4 / 64 * 64, most) : 0;
-      };
-      const size_t per_cu = std::max<size_t>(1, (160 * 1024) / lds_of(want));
-      want = std::max(want, room(per_cu));           // what fits beside the same waves is free
-      if (room(per_cu + 1) >= need) want = room(per_cu + 1);  // one more wave per CU if the average query still fits
-      hcap = (uint32_t)want;
-    }
-  }
-  if (hcap_env >= 256 && hcap_env <= 16384) hcap = (uint32_t)hcap_env / 64 * 64;
-  const size_t lds = (size_t)hcap * 4 + rest;
-  return {hbits, lds, hcap};
-}
-
-
-size_t exact_lds(uint32_t ef, uint32_t d) {
-  return (size_t)TILE_ROWS * TILE_LD * 4 + 64 * 4 + 64 * 4 + 8 * 4 + (size_t)(ef + 1) * 8 + 16 +
-         (size_t)((d + 3) / 4 * 4) * 4;
-}
-
-// Two-level search: LDS of one wave = visited table + approximate-queue window + R + staging + query
-struct TwoLevelCall {
-  float ratio;
-  uint32_t window_scale = 1;  // the window grows 4x per retry after a query outgrew it
-};
-// qbytes = 2: the instantiation that keeps a bf16-valued query as bf16 (bf16 rows)
-size_t two_level_lds(uint32_t hbits, uint32_t wcap, uint32_t ef, uint32_t d, uint32_t qbytes = 4) {
-  return ((size_t)4 << hbits) + (size_t)(wcap + 64) * 8 + (size_t)tl_res_entries(ef) * 8 + 64 * 8 +
-         128 * 4 + (size_t)kTlLdsWords * 4 +
-         (qbytes == 2 ? (size_t)((d + 7) / 8 * 8) * 2 + 64 : (size_t)((d + 3) / 4 * 4) * 4 + ((d & 15) ? 64 : 0));
-}
 
 __global__ void fill_u32_kernel(uint32_t* p, uint64_t n, uint32_t v) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -147,7 +72,6 @@ __global__ void seed_redo_kernel(const uint32_t* __restrict__ list, uint32_t n, 
 constexpr uint32_t kExactSlots = 32;
 constexpr uint32_t kTlPrefetchDefault = 0;  // (set from the measurement: DESIGN.md section 3.4)
 constexpr uint32_t kOvfBits = 15;
-constexpr uint32_t kMaxExactEf = 4096;
 
 // Every allocation of the search path goes through these: a lane counts what it had to set up,
 // and a call reports its share in isl_search_stats::allocations (0 once isl_index_prepare has run).
@@ -175,16 +99,6 @@ isl_status ensure(isl::SearchWorkspace& ws, T*& ptr, uint64_t& have, uint64_t wa
   have = want;
   return ISL_OK;
 }
-
-// resident waves per CU the launch geometry may count on (ISL_WAVES_PER_CU: experiments only)
-size_t waves_per_cu_cap() {
-  static const size_t cap = [] {
-    const char* wc = getenv("ISL_WAVES_PER_CU");
-    return wc ? (size_t)std::max(1, atoi(wc)) : (size_t)16;
-  }();
-  return cap;
-}
-uint32_t push_log_cap(uint32_t ef) { return std::max<uint32_t>(1024, 12 * ef); }  // pushes per query ~ 3-6 x ef
 
 // Streams, events, per-query arrays, overflow table, push log of one lane, sized for nq queries
 // on `slots` resident waves.
@@ -220,8 +134,7 @@ isl_status ensure_lane_stream(const isl_index* idx, isl::SearchWorkspace& ws) {
   hipStream_t st = pool_stream(idx->device, (uint32_t)(&ws - idx->ws), &created);
   if (!st) return isl::fail(ISL_ERR_DEVICE, "hipStreamCreate failed for a search lane");
   if (created) ws.alloc_events++;
-  static const bool no_evdone = getenv("ISL_NO_EVDONE") != nullptr;  // A/B switch for measurements (stream synchronisation instead)
-  if (!ws.ev_done && !no_evdone) { ISL_HIP(hipEventCreateWithFlags(&ws.ev_done, hipEventDisableTiming)); ws.alloc_events++; }
+  if (!ws.ev_done) { ISL_HIP(hipEventCreateWithFlags(&ws.ev_done, hipEventDisableTiming)); ws.alloc_events++; }
   if (!ws.ev0) { ISL_HIP(hipEventCreate(&ws.ev0)); ws.alloc_events++; }
   if (!ws.ev1) { ISL_HIP(hipEventCreate(&ws.ev1)); ws.alloc_events++; }
   if (!ws.ev_in) { ISL_HIP(hipEventCreateWithFlags(&ws.ev_in, hipEventDisableTiming)); ws.alloc_events++; }
@@ -382,70 +295,6 @@ __global__ void pad_rows_kernel(const uint64_t* __restrict__ off, const uint32_t
 // overlap (asynchronous entry point).
 enum class StreamMode { OWN, USER, OWN_AFTER_USER };
 
-// Launch geometry of one call: which kernel answers it and what its lane must hold.
-struct CallGeometry {
-  uint32_t ef = 0;
-  bool use_fast = false;
-  FastGeom fg{};
-  uint32_t slots = 0;      // resident waves of the launch
-  uint32_t vhint = 0;      // evaluations per query the visited table was sized for (0 = by ef alone)
-  uint32_t plog_cap = 0;
-  uint32_t tl_wcap = 0;
-  size_t tl_lds = 0;
-  uint32_t tl_hbits_q = 0;   // the bf16-query instantiation: visited-table bits, LDS, resident waves
-  size_t tl_lds_q = 0;
-  uint32_t tl_slots_q = 0;
-};
-
-isl_status call_geometry(const isl_index* idx, uint64_t d, uint64_t k, uint64_t ef_in, const TwoLevelCall* tl,
-                         CallGeometry& g) {
-  g.ef = (uint32_t)std::min<uint64_t>(std::max(ef_in, k), 0xFFFFFFFFull);  // leann.rs:890
-  if (std::max(ef_in, k) > kMaxExactEf)
-    return isl::fail(ISL_ERR_UNSUPPORTED, "ef = %llu exceeds the device limit %u",
-                     (unsigned long long)std::max(ef_in, k), kMaxExactEf);
-  const uint32_t ef = g.ef;
-  const int ncu = isl::device_cu_count(idx->device);
-  // (searches over the recompute provider park their visited table in state blocks sized by ef alone; the
-  // two-level search sizes its own LDS: neither takes the hint)
-  g.vhint = 0;
-  if (!tl && !idx->recompute) {  // (the evaluations of a call with another ef say nothing about this one)
-    const uint64_t h = idx->evals_hint.load(std::memory_order_relaxed);
-    if ((uint32_t)(h >> 32) == ef) g.vhint = (uint32_t)h;
-  }
-  g.fg = fast_geometry(ef, (uint32_t)d, 4, g.vhint);
-  g.use_fast = ef <= 512 && ef >= 1 && idx->max_degree <= 128;
-  // resident waves per CU: bounded by LDS (visited table + query) and by the kernel's VGPR
-  // budget (<= 128 -> 4 per SIMD)
-  const size_t cu_cap = waves_per_cu_cap();
-  uint32_t per_cu = (uint32_t)std::min<size_t>(cu_cap, (160 * 1024) / g.fg.lds);
-  if (per_cu == 0) g.use_fast = false;
-  if (tl) {
-    // Window of the approximate queue: ceil(a * |AQ|) must stay inside it.  |AQ| is bounded by the
-    // node count and runs at about 10 x ef (1235 at ef = 128 on the 10M-node bench graph); 20 x ef
-    // covers the long queries, and one that outgrows it is re-run alone with four times the window
-    // (never answered differently).  The window is most of a wave's LDS: round 2 sized it for
-    // 32 x ef and ran 3 waves per CU at d = 4096.
-    g.use_fast = false;
-    const float a = tl->ratio > 0.0f ? std::min(tl->ratio, 1.0f) : 0.0f;
-    const double bound = (double)std::min<uint64_t>(idx->ncodes, (uint64_t)20 * ef * tl->window_scale);
-    const uint64_t want = (uint64_t)(a * bound) + 64;
-    g.tl_wcap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((want + 63) / 64 * 64, 256), 16384);
-    while (g.tl_wcap > 256 && two_level_lds(g.fg.hbits, g.tl_wcap, ef, (uint32_t)d) > 160 * 1024) g.tl_wcap -= 64;
-    g.tl_lds = two_level_lds(g.fg.hbits, g.tl_wcap, ef, (uint32_t)d);
-    if (g.tl_lds > 160 * 1024)
-      return isl::fail(ISL_ERR_UNSUPPORTED, "two-level search: ef = %u, d = %llu do not fit the LDS", ef,
-                       (unsigned long long)d);
-    per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(cu_cap, (160 * 1024) / g.tl_lds));
-    // bf16 rows: the queries whose elements are bf16 values keep their query as bf16 in LDS
-    g.tl_hbits_q = fast_geometry(ef, (uint32_t)d, 2).hbits;
-    g.tl_lds_q = two_level_lds(g.tl_hbits_q, g.tl_wcap, ef, (uint32_t)d, 2);
-    g.tl_slots_q = (uint32_t)ncu * (uint32_t)std::max<size_t>(1, std::min<size_t>(cu_cap, (160 * 1024) / g.tl_lds_q));
-  }
-  g.slots = std::max<uint32_t>(1, (uint32_t)ncu * std::max<uint32_t>(per_cu, 1));
-  g.plog_cap = push_log_cap(ef);
-  return ISL_OK;
-}
-
 // status / counters / work-queue heads of the call -> the lane's pinned mirrors, and for a
 // host-buffer call its answers too; one kernel behind the search kernels.
 isl_status publish(isl::SearchWorkspace& ws, uint64_t nq, uint64_t k, hipStream_t st) {
@@ -471,45 +320,75 @@ isl_status publish(isl::SearchWorkspace& ws, uint64_t nq, uint64_t k, hipStream_
   return ISL_OK;
 }
 
-// Enqueues the kernels of one search on a claimed lane; every pointer is a device pointer.
+// One search as its entry point received it; every pointer is a device pointer.
+struct SearchCall {
+  const float* queries = nullptr;
+  uint64_t nq = 0, d = 0, k = 0, ef = 0;
+  uint64_t* ids = nullptr;
+  float* dist = nullptr;
+  uint32_t* count = nullptr;
+  hipStream_t user_stream = nullptr;
+  StreamMode mode = StreamMode::OWN;
+  bool two_level = false;  // the two-level search with a PQ filter, re-ranking `ratio` of the approximate queue
+  float ratio = 0.0f;
+};
+hipStream_t call_stream(const isl::SearchWorkspace& ws, const SearchCall& c) {
+  return c.mode == StreamMode::USER ? c.user_stream : ws.stream;
+}
+
+// What search_sync asks of one enqueue beyond the call itself; the default is an ordinary launch
+// over all queries (asynchronous entry points, warm launches).
+struct RoundPlan {
+  // a round of the recompute provider: the RESUME kernel over `active` queries, listed in ws.qlist
+  // unless it is the first round (`listed`); `exact` queries of ws.h_xlist go straight to the
+  // heap-exact kernel's queue
+  uint32_t active = 0;
+  uint32_t exact = 0;
+  bool exact_parks = false;   // this call's queries park in the heap-exact kernel (bounded row cache)
+  bool listed = false;
+  uint32_t prefetch = 0;      // two-level search: ids a parked query names beyond its misses (0 = none)
+  // two-level search: `retry` queries (listed in ws.qlist) re-run alone with a queue window grown
+  // by `window_scale`; the PQ distance tables of the call's first launch stay
+  uint32_t retry = 0;
+  uint32_t window_scale = 1;
+  bool tables_built = false;
+};
+
+// the one switch over the fast kernel's S: each case is an object of its own (search_fast.hip)
+void launch_fast(const isl_launch::FastKernel& k, uint32_t grid, size_t lds, hipStream_t st, const SearchParams& p) {
+  switch (k.S) {
+    case 1: isl_launch::launch_fast_segments<1>(k, grid, lds, st, &p); break;
+    case 2: isl_launch::launch_fast_segments<2>(k, grid, lds, st, &p); break;
+    case 4: isl_launch::launch_fast_segments<4>(k, grid, lds, st, &p); break;
+    default: isl_launch::launch_fast_segments<8>(k, grid, lds, st, &p); break;
+  }
+}
+
+// Enqueues the kernels of one search on a claimed lane.
 // warm = true: the same launches over zero queries (isl_index_prepare: loads the code objects and
 // brings the lane's stream up) -- nothing is read or written beyond the ticket words.
-isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, const float* d_queries,
-                               uint64_t nq, uint64_t d, uint64_t k, uint64_t ef_in, uint64_t* d_ids,
-                               float* d_dist, uint32_t* d_count, hipStream_t user_stream,
-                               StreamMode mode, const TwoLevelCall* tl, bool warm) {
+isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c,
+                               const RoundPlan& plan, bool warm) {
+  const uint64_t nq = c.nq, d = c.d, k = c.k;
   if (nq > 0x7FFFFFFFull) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "too many queries");
+  const TwoLevelCall tl_call{c.ratio, plan.window_scale};
+  const TwoLevelCall* tl = c.two_level ? &tl_call : nullptr;
   CallGeometry cg;
-  ISL_TRY(call_geometry(idx, d, k, ef_in, tl, cg));
+  ISL_TRY(call_geometry(idx, d, k, c.ef, tl, cg));
   const uint32_t ef = cg.ef;
   const bool use_fast = cg.use_fast;
-  const FastGeom& fg = cg.fg;
-  const uint32_t slots = cg.slots, plog_cap = cg.plog_cap;
   // searches over the recompute provider park and resume on the fast kernel (f32 rows; the
   // two-level and heap-exact kernels re-run a blocked query from its start instead)
-  const bool resume = !warm && (ws.round_active != 0 || ws.round_x != 0);
+  const bool resume = !warm && (plan.active != 0 || plan.exact != 0);
   // two-level search over bf16 rows: first the instantiation that keeps a bf16-valued query as bf16
   // in LDS, then the float32-query one over the queries it passed on (not in a retry's list mode)
-  static const bool no_tl_qh = getenv("ISL_NO_TL_QH") != nullptr;  // A/B switch for measurements
-  const bool tl_qh = tl && !warm && !resume && idx->d_emb16 && ws.retry_count == 0 && !no_tl_qh &&
-                     cg.tl_hbits_q == cg.fg.hbits;
-  // bf16 rows: first the kernel that keeps the query as bf16 in LDS (half the LDS per wave, more
-  // waves per CU), then the float32-query kernel over the queries that one passed on
-  static const bool no_qh = getenv("ISL_NO_QH") != nullptr;  // A/B switch for measurements
-  const bool qh = use_fast && !tl && !resume && idx->d_emb16 && idx->max_degree <= 64 && !no_qh;
-  FastGeom fgq = fg;
-  uint32_t slots_q = slots;
-  if (qh) {
-    fgq = fast_geometry(ef, (uint32_t)d, 2, cg.vhint);
-    slots_q = (uint32_t)isl::device_cu_count(idx->device) *
-              (uint32_t)std::max<size_t>(1, std::min<size_t>(waves_per_cu_cap(), (160 * 1024) / fgq.lds));
-  }
+  const bool tl_qh = tl && !warm && !resume && idx->d_emb16 && plan.retry == 0 && cg.tl_hbits_q == cg.fg.hbits;
+  const bool qh = cg.qh && !resume;  // (the fast kernel's bf16-query instantiation in front)
   // per-slot state is indexed by blockIdx.x < min(nq, slots) -- by the query when it can come back on
   // another wave
   if (!warm)
     ISL_TRY(prepare_workspace(idx, ws, (uint32_t)nq,
-                              (uint32_t)(idx->recompute ? nq : std::min<uint64_t>(nq, std::max(std::max(slots, slots_q), cg.tl_slots_q))),
-                              plog_cap));
+                              (uint32_t)(idx->recompute ? nq : std::min<uint64_t>(nq, cg.lane_slots)), cg.plog_cap));
   if (!idx->pool.slots || ((use_fast || (tl && idx->max_degree <= 128)) && !idx->d_ell && idx->d_off && idx->num_nodes)) {
     // not prepared (isl_index_prepare / isl_index_upload do this ahead of time)
     std::lock_guard<std::mutex> lock(idx->mu);
@@ -518,9 +397,9 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     ISL_TRY(isl::ensure_padded_adjacency(const_cast<isl_index*>(idx)));
     if (idx->d_ell != before) ws.alloc_events += 2;
   }
-  hipStream_t st = mode == StreamMode::USER ? user_stream : ws.stream;
-  if (mode == StreamMode::OWN_AFTER_USER) {
-    ISL_HIP(hipEventRecord(ws.ev_in, user_stream));
+  hipStream_t st = call_stream(ws, c);
+  if (c.mode == StreamMode::OWN_AFTER_USER) {
+    ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));
     ISL_HIP(hipStreamWaitEvent(ws.stream, ws.ev_in, 0));
   }
 
@@ -536,16 +415,16 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.nvec = idx->nvec;
   p.stride = idx->emb_stride;
   p.d = (uint32_t)d;
-  p.queries = d_queries;
+  p.queries = c.queries;
   p.nq = warm ? 0u : (uint32_t)nq;
   p.k = (uint32_t)k;
   p.ef = ef;
   p.prune_ratio = idx->cfg.prune_ratio;
   p.prune_strategy = idx->cfg.pruning_strategy;
   p.entry = (uint32_t)std::min<uint64_t>(idx->entry_point, 0x7FFFFFF0ull);
-  p.out_ids = d_ids;
-  p.out_dist = d_dist;
-  p.out_count = d_count;
+  p.out_ids = c.ids;
+  p.out_dist = c.dist;
+  p.out_count = c.count;
   p.status = ws.status;
   p.payload = ws.payload;
   p.ctr = ws.ctr;
@@ -569,9 +448,9 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.tline = ws.d_tline;
   p.replay = ws.replay;
   p.plog = reinterpret_cast<uint2*>(ws.plog);
-  p.plog_cap = plog_cap;
-  p.hbits = fg.hbits;
-  p.hcap = fg.hcap;
+  p.plog_cap = cg.plog_cap;
+  p.hbits = cg.fg.hbits;
+  p.hcap = cg.fg.hcap;
   p.otab = ws.ovf_tab;
   p.obits = ws.ovf_bits;
   p.cand_d = idx->pool.cand_d;
@@ -583,7 +462,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.ulist_cap = idx->pool.ulist_cap;
   p.pool_locks = idx->pool.locks;
   p.pool_slots = idx->pool.slots;
-  if (resume && !tl && ws.round_xpark) {  // the heap-exact kernel parks and resumes too (recompute provider, bounded cache)
+  if (resume && !tl && plan.exact_parks) {  // the heap-exact kernel parks and resumes too (recompute provider, bounded cache)
     p.xslot = ws.xslot;
     p.xstate = idx->pool.xstate;
     p.xstate_words = idx->pool.xstate_words;
@@ -593,26 +472,23 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.round_no = idx->round_no;
   if (resume) {
     p.qstate = ws.qstate;
-    p.qstate_words = tl ? isl_launch::tl_state_words(ef, cg.tl_wcap, fg.hbits)
-                        : isl_launch::fast_state_words(ef <= 64 ? 1 : ef <= 128 ? 2 : ef <= 256 ? 4 : 8, fg.hbits);
+    p.qstate_words = cg.state_words;
     p.qflag = ws.qflag;
-    p.qlist = ws.round_listed ? ws.qlist : nullptr;
-  } else if (tl && ws.retry_count) {
+    p.qlist = plan.listed ? ws.qlist : nullptr;
+  } else if (tl && plan.retry) {
     p.qlist = ws.qlist;  // the queries whose queue window was too small, alone, with a larger one
   }
   p.miss = ws.miss;
   p.miss_cap = (uint32_t)std::min<uint64_t>(ws.miss_cap, 0xFFFFFFFFull);
   p.pref = ws.miss ? ws.miss + ws.miss_cap : nullptr;
   p.pref_cap = (uint32_t)ws.pref_cap;
-  p.tl_prefetch = (tl && resume && ws.pref_cap) ? ws.round_prefetch : 0u;
+  p.tl_prefetch = (tl && resume && ws.pref_cap) ? plan.prefetch : 0u;
   p.layer_off = idx->d_layer_off;
   p.layer_adj = idx->d_layer_adj;
   p.max_level = idx->is_hnsw ? (uint32_t)idx->max_level : 0u;
   p.hnsw_order = idx->is_hnsw ? 1u : 0u;
   p.q_entry = nullptr;
   p.q_evals = nullptr;
-  static const uint32_t seq_max_env = [] { const char* e = getenv("ISL_SEQ_MAX"); return e ? (uint32_t)atoi(e) : 0u; }();
-  p.seq_max = seq_max_env;
   if (tl) {
     const isl_pq* pq = idx->pq;
     const uint64_t want = std::max<uint64_t>(nq, 1) * pq->m * pq->K;
@@ -626,26 +502,23 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     p.tl_wcap = cg.tl_wcap;
   }
   const uint64_t nq_grid = warm ? 1 : nq;  // a warm launch needs one workgroup to exist
+  const int metric = (int)idx->cfg.metric;
 
   // the work-queue heads are zero at this point: the publish kernel of the lane's previous call
   // left them so; only a lane's first call (or one after a failed enqueue) clears them itself
   if (!ws.ticket_clean) ISL_HIP(hipMemsetAsync(ws.ticket, 0, 64, st));
   ws.ticket_clean = false;
   ISL_HIP(hipEventRecord(ws.ev0, st));
-  if (resume && !tl && ws.round_x) {
-    hipLaunchKernelGGL(seed_redo_kernel, dim3(1), dim3(256), 0, st, ws.h_xlist, ws.round_x, ws.redo, ws.ticket);
+  if (resume && !tl && plan.exact) {
+    hipLaunchKernelGGL(seed_redo_kernel, dim3(1), dim3(256), 0, st, ws.h_xlist, plan.exact, ws.redo, ws.ticket);
     ISL_HIP(hipGetLastError());
   }
   if (tl) {
     // build_distance_tables for the whole batch (pq.rs:307-338; once per call: the rounds of the
     // recompute provider and a retry keep them), then one wave per query
-    if (!warm && !ws.tl_tables_built) {
-      ISL_TRY(isl::pq_launch_tables(idx->pq, d_queries, nq, ws.tl_tables, st));
-      ws.tl_tables_built = true;
-    }
-    const uint64_t n_run = resume ? ws.round_active : ws.retry_count ? ws.retry_count : nq_grid;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_run, slots);
-    const int metric = (int)idx->cfg.metric;
+    if (!warm && !plan.tables_built) ISL_TRY(isl::pq_launch_tables(idx->pq, c.queries, nq, ws.tl_tables, st));
+    const uint64_t n_run = resume ? plan.active : plan.retry ? plan.retry : nq_grid;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_run, cg.slots);
     p.nq = warm ? 0u : (uint32_t)n_run;
     if (tl_qh) {
       p.qsel = ws.qsel;
@@ -670,44 +543,34 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     ISL_TRY(ensure(ws, ws.q_entry, ws.q_entry_cap, std::max<uint64_t>(nq, 1) * 2));
     p.q_entry = ws.q_entry;
     p.q_evals = ws.q_entry + nq;
-    const size_t dlds = (size_t)((d + 3) / 4 * 4) * 4 + 64;
     const uint32_t dgrid = (uint32_t)std::min<uint64_t>(nq_grid, 8192);
-    isl_launch::launch_descent((int)idx->cfg.metric, dgrid, dlds, st, &p);
+    isl_launch::launch_descent(metric, dgrid, cg.descent_lds, st, &p);
     ISL_HIP(hipGetLastError());
   }
   if (tl) {
   } else if (use_fast) {
-    if (resume) p.nq = ws.round_active;  // the fast kernel runs this round's queries; nothing else reads nq
-    uint32_t grid = (uint32_t)std::min<uint64_t>(resume ? ws.round_active : nq_grid, slots);
-    const bool skip_fast = resume && ws.round_active == 0;  // only queries parked in the heap-exact kernel this round
-    int S = ef <= 64 ? 1 : ef <= 128 ? 2 : ef <= 256 ? 4 : 8;
-    const int metric = (int)idx->cfg.metric;
-    const bool wide = idx->max_degree > 64;
-    const bool bf16 = p.emb_bf16 != 0;
-    auto launch_fast = [&](bool q16, uint32_t g, size_t lds_bytes) {
-      switch (S) {
-        case 1: isl_launch::launch_fast_s1(metric, wide, bf16, resume, q16, g, lds_bytes, st, &p); break;
-        case 2: isl_launch::launch_fast_s2(metric, wide, bf16, resume, q16, g, lds_bytes, st, &p); break;
-        case 4: isl_launch::launch_fast_s4(metric, wide, bf16, resume, q16, g, lds_bytes, st, &p); break;
-        default: isl_launch::launch_fast_s8(metric, wide, bf16, resume, q16, g, lds_bytes, st, &p); break;
-      }
-    };
+    if (resume) p.nq = plan.active;  // the fast kernel runs this round's queries; nothing else reads nq
+    uint32_t grid = (uint32_t)std::min<uint64_t>(resume ? plan.active : nq_grid, cg.slots);
+    const bool skip_fast = resume && plan.active == 0;  // only queries parked in the heap-exact kernel this round
+    isl_launch::FastKernel fk{cg.segments, metric, idx->max_degree > 64, p.emb_bf16 != 0, resume, false};
     if (qh) {
       p.qsel = ws.qsel;
       p.qsel_h = ws.qsel_h;
       isl_launch::launch_classify((uint32_t)std::min<uint64_t>(nq_grid, 2048), st, &p);
       ISL_HIP(hipGetLastError());
-      p.hbits = fgq.hbits;
-      p.hcap = fgq.hcap;
-      launch_fast(true, (uint32_t)std::min<uint64_t>(nq_grid, slots_q), fgq.lds);  // the bf16-valued queries
+      p.hbits = cg.fgq.hbits;
+      p.hcap = cg.fgq.hcap;
+      fk.qh = true;  // the bf16-valued queries
+      launch_fast(fk, (uint32_t)std::min<uint64_t>(nq_grid, cg.slots_q), cg.fgq.lds, st, p);
       ISL_HIP(hipGetLastError());
-      p.hbits = fg.hbits;
-      p.hcap = fg.hcap;
+      p.hbits = cg.fg.hbits;
+      p.hcap = cg.fg.hcap;
       p.qsel_mode = 1;  // the others
-      launch_fast(false, grid, fg.lds);
+      fk.qh = false;
+      launch_fast(fk, grid, cg.fg.lds, st, p);
       p.qsel_mode = 0;
     } else if (!skip_fast) {
-      launch_fast(false, grid, fg.lds);
+      launch_fast(fk, grid, cg.fg.lds, st, p);
     }
     ISL_HIP(hipGetLastError());
     p.nq = (uint32_t)nq;
@@ -722,7 +585,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   }
   if (!tl) {
     uint32_t grid = (uint32_t)std::min<uint64_t>(nq_grid, idx->pool.slots);
-    isl_launch::launch_exact((int)idx->cfg.metric, idx->is_hnsw, grid, exact_lds(ef, (uint32_t)d), st, &p);
+    isl_launch::launch_exact(metric, idx->is_hnsw, grid, cg.exact_lds, st, &p);
     ISL_HIP(hipGetLastError());
   }
   ISL_HIP(hipEventRecord(ws.ev1, st));
@@ -731,7 +594,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
 
   ISL_TRY(publish(ws, nq, k, st));
   // the call's own completion event: lanes may share a stream, and a caller's stream carries its other work
-  if (ws.ev_done) ISL_HIP(hipEventRecord(ws.ev_done, st));
+  ISL_HIP(hipEventRecord(ws.ev_done, st));
   ws.enqueued = true;
   ws.nq_inflight = nq;
   ws.k_inflight = k;
@@ -744,16 +607,13 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
 // may leave kernels of this call on the stream: they are drained before the error goes back, because
 // the caller releases the lane next and the lane's next owner rewrites its pinned buffers / may
 // reallocate what those kernels still read.
-isl_status search_enqueue(const isl_index* idx, isl::SearchWorkspace& ws, const float* d_queries,
-                          uint64_t nq, uint64_t d, uint64_t k, uint64_t ef_in, uint64_t* d_ids,
-                          float* d_dist, uint32_t* d_count, hipStream_t user_stream,
-                          StreamMode mode, const TwoLevelCall* tl = nullptr, bool warm = false) {
-  const isl_status st = search_enqueue_impl(idx, ws, d_queries, nq, d, k, ef_in, d_ids, d_dist, d_count, user_stream,
-                                            mode, tl, warm);
+isl_status search_enqueue(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c,
+                          const RoundPlan& plan = RoundPlan{}, bool warm = false) {
+  const isl_status st = search_enqueue_impl(idx, ws, c, plan, warm);
   if (st != ISL_OK) {
     const isl::ErrorRecord keep = isl::last_error();
-    hipStream_t s = mode == StreamMode::USER ? user_stream : ws.stream;
-    if (mode == StreamMode::USER || s) (void)hipStreamSynchronize(s);
+    hipStream_t s = call_stream(ws, c);
+    if (c.mode == StreamMode::USER || s) (void)hipStreamSynchronize(s);
     (void)hipGetLastError();
     ws.ticket_clean = false;
     ws.enqueued = false;
@@ -782,9 +642,7 @@ isl_status search_finish(const isl_index* idx, isl::SearchWorkspace& ws, uint32_
   ws.enqueued = false;
   const uint64_t nq = ws.nq_inflight;
   const bool use_fast = ws.fast_inflight;
-  static const bool sync_stream = getenv("ISL_SYNC_STREAM") != nullptr;  // A/B switch for measurements
-  if (ws.ev_done && !sync_stream) ISL_HIP(hipEventSynchronize(ws.ev_done));
-  else ISL_HIP(hipStreamSynchronize(ws.st_inflight));
+  ISL_HIP(hipEventSynchronize(ws.ev_done));
   const uint32_t* status = ws.h_status;
   const uint32_t* ctr = ws.h_ctr;
   const uint32_t* head = ws.h_head;
@@ -1050,33 +908,27 @@ isl_status prepare_recompute(isl::SearchWorkspace& ws, uint64_t nq, uint64_t sta
 // stops) -> (encode the reported nodes once each) until a round completes without a miss; that
 // last round is an ordinary search over materialised rows, so ids, distances, counters and error
 // behaviour are those of the in-memory provider holding the same embeddings.
-isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const float* d_queries,
-                       uint64_t nq, uint64_t d, uint64_t k, uint64_t ef, uint64_t* d_ids,
-                       float* d_dist, uint32_t* d_count, hipStream_t user_stream, StreamMode mode,
-                       const TwoLevelCall* tl = nullptr) {
+isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c) {
+  const uint64_t nq = c.nq;
+  const bool tl = c.two_level;
   // two-level search: a query whose approximate queue outgrew the LDS window is never answered
   // differently: the queries it happened to are run again, alone, with a window four times the size
-  TwoLevelCall tcall;
-  if (tl) { tcall = *tl; tl = &tcall; }
-  struct CallReset {  // the lane goes back with its per-call two-level fields cleared whatever happens below
-    isl::SearchWorkspace& w;
-    ~CallReset() { w.retry_count = 0; w.tl_tables_built = false; }
-  } call_reset{ws};
-  ws.retry_count = 0;
-  ws.tl_tables_built = false;
+  // (plan.retry of them, plan.window_scale)
+  RoundPlan plan;
   if (!idx->recompute) {
     double ms_total = 0.0;
     for (;;) {
-      ISL_TRY(search_enqueue(idx, ws, d_queries, nq, d, k, ef, d_ids, d_dist, d_count, user_stream, mode, tl));
-      ISL_TRY(search_finish(idx, ws, nullptr, nullptr, tl != nullptr));
+      ISL_TRY(search_enqueue(idx, ws, c, plan));
+      plan.tables_built = tl;
+      ISL_TRY(search_finish(idx, ws, nullptr, nullptr, tl));
       if (!tl) return ISL_OK;  // (statuses evaluated by search_finish)
       ms_total += ws.stats.kernel_ms;
       uint32_t nshort = 0;
       ISL_TRY(tl_collect_short(ws, nq, &nshort));
-      if (nshort && tcall.window_scale < 64) {
-        tcall.window_scale *= 4;
-        ws.retry_count = nshort;
-        hipStream_t st = mode == StreamMode::USER ? user_stream : ws.stream;
+      if (nshort && plan.window_scale < 64) {
+        plan.window_scale *= 4;
+        plan.retry = nshort;
+        hipStream_t st = call_stream(ws, c);
         hipLaunchKernelGGL(copy_u32_kernel, dim3(16), dim3(256), 0, st, ws.h_qlist, ws.qlist, (uint64_t)nshort);
         ISL_HIP(hipGetLastError());
         continue;
@@ -1088,8 +940,10 @@ isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const flo
   // the rounds rewrite the provider's row cache: one recompute search at a time
   std::lock_guard<std::mutex> rlock(idx->recompute_mu);
   CallGeometry cg0;
-  ISL_TRY(call_geometry(idx, d, k, ef, tl, cg0));
-  const int S0 = cg0.ef <= 64 ? 1 : cg0.ef <= 128 ? 2 : cg0.ef <= 256 ? 4 : 8;
+  {
+    const TwoLevelCall tl0{c.ratio};
+    ISL_TRY(call_geometry(idx, c.d, c.k, c.ef, tl ? &tl0 : nullptr, cg0));
+  }
   // searches that park and resume: the wave-per-query traversal and the two-level search (the
   // heap-exact kernel alone -- ef > 512, rows past 128 ids -- re-runs a blocked query from its start)
   // searches park and resume: the wave-per-query traversal, the two-level search, and -- since round 3 --
@@ -1101,10 +955,9 @@ isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const flo
   const bool exact_only = !tl && !cg0.use_fast;
   const bool x_park = !tl && idx->slab_rows < idx->nvec;
   const bool resumable = tl || cg0.use_fast || x_park;
-  ISL_TRY(prepare_recompute(ws, nq, tl ? isl_launch::tl_state_words(cg0.ef, cg0.tl_wcap, cg0.fg.hbits)
-                                       : cg0.use_fast ? isl_launch::fast_state_words(S0, cg0.fg.hbits) : 1));
+  ISL_TRY(prepare_recompute(ws, nq, tl || cg0.use_fast ? cg0.state_words : 1));  // (the heap-exact kernel parks in the pool)
   ISL_TRY(ensure_lane_stream(idx, ws));
-  hipStream_t st = mode == StreamMode::USER ? user_stream : ws.stream;
+  hipStream_t st = call_stream(ws, c);
   if (!idx->keep_rows) {  // every call starts from an empty cache: each node is encoded once per call
     ISL_HIP(hipMemsetAsync(idx->d_slot_of, 0xFF, (idx->nvec + 1) * 4, st));
     ISL_HIP(hipMemsetAsync(idx->d_owner, 0xFF, idx->slab_rows * 4, st));
@@ -1148,22 +1001,16 @@ isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const flo
     for (uint32_t i = 0; i < active; ++i) ws.h_qlist[i] = i;
     hipLaunchKernelGGL(copy_u32_kernel, dim3(16), dim3(256), 0, st, ws.h_qlist, ws.qlist, (uint64_t)active);
   }
-  struct RoundReset {  // the lane goes back with its round fields cleared whatever happens below,
-    const isl_index* idx;  // and no slot of the heap-exact kernel's pool stays with a query of this call
-    isl::SearchWorkspace& w;
+  struct RoundReset {  // no slot of the heap-exact kernel's pool stays with a query of this call whatever happens below
+    const isl_index* idx;
     hipStream_t st;
     ~RoundReset() {
-      w.round_active = 0;
-      w.round_prefetch = 0;
-      w.round_x = 0;
-      w.round_xpark = false;
-      w.round_listed = false;
       if (idx->pool.slots && idx->pool.locks) {
         (void)hipMemsetAsync(idx->pool.locks, 0, (size_t)idx->pool.slots * 4, st);
         (void)hipStreamSynchronize(st);
       }
     }
-  } reset{idx, ws, st};
+  } reset{idx, st};
   uint32_t* h_taken = ws.h_head + 15;  // (word 15 of the pinned ticket mirror is otherwise unused)
   // encoder batches in whole waves of GEMM tiles (assign_slots_kernel; ISL_RECOMPUTE_QUANTUM=0: every miss at once)
   uint32_t enc_quantum = 0, enc_chunk = 0;
@@ -1182,13 +1029,14 @@ isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const flo
   if (const char* pe = getenv("ISL_TL_PREFETCH")) prefetch = tl ? (uint32_t)std::min(8, std::max(0, atoi(pe))) : 0u;
   std::vector<uint32_t> again;  // two-level search: queries to start over with a larger queue window
   for (;;) {
-    ws.round_active = active;
-    ws.round_x = nxl;
-    ws.round_xpark = x_park;
-    ws.round_listed = listed;
-    ws.round_prefetch = prefetch;
+    plan.active = active;
+    plan.exact = nxl;
+    plan.exact_parks = x_park;
+    plan.listed = listed;
+    plan.prefetch = prefetch;
     idx->round_no += 1;
-    ISL_TRY(search_enqueue(idx, ws, d_queries, nq, d, k, ef, d_ids, d_dist, d_count, user_stream, mode, tl));
+    ISL_TRY(search_enqueue(idx, ws, c, plan));
+    plan.tables_built = tl;
     uint32_t misses = 0;
     ISL_TRY(search_finish(idx, ws, &misses, nullptr, resumable));
     const uint32_t guesses = prefetch ? std::min<uint32_t>(ws.h_head[14], (uint32_t)ws.pref_cap) : 0u;
@@ -1217,12 +1065,12 @@ isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const flo
         // nothing is parked now -- with a window four times the size (and a state block to match)
         uint32_t nshort = 0;
         ISL_TRY(tl_collect_short(ws, nq, &nshort));
-        if (nshort && tcall.window_scale < 64) {
-          tcall.window_scale *= 4;
+        if (nshort && plan.window_scale < 64) {
+          plan.window_scale *= 4;
+          const TwoLevelCall tl1{c.ratio, plan.window_scale};
           CallGeometry cg1;
-          ISL_TRY(call_geometry(idx, d, k, ef, tl, cg1));
-          ISL_TRY(ensure(ws, ws.qstate, ws.qstate_words,
-                         std::max<uint64_t>(nq, 1) * isl_launch::tl_state_words(cg1.ef, cg1.tl_wcap, cg1.fg.hbits)));
+          ISL_TRY(call_geometry(idx, c.d, c.k, c.ef, &tl1, cg1));
+          ISL_TRY(ensure(ws, ws.qstate, ws.qstate_words, std::max<uint64_t>(nq, 1) * cg1.state_words));
           again.assign(ws.h_qlist, ws.h_qlist + nshort);
           while (na < max_active && !again.empty()) { ws.h_qlist[na++] = again.back(); again.pop_back(); }
         }
@@ -1293,25 +1141,18 @@ isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const flo
 // depend on what else is in the batch).  If the union fails -- one query's NodeNotFound fails the call it
 // belongs to, not its neighbours' -- every member is run by itself and gets its own status.
 struct RecCall {
-  const float* dq;
-  uint64_t nq, d, k, ef;
-  uint64_t* ids;
-  float* dist;
-  uint32_t* cnt;
-  bool has_tl;
-  float ratio;
+  SearchCall call;  // (on the member's own lane's stream: StreamMode::OWN)
   isl::SearchWorkspace* ws;
   bool done = false;
   isl_status status = ISL_OK;
   isl::ErrorRecord err;
 };
 
-isl_status recompute_coalesced(const isl_index* idx, isl::SearchWorkspace& ws, const float* d_queries, uint64_t nq,
-                               uint64_t d, uint64_t k, uint64_t ef, uint64_t* d_ids, float* d_dist, uint32_t* d_count,
-                               const TwoLevelCall* tl) {
+isl_status recompute_coalesced(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c) {
   static const bool off = getenv("ISL_NO_RECOMPUTE_COALESCE") != nullptr;  // A/B switch for measurements
-  if (off) return search_sync(idx, ws, d_queries, nq, d, k, ef, d_ids, d_dist, d_count, nullptr, StreamMode::OWN, tl);
-  RecCall me{d_queries, nq, d, k, ef, d_ids, d_dist, d_count, tl != nullptr, tl ? tl->ratio : 0.0f, &ws};
+  if (off) return search_sync(idx, ws, c);
+  const uint64_t d = c.d, k = c.k;
+  RecCall me{c, &ws};
   auto& J = idx->rec_join;
   {
     std::lock_guard<std::mutex> l(J.mu);
@@ -1324,30 +1165,30 @@ isl_status recompute_coalesced(const isl_index* idx, isl::SearchWorkspace& ws, c
   }
   constexpr uint64_t kMaxUnion = 1u << 17;  // queries one set of rounds works through
   std::vector<RecCall*> group{&me};
-  uint64_t total = nq;
+  uint64_t total = c.nq;
   {
     std::lock_guard<std::mutex> l(J.mu);
     std::vector<void*> rest;
     for (void* v : J.waiting) {
-      RecCall* c = static_cast<RecCall*>(v);
-      if (c == &me) continue;
-      const bool same = c->d == d && c->k == k && c->ef == ef && c->has_tl == me.has_tl && (!me.has_tl || c->ratio == me.ratio);
-      if (same && total + c->nq <= kMaxUnion) { group.push_back(c); total += c->nq; }
+      RecCall* m = static_cast<RecCall*>(v);
+      if (m == &me) continue;
+      const SearchCall& o = m->call;
+      const bool same = o.d == d && o.k == k && o.ef == c.ef && o.two_level == c.two_level && (!c.two_level || o.ratio == c.ratio);
+      if (same && total + o.nq <= kMaxUnion) { group.push_back(m); total += o.nq; }
       else rest.push_back(v);
     }
     J.waiting.swap(rest);
   }
-  if (group.size() == 1)
-    return search_sync(idx, ws, d_queries, nq, d, k, ef, d_ids, d_dist, d_count, nullptr, StreamMode::OWN, tl);
+  if (group.size() == 1) return search_sync(idx, ws, c);
 
-  auto alone = [&](RecCall* c) {  // the member's own call, on the member's own lane
-    c->status = search_sync(idx, *c->ws, c->dq, c->nq, c->d, c->k, c->ef, c->ids, c->dist, c->cnt, nullptr, StreamMode::OWN, tl);
-    if (c->status != ISL_OK) c->err = isl::last_error();
+  auto alone = [&](RecCall* m) {  // the member's own call, on the member's own lane
+    m->status = search_sync(idx, *m->ws, m->call);
+    if (m->status != ISL_OK) m->err = isl::last_error();
   };
   auto fall_back = [&]() -> isl_status {  // every member by itself: its own answers, its own error
-    for (RecCall* c : group)
-      if (c != &me) { alone(c); c->done = true; }
-    return search_sync(idx, ws, d_queries, nq, d, k, ef, d_ids, d_dist, d_count, nullptr, StreamMode::OWN, tl);
+    for (RecCall* m : group)
+      if (m != &me) { alone(m); m->done = true; }
+    return search_sync(idx, ws, c);
   };
   if (ensure(ws, ws.co_q, ws.co_q_cap, total * d) != ISL_OK || ensure(ws, ws.co_ids, ws.co_ids_cap, total * std::max<uint64_t>(k, 1)) != ISL_OK ||
       ensure(ws, ws.co_dist, ws.co_dist_cap, total * std::max<uint64_t>(k, 1)) != ISL_OK || ensure(ws, ws.co_cnt, ws.co_cnt_cap, total) != ISL_OK ||
@@ -1356,56 +1197,63 @@ isl_status recompute_coalesced(const isl_index* idx, isl::SearchWorkspace& ws, c
   hipStream_t st = ws.stream;
   uint64_t o = 0;
   bool copied = true;
-  for (RecCall* c : group) {  // a member's queries are there once its caller's stream has reached the call (ev_in)
-    if (c != &me) copied = copied && hipStreamWaitEvent(st, c->ws->ev_in, 0) == hipSuccess;
-    copied = copied && hipMemcpyAsync(ws.co_q + o * d, c->dq, c->nq * d * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
-    o += c->nq;
+  for (RecCall* m : group) {  // a member's queries are there once its caller's stream has reached the call (ev_in)
+    if (m != &me) copied = copied && hipStreamWaitEvent(st, m->ws->ev_in, 0) == hipSuccess;
+    copied = copied && hipMemcpyAsync(ws.co_q + o * d, m->call.queries, m->call.nq * d * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    o += m->call.nq;
   }
   if (!copied) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return fall_back(); }
   // (a host-buffer call's lane publishes its answers into pinned mirrors sized for THAT call: not for the union)
   const bool publishes = ws.publish_results;
   ws.publish_results = false;
-  const isl_status rc = search_sync(idx, ws, ws.co_q, total, d, k, ef, ws.co_ids, ws.co_dist, ws.co_cnt, nullptr, StreamMode::OWN, tl);
+  SearchCall all_calls = c;  // the union: every member's queries, answered into the lane's own buffers
+  all_calls.queries = ws.co_q;
+  all_calls.nq = total;
+  all_calls.ids = ws.co_ids;
+  all_calls.dist = ws.co_dist;
+  all_calls.count = ws.co_cnt;
+  const isl_status rc = search_sync(idx, ws, all_calls);
   ws.publish_results = publishes;
   if (rc != ISL_OK) return fall_back();
   const isl_search_stats all = ws.stats;
   o = 0;
   bool scattered = true;
-  for (RecCall* c : group) {
+  for (RecCall* m : group) {
+    const uint64_t mq = m->call.nq;
     if (k) {
-      scattered = scattered && hipMemcpyAsync(c->ids, ws.co_ids + o * k, c->nq * k * 8, hipMemcpyDeviceToDevice, st) == hipSuccess;
-      scattered = scattered && hipMemcpyAsync(c->dist, ws.co_dist + o * k, c->nq * k * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+      scattered = scattered && hipMemcpyAsync(m->call.ids, ws.co_ids + o * k, mq * k * 8, hipMemcpyDeviceToDevice, st) == hipSuccess;
+      scattered = scattered && hipMemcpyAsync(m->call.dist, ws.co_dist + o * k, mq * k * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
     }
-    scattered = scattered && hipMemcpyAsync(c->cnt, ws.co_cnt + o, c->nq * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
-    if (c->ws->publish_results) {  // a host-buffer call (isl_search_batch_async): its wait copies out of the lane's pinned mirrors
+    scattered = scattered && hipMemcpyAsync(m->call.count, ws.co_cnt + o, mq * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    if (m->ws->publish_results) {  // a host-buffer call (isl_search_batch_async): its wait copies out of the lane's pinned mirrors
       if (k) {
-        scattered = scattered && hipMemcpyAsync(c->ws->h_ids, ws.co_ids + o * k, c->nq * k * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-        scattered = scattered && hipMemcpyAsync(c->ws->h_dist, ws.co_dist + o * k, c->nq * k * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+        scattered = scattered && hipMemcpyAsync(m->ws->h_ids, ws.co_ids + o * k, mq * k * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
+        scattered = scattered && hipMemcpyAsync(m->ws->h_dist, ws.co_dist + o * k, mq * k * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
       }
-      scattered = scattered && hipMemcpyAsync(c->ws->h_count, ws.co_cnt + o, c->nq * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-      c->ws->nq_inflight = c->nq;
-      c->ws->k_inflight = c->k;
+      scattered = scattered && hipMemcpyAsync(m->ws->h_count, ws.co_cnt + o, mq * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+      m->ws->nq_inflight = mq;
+      m->ws->k_inflight = k;
     }
-    o += c->nq;
+    o += mq;
   }
   scattered = scattered && hipStreamSynchronize(st) == hipSuccess;
   if (!scattered) { (void)hipGetLastError(); return fall_back(); }
   // each member's counters are its own queries' (the lane's pinned mirror holds the union's, query by query);
   // rounds, encoded nodes and kernel time are the union's
   o = 0;
-  for (RecCall* c : group) {
+  for (RecCall* m : group) {
     isl_search_stats ms = all;
-    ms.queries = c->nq;
+    ms.queries = m->call.nq;
     ms.expansions = ms.edges = ms.evals = ms.pushes = 0;
-    for (uint64_t i = o; i < o + c->nq; ++i) {
+    for (uint64_t i = o; i < o + m->call.nq; ++i) {
       ms.expansions += ws.h_ctr[i * 4 + 0];
       ms.edges += ws.h_ctr[i * 4 + 1];
       ms.evals += ws.h_ctr[i * 4 + 2];
       ms.pushes += ws.h_ctr[i * 4 + 3];
     }
-    c->ws->stats = ms;
-    o += c->nq;
-    if (c != &me) { c->status = ISL_OK; c->done = true; }
+    m->ws->stats = ms;
+    o += m->call.nq;
+    if (m != &me) { m->status = ISL_OK; m->done = true; }
   }
   return ISL_OK;
 }
@@ -1497,13 +1345,49 @@ struct LaneGuard {
   void keep() { ws = nullptr; }
 };
 
+// What every entry point does first, in this order (which decides the error a bad call gets): the
+// checks of the reference, those of the two-level search, the caller's buffers (host or device
+// pointers, as the entry point received them), the device, a free lane.  *answered: nothing is
+// left to do (no queries, an empty index) and no lane was claimed.
+isl_status begin_call(const isl_index* idx, const SearchCall& c, bool count_on_device, isl::SearchWorkspace** ws,
+                      bool* answered) {
+  int done = 0;
+  ISL_TRY(precheck(idx, c.nq, c.d, c.k, c.count, count_on_device, &done));
+  *answered = done == 1;
+  if (*answered) return ISL_OK;
+  if (c.two_level) ISL_TRY(precheck_two_level(idx, c.d));
+  if (!c.queries || !c.count || (c.k && (!c.ids || !c.dist)))
+    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
+  ISL_TRY(isl::use_device(idx->device));
+  *ws = claim_lane(idx);
+  if (!*ws) return no_lane();
+  return ISL_OK;
+}
+// the token an asynchronous call hands out for its lane
+void issue_token(const isl_index* idx, isl::SearchWorkspace& ws, uint64_t* token) {
+  std::lock_guard<std::mutex> lock(idx->mu);
+  ws.token = idx->next_token++;
+  *token = ws.token;
+}
+// Asynchronous calls that run their synchronous form on a worker thread (the rounds of the recompute
+// provider, the two-level search with its retries): the lane's stream is made to wait for the
+// caller's here, and the worker's call runs on the lane's stream alone.
+isl_status order_after_user_stream(const isl_index* idx, isl::SearchWorkspace& ws, SearchCall& c) {
+  ISL_TRY(ensure_lane_stream(idx, ws));
+  ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));
+  ISL_HIP(hipStreamWaitEvent(ws.stream, ws.ev_in, 0));
+  c.user_stream = nullptr;
+  c.mode = StreamMode::OWN;
+  return ISL_OK;
+}
+
 // host-pointer calls: the queries go through the lane's pinned buffer, from where a kernel pulls
 // them into HBM; the answers come back with the publish kernel (ws.publish_results)
-isl_status host_stage_in(const isl_index* idx, isl::SearchWorkspace& ws, const float* queries, uint64_t nq, uint64_t d, uint64_t k) {
-  ISL_TRY(prepare_host_staging(ws, nq, d, k));
+isl_status host_stage_in(const isl_index* idx, isl::SearchWorkspace& ws, SearchCall& c) {
+  ISL_TRY(prepare_host_staging(ws, c.nq, c.d, c.k));
   ISL_TRY(ensure_lane_stream(idx, ws));
-  memcpy(ws.h_q, queries, nq * d * 4);
-  const uint64_t bytes = nq * d * 4;
+  const uint64_t bytes = c.nq * c.d * 4;
+  memcpy(ws.h_q, c.queries, bytes);
   if (bytes % 16 == 0)
     hipLaunchKernelGGL(copy_u128_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint4*)ws.h_q, (uint4*)ws.q_stage,
                        bytes / 16);
@@ -1512,6 +1396,13 @@ isl_status host_stage_in(const isl_index* idx, isl::SearchWorkspace& ws, const f
                        (uint32_t*)ws.q_stage, bytes / 4);
   ISL_HIP(hipGetLastError());
   ws.publish_results = true;
+  // from here on the call runs over the lane's staging buffers, on the lane's stream
+  c.queries = ws.q_stage;
+  c.ids = ws.ids_stage;
+  c.dist = ws.dist_stage;
+  c.count = ws.count_stage;
+  c.user_stream = nullptr;
+  c.mode = StreamMode::OWN;
   return ISL_OK;
 }
 void host_copy_out(const isl::SearchWorkspace& ws, uint64_t nq, uint64_t k, uint64_t* out_ids, float* out_dist,
@@ -1655,7 +1546,7 @@ isl_status search_device_sync(const isl_index* idx, const float* d_queries, uint
   SearchWorkspace* ws = claim_lane(idx);
   if (!ws) return no_lane();
   LaneGuard guard{idx, ws};
-  return search_sync(idx, *ws, d_queries, nq, d, k, ef, d_ids, d_dist, d_count, stream, StreamMode::USER);
+  return search_sync(idx, *ws, SearchCall{d_queries, nq, d, k, ef, d_ids, d_dist, d_count, stream, StreamMode::USER});
 }
 
 }  // namespace isl
@@ -1686,23 +1577,19 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
     // the lanes are held for the duration: the last step exercises them together
     for (int i = 0; i < lanes; ++i) idx->ws[i].busy = true;
   }
-  const int ncu = isl::device_cu_count(idx->device);
   // a smaller ef puts more waves on a CU: size the per-wave overflow tables for the most there can be
-  const uint32_t ovf_slots = (uint32_t)std::min<uint64_t>(max_nq, (uint64_t)ncu * waves_per_cu_cap());
+  const uint32_t ovf_slots = (uint32_t)std::min<uint64_t>(max_nq, (uint64_t)isl::device_cu_count(idx->device) * kMaxWavesPerCu);
+  CallGeometry cg_max;
+  ISL_TRY(call_geometry(idx, d, max_k, max_ef, nullptr, cg_max));
   struct ReleaseAll {
     isl_index* idx; int lanes;
     ~ReleaseAll() { for (int i = 0; i < lanes; ++i) release_lane(idx, idx->ws[i]); }
   } release_all{idx, lanes};
   for (int i = 0; i < lanes; ++i) {
     isl::SearchWorkspace& ws = idx->ws[i];
-    ISL_TRY(prepare_workspace(idx, ws, (uint32_t)max_nq, idx->recompute ? (uint32_t)max_nq : ovf_slots,
-                              push_log_cap((uint32_t)max_ef)));
+    ISL_TRY(prepare_workspace(idx, ws, (uint32_t)max_nq, idx->recompute ? (uint32_t)max_nq : ovf_slots, cg_max.plog_cap));
     ISL_TRY(prepare_host_staging(ws, max_nq, d, std::max<uint64_t>(max_k, 1)));
-    if (idx->recompute) {
-      const uint32_t efm = (uint32_t)max_ef;
-      ISL_TRY(prepare_recompute(ws, max_nq, isl_launch::fast_state_words(efm <= 64 ? 1 : efm <= 128 ? 2 : efm <= 256 ? 4 : 8,
-                                                             fast_geometry(efm, (uint32_t)d).hbits)));
-    }
+    if (idx->recompute) ISL_TRY(prepare_recompute(ws, max_nq, cg_max.state_words));
     if (idx->is_hnsw) ISL_TRY(ensure(ws, ws.q_entry, ws.q_entry_cap, max_nq * 2));
     if (idx->pq && idx->d_codes && !idx->is_hnsw && d == idx->pq->dimension)
       ISL_TRY(ensure(ws, ws.tl_tables, ws.tl_tables_cap, max_nq * idx->pq->m * idx->pq->K));
@@ -1719,13 +1606,19 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
       hipLaunchKernelGGL(copy_u128_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint4*)ws.h_q,
                          (uint4*)ws.q_stage, max_nq * d * 4 / 16);
       const uint64_t efs[] = {max_ef, std::min<uint64_t>(max_ef, 64)};
-      for (uint64_t e : efs)
-        ISL_TRY(search_enqueue(idx, ws, nullptr, 0, d, std::min<uint64_t>(max_k, e), e, nullptr, nullptr, nullptr,
-                               nullptr, StreamMode::OWN, nullptr, true));
+      SearchCall warm_call;  // no queries, no buffers, on the lane's stream
+      warm_call.d = d;
+      for (uint64_t e : efs) {
+        warm_call.k = std::min<uint64_t>(max_k, e);
+        warm_call.ef = e;
+        ISL_TRY(search_enqueue(idx, ws, warm_call, RoundPlan{}, true));
+      }
       if (idx->pq && idx->d_codes && !idx->is_hnsw && d == idx->pq->dimension) {
-        const TwoLevelCall tl{0.5f};
-        ISL_TRY(search_enqueue(idx, ws, nullptr, 0, d, std::min<uint64_t>(max_k, max_ef), max_ef, nullptr, nullptr,
-                               nullptr, nullptr, StreamMode::OWN, &tl, true));
+        warm_call.k = std::min<uint64_t>(max_k, max_ef);
+        warm_call.ef = max_ef;
+        warm_call.two_level = true;
+        warm_call.ratio = 0.5f;
+        ISL_TRY(search_enqueue(idx, ws, warm_call, RoundPlan{}, true));
       }
       ws.publish_results = true;
       ISL_TRY(publish(ws, max_nq, std::max<uint64_t>(max_k, 1), ws.stream));
@@ -1736,58 +1629,56 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
   return ISL_OK;
 }
 
+// device-pointer entries: on the caller's stream; asynchronously on the lane's, behind the caller's
+static isl_status search_batch_device(const isl_index* idx, const SearchCall& c) {
+  isl::SearchWorkspace* ws = nullptr;
+  bool answered = false;
+  ISL_TRY(begin_call(idx, c, true, &ws, &answered));
+  if (answered) return ISL_OK;
+  LaneGuard guard{idx, ws};
+  const isl_status st = search_sync(idx, *ws, c);
+  note_last_stats(idx, ws->stats);
+  return st;
+}
+
+static isl_status search_batch_device_async(const isl_index* idx, SearchCall c, uint64_t* token) {
+  if (!token) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "token is NULL");
+  *token = 0;
+  isl::SearchWorkspace* ws = nullptr;
+  bool answered = false;
+  ISL_TRY(begin_call(idx, c, true, &ws, &answered));
+  if (answered) return ISL_OK;  // token 0: nothing to wait for
+  LaneGuard guard{idx, ws};
+  if (idx->recompute || c.two_level) {
+    // the provider works through the batch in rounds (search, encode what was missed, resume), the
+    // two-level search retries queries: the synchronous form on a thread of its own, ordered after
+    // the caller's stream
+    ISL_TRY(order_after_user_stream(idx, *ws, c));
+    ISL_TRY(start_worker(idx, ws, [=]() {
+      return idx->recompute ? recompute_coalesced(idx, *ws, c) : search_sync(idx, *ws, c);
+    }));
+  } else {
+    c.mode = StreamMode::OWN_AFTER_USER;
+    ISL_TRY(search_enqueue(idx, *ws, c));
+  }
+  issue_token(idx, *ws, token);
+  guard.keep();
+  return ISL_OK;
+}
+
 isl_status isl_search_batch_device(const isl_index* idx, const float* d_queries, uint64_t nq,
                                    uint64_t d, uint64_t k, uint64_t ef, uint64_t* d_out_ids,
                                    float* d_out_dist, uint32_t* d_out_count, void* stream) {
-  int done = 0;
-  ISL_TRY(precheck(idx, nq, d, k, d_out_count, true, &done));
-  if (done == 1) return ISL_OK;
-  if (!d_queries || !d_out_count || (k && (!d_out_ids || !d_out_dist)))
-    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
-  ISL_TRY(isl::use_device(idx->device));
-  isl::SearchWorkspace* ws = claim_lane(idx);
-  if (!ws) return no_lane();
-  LaneGuard guard{idx, ws};
-  const isl_status st = search_sync(idx, *ws, d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count,
-                                    (hipStream_t)stream, StreamMode::USER);
-  note_last_stats(idx, ws->stats);
-  return st;
+  return search_batch_device(idx, SearchCall{d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count,
+                                             (hipStream_t)stream, StreamMode::USER});
 }
 
 isl_status isl_search_batch_device_async(const isl_index* idx, const float* d_queries, uint64_t nq,
                                          uint64_t d, uint64_t k, uint64_t ef, uint64_t* d_out_ids,
                                          float* d_out_dist, uint32_t* d_out_count, void* stream,
                                          uint64_t* token) {
-  if (!token) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "token is NULL");
-  *token = 0;
-  int done = 0;
-  ISL_TRY(precheck(idx, nq, d, k, d_out_count, true, &done));
-  if (done == 1) return ISL_OK;  // token 0: nothing to wait for
-  if (!d_queries || !d_out_count || (k && (!d_out_ids || !d_out_dist)))
-    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
-  ISL_TRY(isl::use_device(idx->device));
-  isl::SearchWorkspace* ws = claim_lane(idx);
-  if (!ws) return no_lane();
-  LaneGuard guard{idx, ws};
-  if (idx->recompute) {
-    // the provider works through the batch in rounds (search, encode what was missed, resume): the
-    // synchronous form on a thread of its own, ordered after the caller's stream
-    ISL_TRY(ensure_lane_stream(idx, *ws));
-    ISL_HIP(hipEventRecord(ws->ev_in, (hipStream_t)stream));
-    ISL_HIP(hipStreamWaitEvent(ws->stream, ws->ev_in, 0));
-    ISL_TRY(start_worker(idx, ws, [=]() {
-      return recompute_coalesced(idx, *ws, d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count, nullptr);
-    }));
-  } else
-  ISL_TRY(search_enqueue(idx, *ws, d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count,
-                         (hipStream_t)stream, StreamMode::OWN_AFTER_USER));
-  {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    ws->token = idx->next_token++;
-    *token = ws->token;
-  }
-  guard.keep();
-  return ISL_OK;
+  return search_batch_device_async(idx, SearchCall{d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count,
+                                                   (hipStream_t)stream, StreamMode::USER}, token);
 }
 
 isl_status isl_search_batch_async(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d,
@@ -1795,32 +1686,23 @@ isl_status isl_search_batch_async(const isl_index* idx, const float* queries, ui
                                   uint32_t* out_count, uint64_t* token) {
   if (!token) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "token is NULL");
   *token = 0;
-  int done = 0;
-  ISL_TRY(precheck(idx, nq, d, k, out_count, false, &done));
-  if (done == 1) return ISL_OK;
-  if (!queries || !out_count || (k && (!out_ids || !out_dist)))
-    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
-  ISL_TRY(isl::use_device(idx->device));
-  isl::SearchWorkspace* ws = claim_lane(idx);
-  if (!ws) return no_lane();
+  SearchCall c{queries, nq, d, k, ef, out_ids, out_dist, out_count};
+  isl::SearchWorkspace* ws = nullptr;
+  bool answered = false;
+  ISL_TRY(begin_call(idx, c, false, &ws, &answered));
+  if (answered) return ISL_OK;
   LaneGuard guard{idx, ws};
-  ISL_TRY(host_stage_in(idx, *ws, queries, nq, d, k));
+  ISL_TRY(host_stage_in(idx, *ws, c));
   if (idx->recompute) {
     ISL_HIP(hipEventRecord(ws->ev_in, ws->stream));  // the staged queries are there (a call that answers this one with its own waits for it)
-    ISL_TRY(start_worker(idx, ws, [=]() {
-      return recompute_coalesced(idx, *ws, ws->q_stage, nq, d, k, ef, ws->ids_stage, ws->dist_stage, ws->count_stage, nullptr);
-    }));
-  } else
-  ISL_TRY(search_enqueue(idx, *ws, ws->q_stage, nq, d, k, ef, ws->ids_stage, ws->dist_stage, ws->count_stage,
-                         nullptr, StreamMode::OWN));
+    ISL_TRY(start_worker(idx, ws, [=]() { return recompute_coalesced(idx, *ws, c); }));
+  } else {
+    ISL_TRY(search_enqueue(idx, *ws, c));
+  }
   ws->u_ids = out_ids;
   ws->u_dist = out_dist;
   ws->u_count = out_count;
-  {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    ws->token = idx->next_token++;
-    *token = ws->token;
-  }
+  issue_token(idx, *ws, token);
   guard.keep();
   return ISL_OK;
 }
@@ -1885,33 +1767,27 @@ isl_status isl_search_stream_wait(const isl_index* idx, uint64_t token, void* st
 }
 
 // host-pointer entry: stage the queries, search on the lane's stream, copy the answers back
-static isl_status search_batch_host(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d,
-                                    uint64_t k, uint64_t ef, uint64_t* out_ids, float* out_dist,
-                                    uint32_t* out_count, const TwoLevelCall* tl) {
-  int done = 0;
-  ISL_TRY(precheck(idx, nq, d, k, out_count, false, &done));
-  if (done == 1) return ISL_OK;
-  if (tl) ISL_TRY(precheck_two_level(idx, d));
-  if (!queries || !out_count || (k && (!out_ids || !out_dist)))
-    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
-  ISL_TRY(isl::use_device(idx->device));
-  isl::SearchWorkspace* wsp = claim_lane(idx);
-  if (!wsp) return no_lane();
-  LaneGuard guard{idx, wsp};
-  isl::SearchWorkspace& ws = *wsp;
-  ISL_TRY(host_stage_in(idx, ws, queries, nq, d, k));
-  const isl_status st = search_sync(idx, ws, ws.q_stage, nq, d, k, ef, ws.ids_stage, ws.dist_stage, ws.count_stage,
-                                    nullptr, StreamMode::OWN, tl);
-  note_last_stats(idx, ws.stats);
+static isl_status search_batch_host(const isl_index* idx, SearchCall c) {
+  uint64_t* const out_ids = c.ids;
+  float* const out_dist = c.dist;
+  uint32_t* const out_count = c.count;
+  isl::SearchWorkspace* ws = nullptr;
+  bool answered = false;
+  ISL_TRY(begin_call(idx, c, false, &ws, &answered));
+  if (answered) return ISL_OK;
+  LaneGuard guard{idx, ws};
+  ISL_TRY(host_stage_in(idx, *ws, c));
+  const isl_status st = search_sync(idx, *ws, c);
+  note_last_stats(idx, ws->stats);
   ISL_TRY(st);
-  host_copy_out(ws, nq, k, out_ids, out_dist, out_count);  // published with the last round's kernels
+  host_copy_out(*ws, c.nq, c.k, out_ids, out_dist, out_count);  // published with the last round's kernels
   return ISL_OK;
 }
 
 isl_status isl_search_batch(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d,
                             uint64_t k, uint64_t ef, uint64_t* out_ids, float* out_dist,
                             uint32_t* out_count) {
-  return search_batch_host(idx, queries, nq, d, k, ef, out_ids, out_dist, out_count, nullptr);
+  return search_batch_host(idx, SearchCall{queries, nq, d, k, ef, out_ids, out_dist, out_count});
 }
 
 // ---- two-level search with a PQ filter (extension, see leann_search_two_level) ----
@@ -1956,64 +1832,24 @@ isl_status isl_index_set_pq_codes(isl_index* idx, const isl_pq* pq, const uint16
 isl_status isl_search_two_level_batch(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d,
                                       uint64_t k, uint64_t ef, float rerank_ratio, uint64_t* out_ids,
                                       float* out_dist, uint32_t* out_count) {
-  const TwoLevelCall tl{rerank_ratio};
-  return search_batch_host(idx, queries, nq, d, k, ef, out_ids, out_dist, out_count, &tl);
+  return search_batch_host(idx, SearchCall{queries, nq, d, k, ef, out_ids, out_dist, out_count, nullptr,
+                                           StreamMode::OWN, true, rerank_ratio});
 }
 
 isl_status isl_search_two_level_batch_device(const isl_index* idx, const float* d_queries, uint64_t nq,
                                              uint64_t d, uint64_t k, uint64_t ef, float rerank_ratio,
                                              uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
                                              void* stream) {
-  int done = 0;
-  ISL_TRY(precheck(idx, nq, d, k, d_out_count, true, &done));
-  if (done == 1) return ISL_OK;
-  ISL_TRY(precheck_two_level(idx, d));
-  if (!d_queries || !d_out_count || (k && (!d_out_ids || !d_out_dist)))
-    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
-  ISL_TRY(isl::use_device(idx->device));
-  isl::SearchWorkspace* ws = claim_lane(idx);
-  if (!ws) return no_lane();
-  LaneGuard guard{idx, ws};
-  const TwoLevelCall tl{rerank_ratio};
-  const isl_status st = search_sync(idx, *ws, d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count,
-                                    (hipStream_t)stream, StreamMode::USER, &tl);
-  note_last_stats(idx, ws->stats);
-  return st;
+  return search_batch_device(idx, SearchCall{d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count,
+                                             (hipStream_t)stream, StreamMode::USER, true, rerank_ratio});
 }
 
 isl_status isl_search_two_level_batch_device_async(const isl_index* idx, const float* d_queries, uint64_t nq,
                                                    uint64_t d, uint64_t k, uint64_t ef, float rerank_ratio,
                                                    uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
                                                    void* stream, uint64_t* token) {
-  if (!token) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "token is NULL");
-  *token = 0;
-  int done = 0;
-  ISL_TRY(precheck(idx, nq, d, k, d_out_count, true, &done));
-  if (done == 1) return ISL_OK;
-  ISL_TRY(precheck_two_level(idx, d));
-  if (!d_queries || !d_out_count || (k && (!d_out_ids || !d_out_dist)))
-    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
-  ISL_TRY(isl::use_device(idx->device));
-  isl::SearchWorkspace* ws = claim_lane(idx);
-  if (!ws) return no_lane();
-  LaneGuard guard{idx, ws};
-  ISL_TRY(ensure_lane_stream(idx, *ws));
-  ISL_HIP(hipEventRecord(ws->ev_in, (hipStream_t)stream));
-  ISL_HIP(hipStreamWaitEvent(ws->stream, ws->ev_in, 0));
-  const TwoLevelCall tl{rerank_ratio};
-  ISL_TRY(start_worker(idx, ws, [=]() {
-    if (idx->recompute)
-      return recompute_coalesced(idx, *ws, d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count, &tl);
-    return search_sync(idx, *ws, d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count, nullptr, StreamMode::OWN,
-                       &tl);
-  }));
-  {
-    std::lock_guard<std::mutex> lock(idx->mu);
-    ws->token = idx->next_token++;
-    *token = ws->token;
-  }
-  guard.keep();
-  return ISL_OK;
+  return search_batch_device_async(idx, SearchCall{d_queries, nq, d, k, ef, d_out_ids, d_out_dist, d_out_count,
+                                                   (hipStream_t)stream, StreamMode::USER, true, rerank_ratio}, token);
 }
 
 isl_status isl_search(const isl_index* idx, const float* query, uint64_t d, uint64_t k,

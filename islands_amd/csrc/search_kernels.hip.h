@@ -1878,12 +1878,19 @@ void launch_one(K kernel, uint32_t grid, size_t lds, hipStream_t st, const Searc
 // Launchers defined in the instantiating units; `params` points at a SearchParams (the struct is
 // the same text in every unit).
 namespace isl_launch {
-// resume = the RESUME instantiation (recompute provider; f32 rows only); qh = the QH instantiation
-// (bf16 rows of up to 64 ids per adjacency row, query held as bf16 in LDS)
-void launch_fast_s1(int metric, bool wide, bool bf16, bool resume, bool qh, uint32_t grid, size_t lds, hipStream_t st, const void* params);
-void launch_fast_s2(int metric, bool wide, bool bf16, bool resume, bool qh, uint32_t grid, size_t lds, hipStream_t st, const void* params);
-void launch_fast_s4(int metric, bool wide, bool bf16, bool resume, bool qh, uint32_t grid, size_t lds, hipStream_t st, const void* params);
-void launch_fast_s8(int metric, bool wide, bool bf16, bool resume, bool qh, uint32_t grid, size_t lds, hipStream_t st, const void* params);
+// Which instantiation of leann_search_fast a launch runs.  S = result-set segments of 64 entries
+// (1, 2, 4, 8); wide = the index has adjacency rows of 65..128 ids (its own instantiation: the common
+// case keeps its register budget); resume = the RESUME instantiation (recompute provider; f32 rows
+// only); qh = the QH instantiation (bf16 rows of up to 64 ids per adjacency row, query held as bf16
+// in LDS)
+struct FastKernel {
+  int S, metric;
+  bool wide, bf16, resume, qh;
+};
+// defined and instantiated for one S by search_fast.hip, which is compiled once per S; search.hip
+// holds the switch over S (launch_fast)
+template <int S>
+void launch_fast_segments(const FastKernel& k, uint32_t grid, size_t lds, hipStream_t st, const void* params);
 // words of one parked query (RESUME) for result sets of S x 64 entries and a visited table of 1 << hbits
 inline uint32_t fast_state_words(int S, uint32_t hbits) { return 208u + (uint32_t)S * 128u + (1u << hbits); }
 void launch_exact(int metric, bool hnsw, uint32_t grid, size_t lds, hipStream_t st, const void* params);
