@@ -570,7 +570,7 @@ isl_status isl_mean_pool_normalize(const float* hidden, const float* mask, uint6
                                    uint64_t H, int32_t normalize, float* out, int32_t mem,
                                    int32_t device, void* stream);
 
-/* ---- HnswGraph, src/core/hnsw.rs:149-515 (search side) ---- */
+/* ---- HnswGraph, src/core/hnsw.rs:149-515 ---- */
 typedef struct isl_hnsw isl_hnsw;
 /* Builds a device-resident HnswGraph from its parts: `levels[i]` = node i's top layer;
  * layer L adjacency in CSR form over ALL nodes (rows of nodes below layer L are empty):
@@ -584,8 +584,8 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
                                 const float* vectors, int32_t device, isl_hnsw** out);
 /* HnswGraph::from_bytes, hnsw.rs:511-514: reads the bincode image of a HnswGraph (1.x default
  * layout; HashMap entries in any order, node ids 0..n-1) and makes it resident on `device`.
- * Truncated or inconsistent input -> ISL_ERR_DESERIALIZATION.  No writer: HashMap order makes the
- * reference's own bytes non-deterministic. */
+ * Truncated or inconsistent input -> ISL_ERR_DESERIALIZATION.  (isl_hnsw_to_bytes writes ascending ids;
+ * HashMap order makes the reference's own bytes non-deterministic) */
 isl_status isl_hnsw_from_bytes(const uint8_t* bytes, size_t len, int32_t device, isl_hnsw** out);
 void isl_hnsw_free(isl_hnsw* h);
 uint64_t isl_hnsw_len(const isl_hnsw* h);
@@ -598,6 +598,61 @@ isl_status isl_hnsw_search_batch(const isl_hnsw* h, const float* queries, uint64
 /* Work counters of the most recent search on this graph (see isl_search_last_stats);
  * exact_path = queries in which two equal distances met and the heap-exact kernel decided. */
 isl_status isl_hnsw_last_stats(const isl_hnsw* h, isl_search_stats* out);
+
+/* ---- HnswGraph construction on the device: HnswGraph::insert, hnsw.rs:214-329 ---- */
+typedef struct isl_hnsw_config { /* HnswConfig, hnsw.rs:15-28 */
+  uint64_t m, m0, ef_construction;
+  double ml;
+  uint32_t metric;
+  uint64_t max_layers;
+} isl_hnsw_config;
+void isl_hnsw_config_default(isl_hnsw_config* cfg); /* 16, 32, 200, 1/ln 16, Cosine, 16: hnsw.rs:37-48 */
+/* random_level (hnsw.rs:206-211) with a seeded generator in place of thread_rng:
+ * out[i] = min(floor(-ln(r_i) * ml), max_layers - 1), r_i = ((x_i >> 11) + 0.5) * 2^-53 in (0, 1),
+ * x_i = splitmix64 output number i of state `seed` (z = seed + (i + 1) * 0x9E3779B97F4A7C15;
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; x_i = z ^ z >> 31).
+ * Host only.  max_layers == 0 or ml not finite -> ISL_ERR_INVALID_ARGUMENT. */
+isl_status isl_hnsw_random_levels(uint64_t seed, uint64_t n, double ml, uint64_t max_layers, uint64_t* out);
+/* Inserts rows 0 .. n-1 in id order into an empty HnswGraph on `device`; `levels[i]` stands for
+ * random_level() (NULL: isl_hnsw_random_levels(level_seed, n, cfg->ml, cfg->max_layers)).  cfg NULL =
+ * the default config; opts NULL = isl_build_options_default.
+ * ISL_SELECT_REFERENCE, batch 1: HnswGraph::insert as written -- greedy descent over layers max_level ..
+ * level + 1, per layer level .. 0 a search_layer with ef_construction from `current`, the first M_L results
+ * (M_L = m0 on layer 0, m above) as the node's list, the new id appended to every selected neighbour that
+ * has the layer, and a list past M_L re-sorted by prune_connections -- which cannot see the node being
+ * inserted (hnsw.rs:417-429 reads a map the node enters at :327) and so drops it again.  Layer lists,
+ * levels, entry point and max level equal the reference's; so does the consequence: once the graph holds
+ * more than m0 nodes no later node receives an inbound edge.
+ * ISL_SELECT_DIVERSE (extension, select() as defined above for isl_index_build_ex): the same loop with the
+ * node's list on layer L = select(i, search result with the search's distances, M_L), and a list that
+ * reaches M_L + 1 ids after the append replaced by select(s, the list stable-sorted by d(s, .), M_L) -- the
+ * new node takes part.  The rule is not recorded in the graph.
+ * opts->batch > 1 (both rules): a throughput mode with the same rules and no parity claim.  A step takes
+ * min(batch, n - id0, max(1, id0 / 8)) nodes, cut so that a node above the current max level is alone in
+ * its step (entry point and max level are the sequential ones for any batch); all of a step's nodes
+ * descend on the graph as of the step's start, then per layer from the step's highest down to 0 they
+ * search, select and link (per-list locks; the order in which back links land is unspecified).
+ * Checked in this order before any device call: opts as in isl_index_build_ex; HnswConfig::validate
+ * (ISL_ERR_INVALID_CONFIG); n == 0 -> an empty graph; d == 0 -> ISL_ERR_EMPTY_COLLECTION; levels[i] >=
+ * max_layers -> ISL_ERR_INVALID_ARGUMENT; m0 > 128, ef_construction > 512 or n beyond the device id range
+ * -> ISL_ERR_UNSUPPORTED.  `vectors`: n rows of d f32 on the host or on `device` (mem = ISL_MEM_*). */
+isl_status isl_hnsw_build(const isl_hnsw_config* cfg, const isl_build_options* opts, const float* vectors,
+                          uint64_t n, uint64_t d, const uint64_t* levels, uint64_t level_seed, int32_t mem,
+                          int32_t device, isl_hnsw** out);
+/* Read-back into host buffers, for every isl_hnsw handle (built, from_layers, from_bytes). */
+isl_status isl_hnsw_info(const isl_hnsw* h, int32_t* has_entry, uint64_t* entry, uint64_t* max_level,
+                         uint64_t* dim);
+isl_status isl_hnsw_levels(const isl_hnsw* h, uint64_t* out /* [len] */);
+/* neighbors_at(layer) of `node`: *count = the list's length (also when cap is smaller: then the first
+ * cap ids are written).  *has_layer (may be NULL) = 1 if the node has the layer (Some), 0 above its level
+ * (None; *count = 0).  node >= len -> ISL_ERR_NODE_NOT_FOUND. */
+isl_status isl_hnsw_get_neighbors(const isl_hnsw* h, uint64_t node, uint64_t layer, uint64_t* out,
+                                  uint64_t cap, uint64_t* count, int32_t* has_layer);
+isl_status isl_hnsw_get_vector(const isl_hnsw* h, uint64_t node, float* out /* [dim] */);
+/* HnswGraph::to_bytes, hnsw.rs:507-509: the bincode image isl_hnsw_from_bytes reads, nodes in ascending
+ * id (the reference's HashMap order is arbitrary), next_id = len; ml / max_layers as built or parsed
+ * (isl_hnsw_from_layers: the default config's).  Free with isl_free_bytes. */
+isl_status isl_hnsw_to_bytes(const isl_hnsw* h, uint8_t** out, size_t* len);
 
 /* isl_distance_matrix for bf16 queries and rows (bit patterns; BASELINE config 5: d = 4096 bf16): the
  * same batch_calculate (distance.rs:32-34) over the exact float32 images of the stored values, on

@@ -255,8 +255,9 @@ struct SearchConfig {
   static SearchConfig accurate(uint64_t k) { SearchConfig c; c.top_k = k; c.ef = k * 10; return c; }
 };
 
-// Search side of HnswGraph, src/core/hnsw.rs:149-515.  Insertion (hnsw.rs:214-329) is outside
-// the search path: the graph is handed over layer by layer (layers[L][node] = neighbour ids).
+// HnswGraph, src/core/hnsw.rs:149-515, on the device.  build() constructs one from its vectors
+// (HnswGraph::insert, hnsw.rs:214-329, as isl_hnsw_build); the constructor takes a graph made elsewhere
+// layer by layer (layers[L][node] = neighbour ids); from_bytes / to_bytes carry the bincode image.
 class HnswGraph {
  public:
   HnswGraph(const std::vector<float>& vectors, uint64_t dim,
@@ -288,6 +289,33 @@ class HnswGraph {
     check(isl_hnsw_from_bytes(bytes.data(), bytes.size(), device, &g.h_));
     return g;
   }
+  // HnswGraph::insert for rows 0 .. n-1 on the device (isl_hnsw_build): `levels` empty = drawn from
+  // level_seed; opts NULL = the reference rule, one node per step
+  static HnswGraph build(const std::vector<float>& vectors, uint64_t dim, const isl_hnsw_config* cfg = nullptr,
+                         const std::vector<uint64_t>& levels = {}, uint64_t level_seed = 0,
+                         const isl_build_options* opts = nullptr, int32_t device = 0) {
+    HnswGraph g;
+    const uint64_t n = dim ? vectors.size() / dim : 0;
+    check(isl_hnsw_build(cfg, opts, n ? vectors.data() : nullptr, n, dim, levels.empty() ? nullptr : levels.data(),
+                         level_seed, ISL_MEM_HOST, device, &g.h_));
+    return g;
+  }
+  // HnswGraph::to_bytes, hnsw.rs:507-509 (nodes in ascending id)
+  std::vector<uint8_t> to_bytes() const {
+    uint8_t* p = nullptr;
+    size_t n = 0;
+    check(isl_hnsw_to_bytes(h_, &p, &n));
+    std::vector<uint8_t> out(p, p + n);
+    isl_free_bytes(p);
+    return out;
+  }
+  std::vector<uint64_t> neighbors(uint64_t node, uint64_t layer) const {  // neighbors_at(layer); empty above the level
+    uint64_t cnt = 0;
+    check(isl_hnsw_get_neighbors(h_, node, layer, nullptr, 0, &cnt, nullptr));
+    std::vector<uint64_t> out(cnt);
+    if (cnt) check(isl_hnsw_get_neighbors(h_, node, layer, out.data(), cnt, &cnt, nullptr));
+    return out;
+  }
   HnswGraph(HnswGraph&& o) noexcept : h_(o.h_), vectors_(std::move(o.vectors_)), dim_(o.dim_) { o.h_ = nullptr; }
   HnswGraph(const HnswGraph&) = delete;
   HnswGraph& operator=(const HnswGraph&) = delete;
@@ -311,8 +339,13 @@ class HnswGraph {
     return out;
   }
   std::optional<std::vector<float>> get_vector(uint64_t id) const {  // get_node(id).vector, hnsw.rs:507-510
-    if (id >= len() || vectors_.empty()) return std::nullopt;  // a graph read by from_bytes keeps no host copy
-    return std::vector<float>(vectors_.begin() + id * dim_, vectors_.begin() + (id + 1) * dim_);
+    if (id >= len()) return std::nullopt;
+    if (!vectors_.empty()) return std::vector<float>(vectors_.begin() + id * dim_, vectors_.begin() + (id + 1) * dim_);
+    uint64_t dim = 0;  // built on the device or read by from_bytes: no host copy, the row comes back from the device
+    check(isl_hnsw_info(h_, nullptr, nullptr, nullptr, &dim));
+    std::vector<float> out(dim);
+    check(isl_hnsw_get_vector(h_, id, out.data()));
+    return out;
   }
 
  private:

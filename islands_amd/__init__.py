@@ -16,7 +16,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _ffi
-from ._ffi import BertConfigC, BuildOptionsC, IndexMetadataC, LeannConfigC, SearchStatsC
+from ._ffi import BertConfigC, BuildOptionsC, IndexMetadataC, LeannConfigC, SearchStatsC, u64
 
 __all__ = [
     "CoreError", "DistanceMetric", "PruningStrategy", "LeannConfig", "CsrGraph",
@@ -814,9 +814,10 @@ class ProductQuantizer:
 
 # ------------------------------------------------------------------- hnsw.rs
 class HnswGraph:
-    """Search side of HnswGraph (hnsw.rs:149-515) on the device.  Construction (insert,
-    hnsw.rs:214-329) is outside the search path: the graph is handed over as per-layer adjacency
-    (`layers[L][node]` = neighbour ids of `node` on layer L, empty above the node's level)."""
+    """HnswGraph (hnsw.rs:149-515) on the device.  `build` constructs one from its vectors
+    (HnswGraph::insert, hnsw.rs:214-329, as isl_hnsw_build); the constructor takes a graph made
+    elsewhere as per-layer adjacency (`layers[L][node]` = neighbour ids of `node` on layer L, empty
+    above the node's level); `from_bytes` / `to_bytes` carry the bincode image."""
 
     def __init__(self, vectors, layers, levels, entry_point: int | None, max_level: int,
                  m: int = 16, m0: int = 32, ef_construction: int = 200,
@@ -878,6 +879,107 @@ class HnswGraph:
         g.vectors = None
         return g
 
+    @classmethod
+    def build(cls, vectors, m: int = 16, m0: int = 32, ef_construction: int = 200,
+              metric: DistanceMetric = DistanceMetric.Cosine, ml: float | None = None, max_layers: int = 16,
+              levels=None, level_seed: int = 0, batch: int = 1, select="reference", alpha: float = 1.0,
+              keep_pruned: bool = True, device: int = 0) -> "HnswGraph":
+        """HnswGraph::insert for rows 0 .. n-1 on the device (isl_hnsw_build).  `levels[i]` stands for
+        random_level(); None draws them from `level_seed` (random_levels).  ml = None is
+        HnswConfig::default()'s 1 / ln 16.  select = "reference", batch = 1 reproduces the reference's
+        graph list by list -- including its defect: a full list drops the node being inserted, so late
+        nodes get no inbound edge.  select = "diverse" is the occlusion rule of LeannIndex.build
+        applied to both selections of the loop, with the new node taking part in a re-selection; that
+        is the rule for an index meant to be searched.  batch > 1 inserts that many nodes per step
+        (same rules, no parity claim).  `vectors`: an array, or a float32 torch tensor resident on
+        `device` (used in place)."""
+        on_device = hasattr(vectors, "data_ptr") and getattr(vectors, "is_cuda", False)
+        if on_device:
+            v = vectors.contiguous()
+            if str(v.dtype) != "torch.float32":
+                raise TypeError("device rows must be float32")
+            n, d = (int(v.shape[0]), int(v.shape[1])) if v.dim() == 2 else (0, 0)
+            vp = C.c_void_p(v.data_ptr())
+        else:
+            v = _f32(vectors)
+            n, d = v.shape if v.ndim == 2 else (0, 0)
+            vp = _ptr(v)
+        c = _ffi.HnswConfigC()
+        _ffi.lib().isl_hnsw_config_default(C.byref(c))
+        c.m, c.m0, c.ef_construction, c.metric, c.max_layers = m, m0, ef_construction, int(metric), max_layers
+        if ml is not None:
+            c.ml = float(ml)
+        lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint64)
+        if lv is not None and lv.size != n:
+            raise ValueError("one level per row")
+        o = LeannIndex._build_options(select, alpha, keep_pruned, batch)
+        h = C.c_void_p()
+        _check(_ffi.lib().isl_hnsw_build(C.byref(c), C.byref(o), vp if n else None, n, d,
+                                         None if lv is None or not n else _ptr(lv), level_seed,
+                                         MEM_DEVICE if on_device else MEM_HOST, device, C.byref(h)))
+        g = cls.__new__(cls)
+        g._h = h
+        g._keep = None
+        g.vectors = None
+        g.m, g.m0, g.ef_construction, g.metric = m, m0, ef_construction, DistanceMetric(metric)
+        return g
+
+    @staticmethod
+    def random_levels(n: int, ml: float | None = None, max_layers: int = 16, seed: int = 0) -> np.ndarray:
+        """isl_hnsw_random_levels: random_level (hnsw.rs:206-211) for n nodes from a seeded generator."""
+        out = np.zeros(n, dtype=np.uint64)
+        _check(_ffi.lib().isl_hnsw_random_levels(seed, n, 1.0 / np.log(16.0) if ml is None else float(ml),
+                                                 max_layers, _ptr(out) if n else None))
+        return out
+
+    def _info(self):
+        he, e, ml, dim = C.c_int32(), u64(), u64(), u64()
+        _check(_ffi.lib().isl_hnsw_info(self._h, C.byref(he), C.byref(e), C.byref(ml), C.byref(dim)))
+        return (int(e.value) if he.value else None), int(ml.value), int(dim.value)
+
+    @property
+    def entry_point(self) -> int | None:
+        return self._info()[0]
+
+    @property
+    def max_level(self) -> int:
+        return self._info()[1]
+
+    def levels(self) -> np.ndarray:
+        out = np.zeros(len(self), dtype=np.uint64)
+        _check(_ffi.lib().isl_hnsw_levels(self._h, _ptr(out) if out.size else None))
+        return out
+
+    def level(self, node: int) -> int | None:
+        """get_node(id).level"""
+        if getattr(self, "_levels", None) is None:  # a handle's levels never change: read once
+            self._levels = self.levels()
+        return int(self._levels[node]) if 0 <= node < self._levels.size else None
+
+    def neighbors(self, node: int, layer: int) -> list[int] | None:
+        """neighbors_at(layer) of a node (hnsw.rs:121-123): None above the node's level (the library
+        says which, isl_hnsw_get_neighbors) or for an unknown node."""
+        if not 0 <= node < len(self):
+            return None
+        out = np.zeros(129, dtype=np.uint64)  # (the builder's longest list; a graph handed over may have longer ones)
+        cnt, has = u64(), C.c_int32()
+        _check(_ffi.lib().isl_hnsw_get_neighbors(self._h, node, layer, _ptr(out), out.size, C.byref(cnt), C.byref(has)))
+        if not has.value:
+            return None
+        if cnt.value > out.size:
+            out = np.zeros(cnt.value, dtype=np.uint64)
+            _check(_ffi.lib().isl_hnsw_get_neighbors(self._h, node, layer, _ptr(out), out.size, C.byref(cnt), None))
+        return out[:cnt.value].tolist()
+
+    def to_bytes(self) -> bytes:
+        """HnswGraph::to_bytes (hnsw.rs:507-509): nodes in ascending id."""
+        p, n = C.c_void_p(), C.c_size_t()
+        _check(_ffi.lib().isl_hnsw_to_bytes(self._h, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            _ffi.lib().isl_free_bytes(p)
+
     def last_stats(self) -> dict:
         s = SearchStatsC()
         _check(_ffi.lib().isl_hnsw_last_stats(self._h, C.byref(s)))
@@ -885,7 +987,13 @@ class HnswGraph:
 
     def get_vector(self, node: int):
         """get_node(id).vector, hnsw.rs:507-510"""
-        return self.vectors[node] if 0 <= node < self.vectors.shape[0] else None
+        if self.vectors is not None:
+            return self.vectors[node] if 0 <= node < self.vectors.shape[0] else None
+        if not 0 <= node < len(self):
+            return None
+        out = np.zeros(self._info()[2], dtype=np.float32)
+        _check(_ffi.lib().isl_hnsw_get_vector(self._h, node, _ptr(out)))
+        return out
 
     def search_batch(self, queries, k: int, ef: int):
         """Batched HnswGraph::search (hnsw.rs:458-504): per query the (id, distance) list."""

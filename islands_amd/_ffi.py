@@ -57,6 +57,12 @@ class BuildOptionsC(C.Structure):
                 ("batch", u64)]
 
 
+class HnswConfigC(C.Structure):
+    """isl_hnsw_config == HnswConfig, src/core/hnsw.rs:15-28."""
+    _fields_ = [("m", u64), ("m0", u64), ("ef_construction", u64), ("ml", C.c_double), ("metric", u32),
+                ("max_layers", u64)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/islands_amd.h
 SIGNATURES = {
     "isl_last_error_message": (C.c_char_p, []),
@@ -189,6 +195,15 @@ SIGNATURES = {
     "isl_hnsw_last_stats": (i32, [C.c_void_p, P(SearchStatsC)]),
     "isl_hnsw_search_batch": (i32, [C.c_void_p, C.c_void_p, u64, u64, u64, u64, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "isl_hnsw_config_default": (None, [P(HnswConfigC)]),
+    "isl_hnsw_random_levels": (i32, [u64, u64, C.c_double, u64, C.c_void_p]),
+    "isl_hnsw_build": (i32, [P(HnswConfigC), P(BuildOptionsC), C.c_void_p, u64, u64, C.c_void_p, u64, i32, i32,
+                             P(C.c_void_p)]),
+    "isl_hnsw_info": (i32, [C.c_void_p, P(i32), P(u64), P(u64), P(u64)]),
+    "isl_hnsw_levels": (i32, [C.c_void_p, C.c_void_p]),
+    "isl_hnsw_get_neighbors": (i32, [C.c_void_p, u64, u64, C.c_void_p, u64, P(u64), P(i32)]),
+    "isl_hnsw_get_vector": (i32, [C.c_void_p, u64, C.c_void_p]),
+    "isl_hnsw_to_bytes": (i32, [C.c_void_p, P(C.c_void_p), P(C.c_size_t)]),
     "isl_pq_new": (i32, [u64, u64, u64, C.c_void_p, i32, i32, P(C.c_void_p)]),
     "isl_pq_free": (None, [C.c_void_p]),
     "isl_pq_build_distance_tables": (i32, [C.c_void_p, C.c_void_p, u64, u64, C.c_void_p, i32,

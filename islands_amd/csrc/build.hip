@@ -13,7 +13,11 @@
 // ISL_SELECT_DIVERSE (isl_index_build_ex) swaps the two selections of that loop -- the new node's
 // row and the re-selection of a row that outgrew m0 -- for the occlusion rule defined in
 // include/islands_amd.h; everything else (order, construction search, locks, step ramp) is shared.
+//
+// The HnswGraph builder (hnsw_build.hip) runs the same selection kernels and link_kernel's HNSW mode
+// over one fixed-width table per layer (build_internal.hpp).
 #include "device_common.hip.h"
+#include "build_internal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -23,29 +27,7 @@ namespace {
 
 using namespace isl_dev;
 
-struct BuildParams {
-  const float* emb;
-  const float* norm2;
-  uint64_t stride;
-  uint32_t d;
-  uint32_t* ell;       // [n][W]
-  uint32_t* ell_deg;   // [n]
-  uint32_t* lock;      // [n]
-  uint32_t W, m0;
-  uint32_t ef;         // candidates per new node (row pitch of cand_*)
-  const uint64_t* cand_ids;   // [B][ef] ascending distance (search output)
-  const float* cand_dist;
-  const uint32_t* cand_cnt;   // [B]
-  uint32_t* sel;       // [B][m0] selected neighbours
-  uint32_t* sel_cnt;   // [B]
-  uint64_t id0;        // first node of the step
-  uint32_t B;
-  float hub_percentile;
-  uint32_t high_degree;  // LeannConfig::high_degree_pruning
-  uint32_t locking;      // batch > 1
-  float alpha;           // ISL_SELECT_DIVERSE: occlusion factor
-  uint32_t keep_pruned;  // ISL_SELECT_DIVERSE: occluded candidates fill a short row
-};
+using isl_build::BuildParams;
 
 // ---------------------------------------------------------------- ISL_SELECT_DIVERSE
 // What a selection reads besides its lists: the rows and the rule's two parameters.
@@ -293,21 +275,27 @@ __global__ __launch_bounds__(64) void select_neighbors_kernel(SelectNeighborsPar
 
 // adjacency.push(neighbors) + bidirectional links + prune_neighbors_temp, leann.rs:592-607, 634-658
 // DIVERSE: a row that outgrew m0 is re-selected by the occlusion rule instead of cut at m0.
-template <int METRIC_API, bool DIVERSE = false>
+// HNSW: insert_node of HnswGraph on one layer (hnsw.rs:295-318): the step's nodes come from node_ids, a
+// selected neighbour takes the back link only if it has the layer, the new id is appended without a
+// `contains` test, and the reference rule's re-sort (prune_connections, :405-446) leaves the new id out --
+// it looks every id up in the node map, which the node being inserted has not entered yet.
+template <int METRIC_API, bool DIVERSE = false, bool HNSW = false>
 __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
   constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
   extern __shared__ __align__(16) unsigned char smem[];
   float* tile = reinterpret_cast<float*>(smem);
   float* qs = tile + TILE_ROWS * TILE_LD;
   const uint32_t lane = threadIdx.x, b = blockIdx.x;
-  const uint32_t node = (uint32_t)(p.id0 + b);
+  const uint32_t node = HNSW ? p.node_ids[b] : (uint32_t)(p.id0 + b);
   const uint32_t nsel = p.sel_cnt[b];
   const uint32_t* sel = p.sel + (uint64_t)b * p.m0;
   // adjacency.push(neighbors.clone()), :592
   for (uint32_t i = lane; i < nsel; i += 64) p.ell[(uint64_t)node * p.W + i] = sel[i];
   if (lane == 0) p.ell_deg[node] = nsel;
+  if (HNSW && lane == 0 && nsel) p.cur_of[node] = sel[0];  // current = selected[0], hnsw.rs:316-318
   for (uint32_t t = 0; t < nsel; ++t) {
     const uint32_t nid = sel[t];
+    if (HNSW && p.node_levels[nid] < p.layer) continue;  // hnsw.rs:305: no such layer, no back link
     if (p.locking) {
       if (lane == 0) while (atomicCAS(&p.lock[nid], 0u, 1u) != 0u) __builtin_amdgcn_s_sleep(1);
       __threadfence();
@@ -316,11 +304,13 @@ __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
     uint32_t* row = p.ell + (uint64_t)nid * p.W;
     uint32_t dg = *((volatile uint32_t*)&p.ell_deg[nid]);
     bool has = false;
-    for (uint32_t i = lane; i < dg; i += 64) has |= ((volatile uint32_t*)row)[i] == node;
-    if (!ballot(has)) {  // :596 if !adjacency[nid].contains(&id)
+    if (!HNSW)
+      for (uint32_t i = lane; i < dg; i += 64) has |= ((volatile uint32_t*)row)[i] == node;
+    if (HNSW || !ballot(has)) {  // :596 if !adjacency[nid].contains(&id); HnswGraph pushes unconditionally
       if (lane == 0) row[dg] = node;
       dg += 1;
       if (dg > p.m0) {
+        if (HNSW && !DIVERSE) dg = p.m0;  // the id just pushed (the last slot) is not a candidate
         // prune_neighbors_temp: distances from nid to every neighbour, stable sort, keep m0
         __threadfence_block();
         __syncthreads();
@@ -428,6 +418,18 @@ void launch_link_diverse(int metric, uint32_t grid, size_t lds, const BuildParam
                        dim3(64), lds, 0, p)
 }
 
+void launch_link_hnsw_reference(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  ISL_LAUNCH_BY_METRIC(metric, (link_kernel<ISL_METRIC_COSINE, false, true>), (link_kernel<ISL_METRIC_EUCLIDEAN, false, true>),
+                       (link_kernel<ISL_METRIC_DOT, false, true>), (link_kernel<ISL_METRIC_MANHATTAN, false, true>),
+                       dim3(grid), dim3(64), lds, 0, p)
+}
+
+void launch_link_hnsw_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  ISL_LAUNCH_BY_METRIC(metric, (link_kernel<ISL_METRIC_COSINE, true, true>), (link_kernel<ISL_METRIC_EUCLIDEAN, true, true>),
+                       (link_kernel<ISL_METRIC_DOT, true, true>), (link_kernel<ISL_METRIC_MANHATTAN, true, true>),
+                       dim3(grid), dim3(64), lds, 0, p)
+}
+
 void launch_select_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
   ISL_LAUNCH_BY_METRIC(metric, select_diverse_kernel<ISL_METRIC_COSINE>, select_diverse_kernel<ISL_METRIC_EUCLIDEAN>,
                        select_diverse_kernel<ISL_METRIC_DOT>, select_diverse_kernel<ISL_METRIC_MANHATTAN>, dim3(grid),
@@ -441,8 +443,10 @@ void launch_select_neighbors(int metric, uint32_t grid, size_t lds, const Select
 }
 #undef ISL_LAUNCH_BY_METRIC
 
+}  // namespace
+
 // struct_size, rule and alpha of caller-supplied options, before any device call
-isl_status check_build_options(const isl_build_options* o, bool need_rule) {
+isl_status isl_build::check_build_options(const isl_build_options* o, bool need_rule) {
   using isl::fail;
   if (o->struct_size < sizeof(isl_build_options))
     return fail(ISL_ERR_INVALID_ARGUMENT, "isl_build_options.struct_size %u is smaller than %zu", o->struct_size,
@@ -454,7 +458,25 @@ isl_status check_build_options(const isl_build_options* o, bool need_rule) {
   return ISL_OK;
 }
 
-}  // namespace
+size_t isl_build::select_lds(uint64_t d, uint32_t nmax, uint32_t M) { return ::sel_lds(d, nmax, M); }
+size_t isl_build::link_lds(uint64_t d) { return (size_t)TILE_ROWS * TILE_LD * 4 + (size_t)((d + 3) / 4 * 4) * 4 + 64; }
+
+void isl_build::select_truncate(uint32_t grid, const BuildParams& p) {
+  hipLaunchKernelGGL(select_kernel, dim3(grid), dim3(64), (size_t)p.ef * 12, 0, p);
+}
+void isl_build::select_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  ::launch_select_diverse(metric, grid, lds, p);
+}
+void isl_build::link_hnsw(int metric, bool diverse, uint32_t grid, size_t lds, const BuildParams& p) {
+  if (diverse) launch_link_hnsw_diverse(metric, grid, lds, p);
+  else launch_link_hnsw_reference(metric, grid, lds, p);
+}
+void isl_build::ell_to_csr(const uint32_t* ell, const uint32_t* deg, uint32_t W, const uint64_t* off,
+                                  uint64_t n, uint32_t* adj) {
+  hipLaunchKernelGGL(ell_to_csr_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, 0, ell, deg, W, off, n, adj);
+}
+
+using isl_build::check_build_options;
 
 extern "C" void isl_build_options_default(isl_build_options* o) {
   if (!o) return;

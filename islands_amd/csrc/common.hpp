@@ -218,6 +218,13 @@ struct isl_index {
   uint32_t ell_w = 0;
   bool ell_owned = false;         // the padded copy made at the first search (freed with the index)
 
+  // HnswGraph under construction (hnsw_build.hip): [nq] entry node of every query of the next construction
+  // search on the layer in d_ell, and the evaluations its counters start from (device arrays, borrowed);
+  // nothing descends.  The builder hands in the descent's count for every layer: it does not read the
+  // construction searches' counters, so they are not HnswGraph's running count below the first layer searched.
+  uint32_t* build_q_entry = nullptr;
+  uint32_t* build_q_evals = nullptr;
+
   // recompute provider (EmbeddingProvider backed by the encoder, leann.rs:82-99): embeddings are
   // not stored (leann.rs:366-371); the search reports the rows it misses and the provider encodes
   // them from the resident token table into a bounded row cache
@@ -263,6 +270,23 @@ struct isl_index {
   mutable isl::SearchWorkspace ws[isl::kSearchLanes];
   mutable isl::ExactPool pool;
   mutable uint64_t next_token = 1;
+};
+
+// HnswGraph handle (hnsw.hip, hnsw_build.hip).
+struct isl_hnsw {
+  isl_index* core = nullptr;  // layer 0 + vectors + workspaces
+  uint64_t m = 0, m0 = 0, ef_construction = 0;
+  uint64_t dim = 0;
+  double ml = 0.0;            // HnswConfig::ml / max_layers: carried for to_bytes
+  uint64_t max_layers = 16;
+  // upper layers as the device holds them (host copies of the pointers in core->d_layer_off / d_layer_adj)
+  std::vector<const uint64_t*> layer_off;
+  std::vector<const uint32_t*> layer_adj;
+  // host mirror of every layer in CSR form, read back on demand (get_neighbors, to_bytes)
+  mutable std::mutex host_mu;
+  mutable bool host_valid = false;
+  mutable std::vector<std::vector<uint64_t>> h_off;
+  mutable std::vector<std::vector<uint64_t>> h_adj;
 };
 
 namespace isl {

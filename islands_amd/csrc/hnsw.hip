@@ -5,13 +5,8 @@
 #include "common.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
-
-struct isl_hnsw {
-  isl_index* core = nullptr;  // layer 0 + vectors + workspaces
-  uint64_t m = 0, m0 = 0, ef_construction = 0;
-  uint64_t dim = 0;
-};
 
 namespace {
 
@@ -61,6 +56,8 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
     return isl::fail(ISL_ERR_INVALID_ARGUMENT, "layers do not cover max_level");
   isl_hnsw* h = new isl_hnsw();
   h->m = m; h->m0 = m0; h->ef_construction = ef_construction; h->dim = d;
+  h->ml = 1.0 / std::log(16.0);  // HnswConfig::default(), hnsw.rs:37-48 (from_bytes: as parsed)
+  h->max_layers = 16;
   auto bail = [&](isl_status st) { isl_hnsw_free(h); return st; };
   isl_leann_config cfg;
   isl_leann_config_paper_default(&cfg);
@@ -116,6 +113,8 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
       hipMemcpy((void*)c->d_layer_adj, adjs.data(), (max_level + 1) * sizeof(void*), hipMemcpyHostToDevice) != hipSuccess)
     return bail(isl::fail(ISL_ERR_DEVICE, "layer table upload failed"));
   c->hnsw_layers = max_level + 1;
+  h->layer_off = offs;
+  h->layer_adj = adjs;
   *out = h;
   return ISL_OK;
 }
@@ -154,9 +153,9 @@ static isl_status hnsw_from_bytes_impl(const uint8_t* bytes, size_t len, int32_t
                      (unsigned long long)pos, (unsigned long long)len);
   };
   const uint64_t m = u64(), m0 = u64(), efc = u64();
-  (void)u64();  // ml: f64, only used by random_level (hnsw.rs:196-200)
+  const uint64_t ml_bits = u64();  // ml: f64, only used by random_level (hnsw.rs:196-200); kept for to_bytes
   const uint32_t metric = u32();
-  (void)u64();  // max_layers
+  const uint64_t max_layers = u64();
   const uint64_t n = u64();
   if (!ok) return bad("truncated header");
   if (metric > ISL_METRIC_MANHATTAN) return bad("unknown DistanceMetric variant");
@@ -220,8 +219,11 @@ static isl_status hnsw_from_bytes_impl(const uint8_t* bytes, size_t len, int32_t
   }
   std::vector<const uint64_t*> po(num_layers), pa(num_layers);
   for (uint64_t L = 0; L < num_layers; ++L) { po[L] = offs[L].data(); pa[L] = adjs[L].data(); }
-  return isl_hnsw_from_layers(m, m0, efc, (int32_t)metric, n, n ? d : dim, num_layers, po.data(), pa.data(),
-                              levels.data(), has_entry, entry, max_level, vectors.data(), device, out);
+  ISL_TRY(isl_hnsw_from_layers(m, m0, efc, (int32_t)metric, n, n ? d : dim, num_layers, po.data(), pa.data(),
+                               levels.data(), has_entry, entry, max_level, vectors.data(), device, out));
+  memcpy(&(*out)->ml, &ml_bits, 8);
+  (*out)->max_layers = max_layers;
+  return ISL_OK;
 }
 
 isl_status isl_hnsw_search_batch(const isl_hnsw* h, const float* queries, uint64_t nq, uint64_t d,

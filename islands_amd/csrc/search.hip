@@ -489,6 +489,14 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.hnsw_order = idx->is_hnsw ? 1u : 0u;
   p.q_entry = nullptr;
   p.q_evals = nullptr;
+  if (idx->build_q_entry && !warm) {
+    // construction search of the HnswGraph builder: per-query entry nodes on the layer in d_ell, no descent
+    p.q_entry = idx->build_q_entry;
+    p.q_evals = idx->build_q_evals;
+    p.entry_given = 1u;
+    p.max_level = 0u;
+    ISL_HIP(hipMemsetAsync(ws.status, 0, nq * 4, st));  // QS_OK: the fast kernel reads it where q_entry is set
+  }
   if (tl) {
     const isl_pq* pq = idx->pq;
     const uint64_t want = std::max<uint64_t>(nq, 1) * pq->m * pq->K;

@@ -111,6 +111,9 @@ struct SearchParams {
   uint32_t seq_max;     // hops with at most this many pushes insert one by one (cheaper than a merge)
   uint32_t* q_entry;    // [nq] layer-0 entry per query after the greedy descent (HnswGraph), or NULL
   uint32_t* q_evals;    // [nq] distance evaluations of the descent (+ 1 for the entry point)
+  // graph under construction (hnsw_build.hip): q_entry / q_evals are the CALLER's per-query entry nodes on the
+  // layer being searched; no kernel descends (the heap-exact kernel included)
+  uint32_t entry_given;
   // two-level search (extension, leann_search_two_level)
   const float* tl_tables;     // [nq][tl_m][tl_K] distances of build_distance_tables
   const uint16_t* tl_codes;   // [tl_ncodes][tl_m]
@@ -726,7 +729,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void le
     if (!p.q_entry && (uint64_t)p.entry >= p.nvec) {
       status = QS_NODE_NOT_FOUND;
       payload = p.entry;
-    } else if (!rows_present(p, p.entry, 1)) {
+    } else if (p.entry_given && (uint64_t)p.q_entry[qi] >= p.nvec) {  // a caller's entry node is checked like p.entry
+      status = QS_NODE_NOT_FOUND;
+      payload = p.q_entry[qi];
+    } else if (!rows_present(p, p.entry_given ? p.q_entry[qi] : p.entry, 1)) {
       status = QS_BLOCKED;
     } else {
       // HnswGraph: the layer-0 search starts where the greedy descent (hnsw_descent_kernel) ended
@@ -1180,18 +1186,18 @@ __global__ __launch_bounds__(64) void leann_search_exact(SearchParams p) {
       __threadfence_block();
       __syncthreads();
     } else
-    if ((uint64_t)p.entry >= p.nvec) {
+    if ((uint64_t)(p.entry_given ? p.q_entry[qi] : p.entry) >= p.nvec) {
       status = QS_NODE_NOT_FOUND;
-      payload = p.entry;
-    } else if (!rows_present(p, p.entry, 1)) {
+      payload = p.entry_given ? p.q_entry[qi] : p.entry;
+    } else if (!rows_present(p, p.entry_given ? p.q_entry[qi] : p.entry, 1)) {
       status = QS_BLOCKED;
     } else {
-      uint32_t entry = p.entry;
+      uint32_t entry = p.entry_given ? p.q_entry[qi] : p.entry;
       const uint32_t erow = row_index(p, entry, true);
       float e_aux = METRIC == METRIC_COSINE_PRE ? p.norm2[erow] : 0.0f;
       float ed = rl_f(exact_rows<METRIC>(p, erow, 1, qs, tile, q_norm, e_aux), 0);
-      cV = 1;
-      if (HNSW) {
+      cV = p.entry_given ? p.q_evals[qi] : 1;
+      if (HNSW && !p.entry_given) {
         // greedy search from the top layer down to layer 1, hnsw.rs:478-497: per round the
         // neighbours of the node the round STARTED at are scanned in order, `current` moves to
         // every strictly closer one (= first occurrence of the minimum if it beats current)
