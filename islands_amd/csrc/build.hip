@@ -15,7 +15,10 @@
 // include/islands_amd.h; everything else (order, construction search, locks, step ramp) is shared.
 //
 // The HnswGraph builder (hnsw_build.hip) runs the same selection kernels and link_kernel's HNSW mode
-// over one fixed-width table per layer (build_internal.hpp).
+// over one fixed-width table per layer.  Both go through one host path, isl_build::Scaffold
+// (build_internal.hpp, defined below the kernels): the construction graph and everything allocated for
+// it, "insert these nodes on this table", table -> CSR, one way out on failure.  The steps and the LDS
+// sizes are build_plan.hpp's.
 #include "device_common.hip.h"
 #include "build_internal.hpp"
 
@@ -48,7 +51,7 @@ struct SelState {
   uint32_t* kept;  // [nmax] 1 = kept
   uint32_t* out;   // [M] the row: kept, then the fillers
 };
-__device__ __forceinline__ uint32_t query_floats(uint32_t d) { return (d + 3u) / 4u * 4u + 16u; }
+using isl_plan::query_floats;  // (constexpr: the figure the host reserves is the one the kernels lay out by)
 __device__ __forceinline__ SelState sel_state(float* qs, uint32_t d, uint32_t nmax) {
   uint32_t* w = reinterpret_cast<uint32_t*>(qs + query_floats(d));
   SelState s;
@@ -394,59 +397,33 @@ __global__ void gather_rows_kernel(const float* __restrict__ emb, uint64_t strid
   out[i] = emb[(id0 + i / d) * stride + i % d];
 }
 
-// bytes of LDS behind the tile: the query (and its slack) plus the lists of a selection
-size_t sel_lds(uint64_t d, uint32_t nmax, uint32_t M) {
-  return (size_t)TILE_ROWS * TILE_LD * 4 + (size_t)((d + 3) / 4 * 4) * 4 + 64 + (size_t)nmax * 16 + (size_t)M * 4;
-}
+constexpr size_t kTileBytes = (size_t)TILE_ROWS * TILE_LD * 4;
+size_t sel_lds(uint64_t d, uint32_t nmax, uint32_t M) { return isl_plan::select_lds(kTileBytes, (uint32_t)d, nmax, M); }
 
-#define ISL_LAUNCH_BY_METRIC(metric, K0, K1, K2, K3, ...)               \
-  switch (metric) {                                                     \
-    case ISL_METRIC_COSINE: hipLaunchKernelGGL(K0, __VA_ARGS__); break;    \
-    case ISL_METRIC_EUCLIDEAN: hipLaunchKernelGGL(K1, __VA_ARGS__); break; \
-    case ISL_METRIC_DOT: hipLaunchKernelGGL(K2, __VA_ARGS__); break;       \
-    default: hipLaunchKernelGGL(K3, __VA_ARGS__); break;                   \
-  }
-
-void launch_link(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  ISL_LAUNCH_BY_METRIC(metric, link_kernel<ISL_METRIC_COSINE>, link_kernel<ISL_METRIC_EUCLIDEAN>,
-                       link_kernel<ISL_METRIC_DOT>, link_kernel<ISL_METRIC_MANHATTAN>, dim3(grid), dim3(64), lds, 0, p)
+// one wave per node of the step, the kernel instantiated for the index's metric
+template <bool DIVERSE, bool HNSW>
+void launch_link_as(uint32_t metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  isl_build::by_metric(metric, [&](auto mc) {
+    hipLaunchKernelGGL((link_kernel<decltype(mc)::value, DIVERSE, HNSW>), dim3(grid), dim3(64), lds, 0, p);
+  });
 }
-
-void launch_link_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  ISL_LAUNCH_BY_METRIC(metric, (link_kernel<ISL_METRIC_COSINE, true>), (link_kernel<ISL_METRIC_EUCLIDEAN, true>),
-                       (link_kernel<ISL_METRIC_DOT, true>), (link_kernel<ISL_METRIC_MANHATTAN, true>), dim3(grid),
-                       dim3(64), lds, 0, p)
+void launch_link(uint32_t metric, bool diverse, bool hnsw, uint32_t grid, size_t lds, const BuildParams& p) {
+  if (!diverse && !hnsw) launch_link_as<false, false>(metric, grid, lds, p);
+  else if (!hnsw) launch_link_as<true, false>(metric, grid, lds, p);
+  else if (!diverse) launch_link_as<false, true>(metric, grid, lds, p);
+  else launch_link_as<true, true>(metric, grid, lds, p);
 }
-
-void launch_link_hnsw_reference(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  ISL_LAUNCH_BY_METRIC(metric, (link_kernel<ISL_METRIC_COSINE, false, true>), (link_kernel<ISL_METRIC_EUCLIDEAN, false, true>),
-                       (link_kernel<ISL_METRIC_DOT, false, true>), (link_kernel<ISL_METRIC_MANHATTAN, false, true>),
-                       dim3(grid), dim3(64), lds, 0, p)
+void launch_select_diverse(uint32_t metric, uint32_t grid, size_t lds, const BuildParams& p) {
+  isl_build::by_metric(metric, [&](auto mc) {
+    hipLaunchKernelGGL(select_diverse_kernel<decltype(mc)::value>, dim3(grid), dim3(64), lds, 0, p);
+  });
 }
-
-void launch_link_hnsw_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  ISL_LAUNCH_BY_METRIC(metric, (link_kernel<ISL_METRIC_COSINE, true, true>), (link_kernel<ISL_METRIC_EUCLIDEAN, true, true>),
-                       (link_kernel<ISL_METRIC_DOT, true, true>), (link_kernel<ISL_METRIC_MANHATTAN, true, true>),
-                       dim3(grid), dim3(64), lds, 0, p)
-}
-
-void launch_select_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  ISL_LAUNCH_BY_METRIC(metric, select_diverse_kernel<ISL_METRIC_COSINE>, select_diverse_kernel<ISL_METRIC_EUCLIDEAN>,
-                       select_diverse_kernel<ISL_METRIC_DOT>, select_diverse_kernel<ISL_METRIC_MANHATTAN>, dim3(grid),
-                       dim3(64), lds, 0, p)
-}
-
-void launch_select_neighbors(int metric, uint32_t grid, size_t lds, const SelectNeighborsParams& p) {
-  ISL_LAUNCH_BY_METRIC(metric, select_neighbors_kernel<ISL_METRIC_COSINE>, select_neighbors_kernel<ISL_METRIC_EUCLIDEAN>,
-                       select_neighbors_kernel<ISL_METRIC_DOT>, select_neighbors_kernel<ISL_METRIC_MANHATTAN>, dim3(grid),
-                       dim3(64), lds, 0, p)
-}
-#undef ISL_LAUNCH_BY_METRIC
 
 }  // namespace
 
-// struct_size, rule and alpha of caller-supplied options, before any device call
-isl_status isl_build::check_build_options(const isl_build_options* o, bool need_rule) {
+namespace isl_build {
+
+isl_status check_build_options(const isl_build_options* o, bool need_rule) {
   using isl::fail;
   if (o->struct_size < sizeof(isl_build_options))
     return fail(ISL_ERR_INVALID_ARGUMENT, "isl_build_options.struct_size %u is smaller than %zu", o->struct_size,
@@ -458,25 +435,120 @@ isl_status isl_build::check_build_options(const isl_build_options* o, bool need_
   return ISL_OK;
 }
 
-size_t isl_build::select_lds(uint64_t d, uint32_t nmax, uint32_t M) { return ::sel_lds(d, nmax, M); }
-size_t isl_build::link_lds(uint64_t d) { return (size_t)TILE_ROWS * TILE_LD * 4 + (size_t)((d + 3) / 4 * 4) * 4 + 64; }
+size_t link_lds(uint64_t d) { return isl_plan::link_lds(kTileBytes, (uint32_t)d); }
 
-void isl_build::select_truncate(uint32_t grid, const BuildParams& p) {
-  hipLaunchKernelGGL(select_kernel, dim3(grid), dim3(64), (size_t)p.ef * 12, 0, p);
-}
-void isl_build::select_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  ::launch_select_diverse(metric, grid, lds, p);
-}
-void isl_build::link_hnsw(int metric, bool diverse, uint32_t grid, size_t lds, const BuildParams& p) {
-  if (diverse) launch_link_hnsw_diverse(metric, grid, lds, p);
-  else launch_link_hnsw_reference(metric, grid, lds, p);
-}
-void isl_build::ell_to_csr(const uint32_t* ell, const uint32_t* deg, uint32_t W, const uint64_t* off,
-                                  uint64_t n, uint32_t* adj) {
-  hipLaunchKernelGGL(ell_to_csr_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, 0, ell, deg, W, off, n, adj);
+Scaffold::~Scaffold() {
+  const isl::ErrorRecord first = isl::last_error();
+  for (void* q : tmp) (void)hipFree(q);
+  for (void* q : keep) (void)hipFree(q);
+  isl_index_free(res);
+  if (g) {  // the tables and per-query arrays it searched were borrowed from tmp
+    g->d_ell = nullptr; g->d_ell_deg = nullptr;
+    g->build_q_entry = nullptr; g->build_q_evals = nullptr;
+    isl_index_free(g);
+  }
+  isl::last_error() = first;
 }
 
-using isl_build::check_build_options;
+isl_status Scaffold::alloc_bytes(void** out, uint64_t bytes, bool zero, bool kept) {
+  bytes = bytes ? bytes : 4;
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes) != hipSuccess)
+    return isl::fail(ISL_ERR_DEVICE, "hipMalloc of %llu bytes failed for the builder", (unsigned long long)bytes);
+  (kept ? keep : tmp).push_back(q);
+  if (zero && hipMemset(q, 0, bytes) != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "hipMemset failed");
+  *out = q;
+  return ISL_OK;
+}
+
+isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw_, const float* vectors,
+                          uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef) {
+  ISL_TRY(isl_index_new(&cfg, &g));
+  g->cfg.prune_ratio = 0.0f;  // construction searches do not prune (leann.rs:692-749)
+  g->is_hnsw = hnsw_;         // HnswGraph heap order: distance alone
+  g->host_csr_valid = false;
+  g->num_nodes = n;
+  g->device = device;
+  g->has_dimension = true;
+  g->dimension = d;
+  g->max_degree = m0;  // the widest row a construction search can meet: a row is back at <= m0 ids before the next search
+  ISL_TRY(isl_set_embeddings(g, vectors, n, d, ISL_DTYPE_F32, mem));
+  hnsw = hnsw_;
+  diverse = opts.select_rule == ISL_SELECT_DIVERSE;
+  ISL_TRY(alloc(&p.lock, n, true));
+  ISL_TRY(alloc(&qbuf, B * d));
+  ISL_TRY(alloc(&cand_ids, B * ef));
+  ISL_TRY(alloc(&cand_dist, B * ef));
+  ISL_TRY(alloc(&cand_cnt, B));
+  ISL_TRY(alloc(&p.sel, B * m0));
+  ISL_TRY(alloc(&p.sel_cnt, B));
+  p.emb = g->d_emb; p.norm2 = g->d_norm2; p.stride = g->emb_stride; p.d = (uint32_t)d;
+  p.ef = ef;
+  p.cand_ids = cand_ids; p.cand_dist = cand_dist; p.cand_cnt = cand_cnt;
+  if (!hnsw) { p.hub_percentile = cfg.hub_percentile; p.high_degree = cfg.high_degree_pruning; }
+  p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
+  return ISL_OK;
+}
+
+isl_status Scaffold::insert(const Table& t, uint32_t cnt, bool locking, uint64_t id0, const uint32_t* node_ids,
+                            uint32_t layer) {
+  const uint64_t d = p.d;
+  g->d_ell = t.ell;
+  g->d_ell_deg = t.deg;
+  g->ell_w = t.M + 1;
+  ISL_TRY(isl::search_device_sync(g, qbuf, cnt, d, p.ef, p.ef, cand_ids, cand_dist, cand_cnt, nullptr));
+  p.ell = t.ell; p.ell_deg = t.deg; p.W = t.M + 1; p.m0 = t.M;
+  p.id0 = id0; p.node_ids = node_ids; p.layer = layer;
+  p.B = cnt;
+  p.locking = locking;
+  const uint32_t metric = g->cfg.metric;
+  if (diverse) {
+    launch_select_diverse(metric, cnt, sel_lds(d, p.ef, t.M), p);
+    launch_link(metric, true, hnsw, cnt, sel_lds(d, t.M + 1, t.M), p);
+  } else {
+    // the reference rule's selection does not measure: take(M), or the hub rule of LeannIndex::build
+    hipLaunchKernelGGL(select_kernel, dim3(cnt), dim3(64), (size_t)p.ef * 12, 0, p);
+    launch_link(metric, false, hnsw, cnt, link_lds(d), p);
+  }
+  if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "builder launch failed");
+  return ISL_OK;
+}
+
+isl_status Scaffold::table_to_csr(const Table& t, uint64_t n, bool kept, uint64_t** off, uint32_t** adj) {
+  std::vector<uint32_t> hdeg(n);
+  if (hipMemcpy(hdeg.data(), t.deg, n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return isl::fail(ISL_ERR_DEVICE, "cannot read the degrees back");
+  std::vector<uint64_t> hoff(n + 1, 0);
+  for (uint64_t i = 0; i < n; ++i) hoff[i + 1] = hoff[i] + hdeg[i];
+  ISL_TRY(alloc(off, n + 1, false, kept));
+  ISL_TRY(alloc(adj, hoff[n], false, kept));
+  if (hipMemcpy(*off, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
+    return isl::fail(ISL_ERR_DEVICE, "cannot upload the CSR offsets");
+  hipLaunchKernelGGL(ell_to_csr_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, 0, t.ell, t.deg, t.M + 1, *off, n,
+                     *adj);
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return isl::fail(ISL_ERR_DEVICE, "CSR compaction failed");
+  return ISL_OK;
+}
+
+void Scaffold::hand_rows_to(isl_index* r) {
+  r->d_emb = g->d_emb; r->d_norm2 = g->d_norm2;
+  r->nvec = g->nvec; r->emb_d = g->emb_d; r->emb_stride = g->emb_stride;
+  g->d_emb = nullptr; g->d_norm2 = nullptr;
+}
+
+isl_index* Scaffold::release() {
+  isl_index* r = res;
+  r->hnsw_owned.insert(r->hnsw_owned.end(), keep.begin(), keep.end());
+  keep.clear();
+  res = nullptr;
+  return r;
+}
+
+}  // namespace isl_build
+
+using isl_build::Scaffold;
+using isl_build::Table;
 
 extern "C" void isl_build_options_default(isl_build_options* o) {
   if (!o) return;
@@ -504,71 +576,32 @@ extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg_in, const i
   isl_build_options opts;
   isl_build_options_default(&opts);
   if (opts_in) {
-    ISL_TRY(check_build_options(opts_in, true));
+    ISL_TRY(isl_build::check_build_options(opts_in, true));
     opts = *opts_in;
   }
-  const bool diverse = opts.select_rule == ISL_SELECT_DIVERSE;
-  uint64_t batch = opts.batch;
   isl_leann_config cfg;
   if (cfg_in) cfg = *cfg_in;
   else isl_leann_config_paper_default(&cfg);
   ISL_TRY(isl_leann_config_validate(&cfg));
   if (n == 0) return isl_index_new(&cfg, out);  // build(&[]) -> Ok(()), leann.rs:565-567
   if (d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
-  if (cfg.m0 > 128) return fail(ISL_ERR_UNSUPPORTED, "the device builder keeps rows of up to 129 ids: m0 <= 128");
-  if (cfg.ef_construction > 512) return fail(ISL_ERR_UNSUPPORTED, "ef_construction <= 512 on the device");
-  if (n >= 0x7FFFFFF0ull) return fail(ISL_ERR_UNSUPPORTED, "num_nodes exceeds the device id range");
-  if (batch == 0) batch = 1;
+  if (const char* why = isl_plan::shape_limit(cfg.m0, cfg.ef_construction, n)) return fail(ISL_ERR_UNSUPPORTED, "%s", why);
   ISL_TRY(isl::use_device(device));
-  const uint32_t W = (uint32_t)cfg.m0 + 1, m0 = (uint32_t)cfg.m0, ef = (uint32_t)cfg.ef_construction;
-  const uint64_t B = std::min<uint64_t>(batch, n);
+  // `levels` only name the entry point here (they are an input because random_level draws from thread_rng):
+  // the steps are the planner's for all-zero levels, nodes in id order
+  std::vector<isl_plan::Step> steps;
+  {
+    std::vector<uint32_t> order;
+    isl_plan::plan_steps(std::vector<uint32_t>(n, 0u), opts.batch ? opts.batch : 1, steps, order);
+  }
+  const uint32_t m0 = (uint32_t)cfg.m0, ef = (uint32_t)cfg.ef_construction;
 
-  // the graph under construction: an index whose adjacency is the fixed-width table
-  isl_index* g = nullptr;
-  ISL_TRY(isl_index_new(&cfg, &g));
-  auto bail = [&](isl_status st) { isl_index_free(g); return st; };
-  g->cfg.prune_ratio = 0.0f;  // construction searches do not prune (leann.rs:692-749)
-  g->host_csr_valid = false;
-  g->num_nodes = n;
-  g->device = device;
-  g->has_dimension = true;
-  g->dimension = d;
-  g->max_degree = m0;  // what a construction search can meet: a row is back at <= m0 ids before the next search
-  isl_status st = isl_set_embeddings(g, vectors, n, d, ISL_DTYPE_F32, mem);
-  if (st != ISL_OK) return bail(st);
-  std::vector<void*> tmp;
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-    tmp.push_back(p);
-    return p;
-  };
-  auto cleanup = [&]() { for (void* p : tmp) (void)hipFree(p); };
-  auto bail2 = [&](isl_status s) { cleanup(); g->d_ell = nullptr; g->d_ell_deg = nullptr; return bail(s); };
-  uint32_t* ell = (uint32_t*)dalloc(n * W * 4);
-  uint32_t* ell_deg = (uint32_t*)dalloc(n * 4);
-  uint32_t* lock = (uint32_t*)dalloc(n * 4);
-  float* qbuf = (float*)dalloc(B * d * 4);
-  uint64_t* cand_ids = (uint64_t*)dalloc(B * ef * 8);
-  float* cand_dist = (float*)dalloc(B * ef * 4);
-  uint32_t* cand_cnt = (uint32_t*)dalloc(B * 4);
-  uint32_t* sel = (uint32_t*)dalloc(B * m0 * 4);
-  uint32_t* sel_cnt = (uint32_t*)dalloc(B * 4);
-  if (!ell || !ell_deg || !lock || !qbuf || !cand_ids || !cand_dist || !cand_cnt || !sel || !sel_cnt)
-    return bail2(fail(ISL_ERR_DEVICE, "hipMalloc failed for the builder"));
-  if (hipMemset(ell_deg, 0, n * 4) != hipSuccess || hipMemset(lock, 0, n * 4) != hipSuccess)
-    return bail2(fail(ISL_ERR_DEVICE, "hipMemset failed"));
-  g->d_ell = ell;
-  g->d_ell_deg = ell_deg;
-  g->ell_w = W;
-
-  BuildParams p{};
-  p.emb = g->d_emb; p.norm2 = g->d_norm2; p.stride = g->emb_stride; p.d = (uint32_t)d;
-  p.ell = ell; p.ell_deg = ell_deg; p.lock = lock; p.W = W; p.m0 = m0; p.ef = ef;
-  p.cand_ids = cand_ids; p.cand_dist = cand_dist; p.cand_cnt = cand_cnt; p.sel = sel; p.sel_cnt = sel_cnt;
-  p.hub_percentile = cfg.hub_percentile; p.high_degree = cfg.high_degree_pruning;
-  p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
-  const size_t link_lds = (size_t)TILE_ROWS * TILE_LD * 4 + (size_t)((d + 3) / 4 * 4) * 4 + 64;
+  Scaffold c;
+  ISL_TRY(c.open(cfg, opts, false, vectors, n, d, mem, device, isl_plan::largest_step(steps), m0, ef));
+  Table t{nullptr, nullptr, m0};
+  ISL_TRY(c.alloc(&t.ell, n * (m0 + 1)));
+  ISL_TRY(c.alloc(&t.deg, n, true));
+  isl_index* g = c.g;
 
   bool has_entry = false;
   uint64_t entry = 0, max_level = 0;
@@ -578,59 +611,26 @@ extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg_in, const i
   };
   // node 0: no neighbours (adjacency is empty, :585), becomes the entry point
   note_level(0);
-  for (uint64_t id0 = 1; id0 < n;) {
-    // a step never inserts more than an eighth of the nodes already in the graph: the nodes of
-    // a step cannot see each other, and a young graph would otherwise end up as a star
-    const uint64_t nb = std::min<uint64_t>(std::min<uint64_t>(B, n - id0), std::max<uint64_t>(1, id0 / 8));
+  for (const isl_plan::Step& s : steps) {
     g->has_entry = true;
     g->entry_point = entry;  // :669: entry_point.unwrap_or(0) as of the start of the step
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((uint32_t)((nb * d + 255) / 256)), dim3(256), 0, 0,
-                       g->d_emb, g->emb_stride, (uint32_t)d, id0, (uint32_t)nb, qbuf);
-    if (hipGetLastError() != hipSuccess) return bail2(fail(ISL_ERR_DEVICE, "gather launch failed"));
-    st = isl::search_device_sync(g, qbuf, nb, d, ef, ef, cand_ids, cand_dist, cand_cnt, nullptr);
-    if (st != ISL_OK) return bail2(st);
-    p.id0 = id0;
-    p.B = (uint32_t)nb;
-    p.locking = nb > 1;
-    if (diverse) {
-      launch_select_diverse((int)cfg.metric, (uint32_t)nb, sel_lds(d, ef, m0), p);
-      launch_link_diverse((int)cfg.metric, (uint32_t)nb, sel_lds(d, W, m0), p);
-    } else {
-      hipLaunchKernelGGL(select_kernel, dim3((uint32_t)nb), dim3(64), (size_t)ef * 12, 0, p);
-      launch_link((int)cfg.metric, (uint32_t)nb, link_lds, p);
-    }
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-      return bail2(fail(ISL_ERR_DEVICE, "builder kernels failed"));
-    for (uint64_t i = 0; i < nb; ++i) note_level(id0 + i);
-    id0 += nb;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((uint32_t)((s.count * d + 255) / 256)), dim3(256), 0, 0,
+                       g->d_emb, g->emb_stride, (uint32_t)d, s.first, s.count, c.qbuf);
+    if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "gather launch failed");
+    ISL_TRY(c.insert(t, s.count, s.count > 1, s.first));
+    if (hipDeviceSynchronize() != hipSuccess) return fail(ISL_ERR_DEVICE, "builder kernels failed");
+    for (uint64_t i = 0; i < s.count; ++i) note_level(s.first + i);
   }
 
   // flatten, :617-627
-  std::vector<uint32_t> hdeg(n);
-  if (hipMemcpy(hdeg.data(), ell_deg, n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return bail2(fail(ISL_ERR_DEVICE, "cannot read the degrees back"));
-  std::vector<uint64_t> off(n + 1, 0);
-  for (uint64_t i = 0; i < n; ++i) off[i + 1] = off[i] + hdeg[i];
-  uint64_t* d_off = (uint64_t*)dalloc((n + 1) * 8);
-  uint32_t* d_adj = (uint32_t*)dalloc((off[n] ? off[n] : 1) * 4);
-  if (!d_off || !d_adj || hipMemcpy(d_off, off.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
-    return bail2(fail(ISL_ERR_DEVICE, "hipMalloc failed for the CSR"));
-  hipLaunchKernelGGL(ell_to_csr_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, 0, ell, ell_deg, W, d_off, n, d_adj);
-  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return bail2(fail(ISL_ERR_DEVICE, "CSR compaction failed"));
-  isl_index* res = nullptr;
-  st = isl_index_from_device_csr(&cfg, device, n, d_off, d_adj, 1, entry, 1, d, &res);
-  if (st != ISL_OK) return bail2(st);
-  res->max_level = max_level;
-  if (levels) res->levels.assign(levels, levels + n);
-  // the finished index takes over the rows (and their norms) of the construction graph
-  res->d_emb = g->d_emb; res->d_norm2 = g->d_norm2;
-  res->nvec = g->nvec; res->emb_d = g->emb_d; res->emb_stride = g->emb_stride;
-  g->d_emb = nullptr; g->d_norm2 = nullptr;
-  g->d_ell = nullptr; g->d_ell_deg = nullptr;
-  cleanup();
-  isl_index_free(g);
-  *out = res;
+  uint64_t* d_off = nullptr;
+  uint32_t* d_adj = nullptr;
+  ISL_TRY(c.table_to_csr(t, n, false, &d_off, &d_adj));
+  ISL_TRY(isl_index_from_device_csr(&cfg, device, n, d_off, d_adj, 1, entry, 1, d, &c.res));
+  c.res->max_level = max_level;
+  if (levels) c.res->levels.assign(levels, levels + n);
+  c.hand_rows_to(c.res);
+  *out = c.release();
   return ISL_OK;
 }
 
@@ -644,17 +644,17 @@ extern "C" isl_status isl_select_neighbors(const isl_index* idx, const isl_build
   isl_build_options opts;
   isl_build_options_default(&opts);
   if (opts_in) {
-    ISL_TRY(check_build_options(opts_in, false));
+    ISL_TRY(isl_build::check_build_options(opts_in, false));
     opts = *opts_in;
   }
-  if (cap == 0 || cap > 128) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: 1 <= cap <= 128");
+  if (cap == 0 || cap > isl_plan::kMaxM0) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: 1 <= cap <= 128");
   if (nb == 0) return ISL_OK;
   if (nb > 0x7FFFFFFFull) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: too many base nodes");
   if (idx->recompute || idx->d_emb16 || !idx->d_emb || idx->device < 0)
     return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors needs float32 rows resident on the device");
   uint32_t nmax = 1;
   for (uint64_t i = 0; i < nb; ++i) {
-    if (cand_cnt[i] > 512 || cand_cnt[i] > pitch)
+    if (cand_cnt[i] > isl_plan::kMaxEfConstruction || cand_cnt[i] > pitch)
       return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: cand_cnt <= min(pitch, 512)");
     nmax = std::max(nmax, cand_cnt[i]);
   }
@@ -670,38 +670,31 @@ extern "C" isl_status isl_select_neighbors(const isl_index* idx, const isl_build
     }
   }
   ISL_TRY(isl::use_device(idx->device));
-  std::vector<void*> tmp;
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-    tmp.push_back(p);
-    return p;
-  };
-  auto done = [&](isl_status s) { for (void* p : tmp) (void)hipFree(p); return s; };
-  uint32_t* d_base = (uint32_t*)dalloc(nb * 4);
-  uint32_t* d_cand = (uint32_t*)dalloc((size_t)nb * nmax * 4);
-  uint32_t* d_cnt = (uint32_t*)dalloc(nb * 4);
-  uint32_t* d_out = (uint32_t*)dalloc((size_t)nb * cap * 4);
-  uint32_t* d_ocnt = (uint32_t*)dalloc(nb * 4);
-  if (!d_base || !d_cand || !d_cnt || !d_out || !d_ocnt)
-    return done(fail(ISL_ERR_DEVICE, "hipMalloc failed for isl_select_neighbors"));
+  Scaffold c;  // the staging buffers alone: no construction graph
+  SelectNeighborsParams p{};
+  uint32_t *d_base = nullptr, *d_cand = nullptr, *d_cnt = nullptr;
+  ISL_TRY(c.alloc(&d_base, nb));
+  ISL_TRY(c.alloc(&d_cand, nb * nmax));
+  ISL_TRY(c.alloc(&d_cnt, nb));
+  ISL_TRY(c.alloc(&p.out, nb * cap, true));
+  ISL_TRY(c.alloc(&p.out_cnt, nb));
   if (hipMemcpy(d_base, hbase.data(), nb * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d_cand, hcand.data(), (size_t)nb * nmax * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_cnt, cand_cnt, nb * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(d_out, 0, (size_t)nb * cap * 4) != hipSuccess)
-    return done(fail(ISL_ERR_DEVICE, "cannot stage the candidates"));
-  SelectNeighborsParams p{};
+      hipMemcpy(d_cnt, cand_cnt, nb * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "cannot stage the candidates");
   p.c = SelCtx{idx->d_emb, idx->d_norm2, idx->emb_stride, (uint32_t)idx->emb_d, opts.alpha, opts.keep_pruned ? 1u : 0u};
   p.base_ids = d_base; p.cand = d_cand; p.cand_cnt = d_cnt;
   p.pitch = nmax; p.cap = (uint32_t)cap; p.nmax = nmax;
-  p.out = d_out; p.out_cnt = d_ocnt;
-  launch_select_neighbors((int)idx->cfg.metric, (uint32_t)nb, sel_lds(idx->emb_d, nmax, (uint32_t)cap), p);
+  isl_build::by_metric(idx->cfg.metric, [&](auto mc) {
+    hipLaunchKernelGGL(select_neighbors_kernel<decltype(mc)::value>, dim3((uint32_t)nb), dim3(64),
+                       sel_lds(idx->emb_d, nmax, (uint32_t)cap), 0, p);
+  });
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return done(fail(ISL_ERR_DEVICE, "select_neighbors kernel failed"));
+    return fail(ISL_ERR_DEVICE, "select_neighbors kernel failed");
   std::vector<uint32_t> hout((size_t)nb * cap);
-  if (hipMemcpy(hout.data(), d_out, (size_t)nb * cap * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(out_cnt, d_ocnt, nb * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return done(fail(ISL_ERR_DEVICE, "cannot read the selection back"));
+  if (hipMemcpy(hout.data(), p.out, (size_t)nb * cap * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(out_cnt, p.out_cnt, nb * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "cannot read the selection back");
   for (size_t i = 0; i < hout.size(); ++i) out_ids[i] = hout[i];
-  return done(ISL_OK);
+  return ISL_OK;
 }

@@ -1,8 +1,12 @@
-// What the two graph builders share (build.hip: LeannIndex::build and the kernels; hnsw_build.hip:
-// HnswGraph::insert over per-layer tables).  Internal, not part of the ABI.
+// What the two graph builders share (build.hip: LeannIndex::build, the kernels and the scaffold below;
+// hnsw_build.hip: HnswGraph::insert over per-layer tables; build_plan.hpp: their host-only arithmetic).
+// Internal, not part of the ABI.
 #pragma once
 
+#include "build_plan.hpp"
 #include "common.hpp"
+
+#include <type_traits>
 
 namespace isl_build {
 
@@ -37,18 +41,71 @@ struct BuildParams {
 
 // struct_size, rule and alpha of caller-supplied options, before any device call
 isl_status check_build_options(const isl_build_options* o, bool need_rule);
-// bytes of LDS of the selection kernels (tile, query, lists of up to nmax candidates, a row of M) and of
-// the reference-rule link kernel
-size_t select_lds(uint64_t d, uint32_t nmax, uint32_t M);
+// bytes of LDS of the reference-rule link kernel and of the insertion descent (tile + query)
 size_t link_lds(uint64_t d);
 
-// take(m0) of the search result (select_kernel without the hub rule: p.high_degree == 0)
-void select_truncate(uint32_t grid, const BuildParams& p);
-void select_diverse(int metric, uint32_t grid, size_t lds, const BuildParams& p);
-// link_kernel in its HnswGraph mode (insert_node, hnsw.rs:295-318)
-void link_hnsw(int metric, bool diverse, uint32_t grid, size_t lds, const BuildParams& p);
-// fixed-width table -> CSR neighbours (one wave per row)
-void ell_to_csr(const uint32_t* ell, const uint32_t* deg, uint32_t W, const uint64_t* off, uint64_t n,
-                       uint32_t* adj);
+// f(std::integral_constant<int, METRIC>{}) for the metric of a call: the one place a kernel template's
+// metric argument is chosen at run time
+template <class F>
+void by_metric(uint32_t metric, F&& f) {
+  switch (metric) {
+    case ISL_METRIC_COSINE: f(std::integral_constant<int, ISL_METRIC_COSINE>{}); break;
+    case ISL_METRIC_EUCLIDEAN: f(std::integral_constant<int, ISL_METRIC_EUCLIDEAN>{}); break;
+    case ISL_METRIC_DOT: f(std::integral_constant<int, ISL_METRIC_DOT>{}); break;
+    default: f(std::integral_constant<int, ISL_METRIC_MANHATTAN>{}); break;
+  }
+}
+
+// One table the nodes of a step are inserted on: the whole graph of LeannIndex::build, or one layer of an
+// HnswGraph under construction.
+struct Table {
+  uint32_t* ell;   // [n][M + 1]
+  uint32_t* deg;   // [n]
+  uint32_t M;      // ids a row keeps
+};
+
+// A construction in progress.  It owns the construction graph `g` (an isl_index whose adjacency is the table
+// being searched), every temporary device allocation, the per-step buffers and, until release(), what the
+// finished graph will keep.  Leaving the scope is the one failure path: everything is freed and the error
+// record of the first failure survives the frees.
+struct Scaffold {
+  isl_index* g = nullptr;
+  isl_index* res = nullptr;   // the finished index, once there is one
+  std::vector<void*> tmp;     // freed on every way out
+  std::vector<void*> keep;    // res->hnsw_owned after release(), freed before it
+  float* qbuf = nullptr;      // [B][d] queries of a step: the rows of its nodes
+  uint64_t* cand_ids = nullptr;  // [B][ef] what the construction search found (p.cand_*)
+  float* cand_dist = nullptr;
+  uint32_t* cand_cnt = nullptr;
+  BuildParams p{};            // rows, per-step buffers and rule parameters; insert() fills in the table
+  bool diverse = false, hnsw = false;
+
+  Scaffold() = default;
+  Scaffold(const Scaffold&) = delete;
+  Scaffold& operator=(const Scaffold&) = delete;
+  ~Scaffold();
+
+  // `count` elements on the device (at least one), owned by tmp or keep
+  template <class T>
+  isl_status alloc(T** out, uint64_t count, bool zero = false, bool kept = false) {
+    return alloc_bytes((void**)out, count * sizeof(T), zero, kept);
+  }
+  isl_status alloc_bytes(void** out, uint64_t bytes, bool zero, bool kept);
+  // The construction graph over `vectors` and the buffers of steps of up to B nodes, rows of up to m0 ids.
+  // cfg: metric (and, for LeannIndex::build, the hub rule); opts: the selection rule.
+  isl_status open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw, const float* vectors,
+                  uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef);
+  // Inserts `cnt` nodes on table `t`, their rows being in qbuf: construction search over the table, selection
+  // (truncation / hub rule, or select()), links both ways.  The nodes are id0 .. id0 + cnt - 1, or node_ids[]
+  // on `layer` of an HnswGraph.  Returns once the kernels are launched.
+  isl_status insert(const Table& t, uint32_t cnt, bool locking, uint64_t id0, const uint32_t* node_ids = nullptr,
+                    uint32_t layer = 0);
+  // fixed-width table -> CSR arrays on the device (one wave per row)
+  isl_status table_to_csr(const Table& t, uint64_t n, bool kept, uint64_t** off, uint32_t** adj);
+  // the finished index takes over the rows (and their norms) of the construction graph
+  void hand_rows_to(isl_index* r);
+  // success: the finished graph leaves with what was kept for it
+  isl_index* release();
+};
 
 }  // namespace isl_build

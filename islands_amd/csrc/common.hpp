@@ -310,4 +310,10 @@ bool any_lane_busy(const isl_index* idx);
 void join_lane_workers(const isl_index* idx);
 // Builds the padded adjacency (64 ids per node + degrees) the traversal reads; under idx->mu.
 isl_status ensure_padded_adjacency(isl_index* idx);
+// hnsw.hip -- HnswConfig::validate (hnsw.rs:72-85) and the metric's range
+isl_status hnsw_config_validate(uint64_t m, uint64_t m0, uint64_t ef_construction, int64_t metric);
+// hnsw.hip -- the upper layers of a finished graph, device CSR arrays per layer (entry 0 unused: layer 0 is the
+// core index): uploads the two pointer tables the descent reads and records them in `h`
+isl_status attach_upper_layers(isl_hnsw* h, const std::vector<const uint64_t*>& offs,
+                               const std::vector<const uint32_t*>& adjs);
 }  // namespace isl

@@ -1,7 +1,9 @@
-// HnswGraph search facade (src/core/hnsw.rs:149-515, search side) on gfx950.
+// HnswGraph facade (src/core/hnsw.rs:149-515) on gfx950: everything about a finished graph -- handing one
+// over (from_layers, from_bytes), searching it, reading it back (info, levels, neighbours, rows, to_bytes).
 // The graph is handed over layer by layer in CSR form; layer 0 and the node vectors live in an
 // internal LeannIndex-like handle (so the same exact kernel, visited bitmap and row staging are
-// used), the upper layers are kept as device CSR arrays for the greedy descent.
+// used), the upper layers are kept as device CSR arrays for the greedy descent.  isl_hnsw_build
+// (hnsw_build.hip) constructs one on the device and installs its layers through attach_upper_layers.
 #include "common.hpp"
 
 #include <algorithm>
@@ -21,7 +23,73 @@ __global__ void hnsw_convert_adj(const uint64_t* __restrict__ in, uint32_t* __re
   }
 }
 
+// every layer of `h` in CSR form on the host (under h->host_mu)
+isl_status ensure_host_layers(const isl_hnsw* h) {
+  if (h->host_valid) return ISL_OK;
+  const isl_index* c = h->core;
+  const uint64_t n = c->num_nodes;
+  std::vector<std::vector<uint64_t>> off, adj;
+  if (n) {
+    ISL_TRY(isl::materialise_host_csr(c));
+    const uint64_t layers = std::max<uint64_t>(c->hnsw_layers, 1);
+    off.resize(layers);
+    adj.resize(layers);
+    off[0] = c->node_offsets;
+    adj[0] = c->neighbors;
+    if (layers > 1) ISL_TRY(isl::use_device(c->device));
+    std::vector<uint32_t> tmp;
+    for (uint64_t L = 1; L < layers; ++L) {
+      off[L].assign(n + 1, 0);
+      ISL_HIP(hipMemcpy(off[L].data(), h->layer_off[L], (n + 1) * 8, hipMemcpyDeviceToHost));
+      const uint64_t nnz = off[L][n];
+      tmp.resize(nnz);
+      if (nnz) ISL_HIP(hipMemcpy(tmp.data(), h->layer_adj[L], nnz * 4, hipMemcpyDeviceToHost));
+      adj[L].assign(tmp.begin(), tmp.end());
+    }
+  }
+  h->h_off.swap(off);
+  h->h_adj.swap(adj);
+  h->host_valid = true;
+  return ISL_OK;
+}
+
+// HnswNode::level: what the caller supplied, or 0 for all where a handle came without levels
+uint64_t level_of(const isl_index* c, uint64_t i) { return i < c->levels.size() ? c->levels[i] : 0; }
+
+// node rows [i0, i0 + cnt) of the handle's f32 provider -> host
+isl_status read_rows(const isl_index* c, uint64_t i0, uint64_t cnt, float* out) {
+  if (!cnt || !c->emb_d) return ISL_OK;
+  if (!c->d_emb) return isl::fail(ISL_ERR_EMBEDDING, "Embedding error: no embedding provider attached");
+  ISL_TRY(isl::use_device(c->device));
+  ISL_HIP(hipMemcpy2D(out, c->emb_d * 4, c->d_emb + i0 * c->emb_stride, c->emb_stride * 4, c->emb_d * 4, cnt,
+                      hipMemcpyDeviceToHost));
+  return ISL_OK;
+}
+
 }  // namespace
+
+isl_status isl::hnsw_config_validate(uint64_t m, uint64_t m0, uint64_t ef_construction, int64_t metric) {
+  // HnswConfig::validate, hnsw.rs:72-85
+  if (m == 0) return fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: M must be > 0");
+  if (m0 < m) return fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: M0 must be >= M");
+  if (ef_construction < m) return fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: ef_construction must be >= M");
+  if (metric < 0 || metric > ISL_METRIC_MANHATTAN) return fail(ISL_ERR_INVALID_ARGUMENT, "unknown metric");
+  return ISL_OK;
+}
+
+isl_status isl::attach_upper_layers(isl_hnsw* h, const std::vector<const uint64_t*>& offs,
+                                    const std::vector<const uint32_t*>& adjs) {
+  isl_index* c = h->core;
+  const size_t bytes = offs.size() * sizeof(void*);
+  if (hipMalloc((void**)&c->d_layer_off, bytes) != hipSuccess || hipMalloc((void**)&c->d_layer_adj, bytes) != hipSuccess ||
+      hipMemcpy((void*)c->d_layer_off, offs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy((void*)c->d_layer_adj, adjs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "layer table upload failed");
+  c->hnsw_layers = offs.size();
+  h->layer_off = offs;
+  h->layer_adj = adjs;
+  return ISL_OK;
+}
 
 extern "C" {
 
@@ -45,13 +113,7 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
                                 int32_t has_entry, uint64_t entry_point, uint64_t max_level,
                                 const float* vectors, int32_t device, isl_hnsw** out) {
   if (!out) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "out is NULL");
-  // HnswConfig::validate, hnsw.rs:72-85
-  if (m == 0) return isl::fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: M must be > 0");
-  if (m0 < m) return isl::fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: M0 must be >= M");
-  if (ef_construction < m)
-    return isl::fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: ef_construction must be >= M");
-  if (metric < 0 || metric > ISL_METRIC_MANHATTAN)
-    return isl::fail(ISL_ERR_INVALID_ARGUMENT, "unknown metric");
+  ISL_TRY(isl::hnsw_config_validate(m, m0, ef_construction, metric));
   if (num_nodes && (num_layers == 0 || max_level >= num_layers || !layer_offsets || !layer_neighbors))
     return isl::fail(ISL_ERR_INVALID_ARGUMENT, "layers do not cover max_level");
   isl_hnsw* h = new isl_hnsw();
@@ -107,14 +169,8 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
   uint32_t flag = 0;
   (void)hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost);
   if (flag) return bail(isl::fail(ISL_ERR_UNSUPPORTED, "node ids above the device id range"));
-  if (hipMalloc((void**)&c->d_layer_off, (max_level + 1) * sizeof(void*)) != hipSuccess ||
-      hipMalloc((void**)&c->d_layer_adj, (max_level + 1) * sizeof(void*)) != hipSuccess ||
-      hipMemcpy((void*)c->d_layer_off, offs.data(), (max_level + 1) * sizeof(void*), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((void*)c->d_layer_adj, adjs.data(), (max_level + 1) * sizeof(void*), hipMemcpyHostToDevice) != hipSuccess)
-    return bail(isl::fail(ISL_ERR_DEVICE, "layer table upload failed"));
-  c->hnsw_layers = max_level + 1;
-  h->layer_off = offs;
-  h->layer_adj = adjs;
+  st = isl::attach_upper_layers(h, offs, adjs);
+  if (st != ISL_OK) return bail(st);
   *out = h;
   return ISL_OK;
 }
@@ -194,6 +250,8 @@ static isl_status hnsw_from_bytes_impl(const uint8_t* bytes, size_t len, int32_t
       pos += c * 8;
     }
     levels[id] = u64();
+    // (to_bytes writes level + 1 lists per node; the layer count below bounds every list that exists)
+    if (ok && levels[id] >= 64) return bad("implausible node level");
   }
   const uint8_t has_entry = u8();
   const uint64_t entry = has_entry ? u64() : 0;
@@ -224,6 +282,93 @@ static isl_status hnsw_from_bytes_impl(const uint8_t* bytes, size_t len, int32_t
   memcpy(&(*out)->ml, &ml_bits, 8);
   (*out)->max_layers = max_layers;
   return ISL_OK;
+}
+
+// ---- reading a graph back: HnswGraph::to_bytes (hnsw.rs:506-509) and the accessors
+isl_status isl_hnsw_info(const isl_hnsw* h, int32_t* has_entry, uint64_t* entry, uint64_t* max_level, uint64_t* dim) {
+  if (!h || !h->core) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "hnsw handle is NULL");
+  if (has_entry) *has_entry = h->core->has_entry ? 1 : 0;
+  if (entry) *entry = h->core->has_entry ? h->core->entry_point : 0;
+  if (max_level) *max_level = h->core->max_level;
+  if (dim) *dim = h->dim;
+  return ISL_OK;
+}
+
+isl_status isl_hnsw_levels(const isl_hnsw* h, uint64_t* out) {
+  if (!h || !h->core) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "hnsw handle is NULL");
+  const uint64_t n = h->core->num_nodes;
+  if (n && !out) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  for (uint64_t i = 0; i < n; ++i) out[i] = level_of(h->core, i);
+  return ISL_OK;
+}
+
+isl_status isl_hnsw_get_neighbors(const isl_hnsw* h, uint64_t node, uint64_t layer, uint64_t* out, uint64_t cap,
+                                  uint64_t* count, int32_t* has_layer) {
+  if (!h || !h->core || !count || (cap && !out)) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (node >= h->core->num_nodes) return isl::fail_node(node);
+  std::lock_guard<std::mutex> lock(h->host_mu);
+  ISL_TRY(ensure_host_layers(h));
+  *count = 0;
+  if (has_layer) *has_layer = layer <= level_of(h->core, node) ? 1 : 0;
+  if (layer > level_of(h->core, node) || layer >= h->h_off.size()) return ISL_OK;
+  const uint64_t s = h->h_off[layer][node], e = h->h_off[layer][node + 1];
+  *count = e - s;
+  for (uint64_t i = 0; i < e - s && i < cap; ++i) out[i] = h->h_adj[layer][s + i];
+  return ISL_OK;
+}
+
+isl_status isl_hnsw_get_vector(const isl_hnsw* h, uint64_t node, float* out) {
+  if (!h || !h->core || !out) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  if (node >= h->core->num_nodes) return isl::fail_node(node);
+  return read_rows(h->core, node, 1, out);
+}
+
+isl_status isl_hnsw_to_bytes(const isl_hnsw* h, uint8_t** out, size_t* len) {
+  if (!h || !h->core || !out || !len) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  const isl_index* c = h->core;
+  const uint64_t n = c->num_nodes, d = n ? c->emb_d : 0;
+  try {
+    std::lock_guard<std::mutex> lock(h->host_mu);
+    ISL_TRY(ensure_host_layers(h));
+    std::vector<float> rows((size_t)n * d);
+    ISL_TRY(read_rows(c, 0, n, rows.data()));
+    std::vector<uint8_t> b;
+    auto raw = [&](const void* q, size_t bytes) { const uint8_t* s = (const uint8_t*)q; b.insert(b.end(), s, s + bytes); };
+    auto u64 = [&](uint64_t v) { raw(&v, 8); };
+    // the layout hnsw_from_bytes_impl reads (above it)
+    u64(h->m); u64(h->m0); u64(h->ef_construction);
+    raw(&h->ml, 8);
+    const uint32_t metric = c->cfg.metric;
+    raw(&metric, 4);
+    u64(h->max_layers);
+    u64(n);
+    for (uint64_t i = 0; i < n; ++i) {
+      u64(i); u64(i); u64(d);
+      raw(rows.data() + (size_t)i * d, d * 4);
+      const uint64_t lvl = level_of(c, i);
+      u64(lvl + 1);
+      for (uint64_t L = 0; L <= lvl; ++L) {
+        if (L >= h->h_off.size()) { u64(0); continue; }
+        const uint64_t s = h->h_off[L][i], e = h->h_off[L][i + 1];
+        u64(e - s);
+        raw(h->h_adj[L].data() + s, (e - s) * 8);
+      }
+      u64(lvl);
+    }
+    const uint8_t one = 1, zero = 0;
+    if (c->has_entry) { raw(&one, 1); u64(c->entry_point); } else raw(&zero, 1);
+    u64(c->max_level);
+    if (c->has_dimension) { raw(&one, 1); u64(c->dimension); } else raw(&zero, 1);
+    u64(n);  // next_id
+    uint8_t* buf = (uint8_t*)malloc(b.size() ? b.size() : 1);
+    if (!buf) return isl::fail(ISL_ERR_SERIALIZATION, "Serialization error: out of memory");
+    memcpy(buf, b.data(), b.size());
+    *out = buf;
+    *len = b.size();
+    return ISL_OK;
+  } catch (const std::exception& e) {
+    return isl::fail(ISL_ERR_SERIALIZATION, "Serialization error: %s", e.what());
+  }
 }
 
 isl_status isl_hnsw_search_batch(const isl_hnsw* h, const float* queries, uint64_t nq, uint64_t d,

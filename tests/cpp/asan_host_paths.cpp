@@ -1,7 +1,8 @@
 // Host-only paths of libislands_amd.so under AddressSanitizer (CPU build; GPU ASan is not
 // available on this pool): the bincode readers of LeannIndex (leann.rs:1059-1066) and HnswGraph
 // (hnsw.rs:511-514), the chunk framing of storage.rs:113-174, the host CSR accessors and the
-// record-size arithmetic of the shard exchange.  Valid images must round-trip; every truncation,
+// record-size arithmetic of the shard exchange.  Valid images must round-trip (an HnswGraph wherever
+// its reader got as far as a handle: to_bytes, hnsw.hip, is host code of this build); every truncation,
 // a few thousand seeded byte flips and every 8-byte field overwritten with wrapping lengths must
 // come back as a status code -- never as a read or write outside a buffer (ASan aborts on those).
 // Built by `make -C islands_amd/csrc asan` from the same sources as the library (host code
@@ -54,11 +55,28 @@ static std::vector<uint8_t> hnsw_image(size_t n, size_t d, unsigned seed) {
     }
     put64(b, level);
   }
-  b.push_back(1); put64(b, 0);   // entry_point: Some(0)
-  put64(b, 1);                   // max_level
-  b.push_back(1); put64(b, d);   // dimension: Some(d)
+  if (n) {
+    b.push_back(1); put64(b, 0);   // entry_point: Some(0)
+    put64(b, 1);                   // max_level
+    b.push_back(1); put64(b, d);   // dimension: Some(d)
+  } else {                         // HnswGraph::new: None, 0, None -- the image no device is needed for
+    b.push_back(0); put64(b, 0); b.push_back(0);
+  }
   put64(b, n);                   // next_id
   return b;
+}
+
+// whatever isl_hnsw_from_bytes accepted: to_bytes -> from_bytes -> to_bytes gives the same bytes twice
+static void hnsw_round_trip(const isl_hnsw* h) {
+  uint8_t *b1 = nullptr, *b2 = nullptr;
+  size_t l1 = 0, l2 = 0;
+  isl_hnsw* again = nullptr;
+  EXPECT(isl_hnsw_to_bytes(h, &b1, &l1) == ISL_OK && b1);
+  if (b1) EXPECT(isl_hnsw_from_bytes(b1, l1, 0, &again) == ISL_OK && again);
+  if (again) EXPECT(isl_hnsw_to_bytes(again, &b2, &l2) == ISL_OK && b2 && l2 == l1 && !memcmp(b1, b2, l1));
+  if (again) isl_hnsw_free(again);
+  if (b1) isl_free_bytes(b1);
+  if (b2) isl_free_bytes(b2);
 }
 
 static std::vector<uint8_t> leann_image(size_t n, unsigned seed) {
@@ -148,17 +166,22 @@ int main() {
     std::printf("leann n=%zu: %zu mutants parsed, %zu rejected\n", n, ok, bad);
   }
   // ---- HnswGraph bytes: parsed completely before anything touches a device ----
-  for (size_t n : {1u, 5u, 33u}) {
+  // (the empty graph has nothing to upload: its image is read and written back without a card as well)
+  for (size_t n : {0u, 1u, 5u, 33u}) {
     const std::vector<uint8_t> good = hnsw_image(n, 6, (unsigned)n);
     isl_hnsw* h = nullptr;
     const isl_status st0 = isl_hnsw_from_bytes(good.data(), good.size(), 0, &h);
-    EXPECT(st0 == ISL_OK || st0 == ISL_ERR_DEVICE);  // no card here: the upload is what fails
-    if (h) isl_hnsw_free(h);
+    EXPECT(st0 == ISL_OK || (n && st0 == ISL_ERR_DEVICE));  // no card here: the upload is what fails
+    EXPECT((st0 == ISL_OK) == (h != nullptr));
+    if (h) {
+      hnsw_round_trip(h);
+      isl_hnsw_free(h);
+    }
     size_t dev = 0, bad = 0;
     mutate(good, 200 + (unsigned)n, [&](const std::vector<uint8_t>& t) {
       isl_hnsw* x = nullptr;
       const isl_status st = isl_hnsw_from_bytes(t.data(), t.size(), 0, &x);
-      if (x) isl_hnsw_free(x);
+      if (x) { hnsw_round_trip(x); isl_hnsw_free(x); }
       if (st == ISL_OK || st == ISL_ERR_DEVICE) dev++; else bad++;
       EXPECT(is_status(st));
     });

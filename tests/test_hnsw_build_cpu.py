@@ -2,7 +2,9 @@
 against the oracle's HnswGraph::insert, what the two selection rules leave behind, and every part of the
 new entry points that needs no GPU (argument checks, seeded levels, the empty graph, to_bytes)."""
 import math
+import os
 import struct
+import subprocess
 
 import numpy as np
 import pytest
@@ -74,6 +76,50 @@ def test_step_planner():
     for (a, ca), (b, _) in zip(steps, steps[1:]):
         assert a + ca == b and ca <= max(1, a // 8) and ca <= 64
     assert ref.plan_steps(lv, 1) == [(i, 1) for i in range(300)]
+
+
+@pytest.fixture(scope="module")
+def plan_dump():
+    """tests/cpp/build_plan_dump.cpp: the library's own planner (build_plan.hpp), built with g++ alone"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = os.path.join(root, "islands_amd", "lib", "build_plan_dump")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(root, "tests", "cpp", "build_plan_dump.cpp"),
+                           "-o", exe])
+
+    def run(levels, batch):
+        text = f"{batch} {len(levels)}\n" + " ".join(str(int(x)) for x in levels) + "\n"
+        out = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60, check=True).stdout
+        lines = out.splitlines()
+        steps = [tuple(int(x) for x in ln.split()[1:]) for ln in lines if ln.startswith("step")]
+        order = [int(x) for x in next(ln for ln in lines if ln.startswith("order")).split()[1:]]
+        largest = int(next(ln for ln in lines if ln.startswith("largest")).split()[1])
+        return steps, order, largest
+
+    return run
+
+
+PLAN_LEVELS = [("forced", forced_levels)] + [
+    (f"random{n}", lambda n=n: random_levels(n, 16, 40 + n)) for n in (1, 2, 9, 300, 5000)] + [
+    ("flat", lambda: np.zeros(5000, np.uint64))]  # all-zero levels: the steps of LeannIndex::build
+
+
+@pytest.mark.parametrize("batch", [1, 64, 4096])
+@pytest.mark.parametrize("levels", [c[1] for c in PLAN_LEVELS], ids=[c[0] for c in PLAN_LEVELS])
+def test_library_step_planner(plan_dump, levels, batch):
+    """plan_steps of build_plan.hpp == the tests' planner; inside a step the nodes are the step's id range in
+    level order, highest first, equal levels in id order (so the nodes that have a layer are a prefix)"""
+    lv = levels()
+    steps, order, largest = plan_dump(lv, batch)
+    assert [(0, 1)] + [(first, count) for first, count, _ in steps] == ref.plan_steps(lv, batch)
+    assert len(order) == len(lv) and order[0] == 0
+    for first, count, top in steps:
+        want = sorted(range(first, first + count), key=lambda i: -int(lv[i]))  # sorted() is stable
+        assert order[first:first + count] == want, (first, count)
+        assert top == max(int(lv[i]) for i in range(first, first + count))
+    assert largest == max([c for _, c, _ in steps] + [1])
+    if not np.any(lv):
+        assert order == list(range(len(lv)))  # the flat builder's case: no reorder
 
 
 @pytest.mark.parametrize("case", [("uniform", 0), ("clustered", 1)])
