@@ -80,20 +80,11 @@ int device_cu_count(int32_t device) {
 }
 
 void free_workspace(SearchWorkspace& ws) {
-  void* ptrs[] = {ws.ovf_tab, ws.status,  ws.payload,   ws.ctr,        ws.ticket,     ws.redo, ws.replay, ws.qsel, ws.qsel_h, ws.plog,
-                  ws.q_stage, ws.ids_stage, ws.dist_stage, ws.count_stage, ws.d_prof, ws.d_tline, ws.q_entry, ws.miss, ws.uniq,
-                  ws.uniq_count, ws.tl_tables, ws.qstate, ws.qflag, ws.qlist, ws.uslots, ws.xslot, ws.co_q, ws.co_ids, ws.co_dist,
-                  ws.co_cnt};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  void* pinned[] = {ws.h_status, ws.h_ctr, ws.h_head, ws.h_q, ws.h_ids, ws.h_dist, ws.h_count, ws.h_qlist, ws.h_xlist};
-  for (void* p : pinned)
-    if (p) (void)hipHostFree(p);
   if (ws.ev0) (void)hipEventDestroy(ws.ev0);
   if (ws.ev1) (void)hipEventDestroy(ws.ev1);
   if (ws.ev_in) (void)hipEventDestroy(ws.ev_in);
   if (ws.ev_done) (void)hipEventDestroy(ws.ev_done);
-  // (ws.stream belongs to the device's stream pool)
+  // (ws.stream belongs to the device's stream pool; the reset frees every buffer of the lane)
   ws = SearchWorkspace{};
 }
 
@@ -273,26 +264,9 @@ void isl_index_free(isl_index* idx) {
     join_lane_workers(idx);
     for (auto& w : idx->ws)
       if (w.busy && w.st_inflight) (void)hipStreamSynchronize(w.st_inflight);
-    if (idx->ell_owned) { (void)hipFree(idx->d_ell); (void)hipFree(idx->d_ell_deg); }
-    if (idx->d_emb16) (void)hipFree(idx->d_emb16);
-    if (idx->d_tokens) (void)hipFree(idx->d_tokens);
-    if (idx->d_lens) (void)hipFree(idx->d_lens);
-    if (idx->d_slot_of) (void)hipFree(idx->d_slot_of);
-    if (idx->d_owner) (void)hipFree(idx->d_owner);
-    if (idx->d_stamp) (void)hipFree(idx->d_stamp);
-    if (idx->d_slab_head) (void)hipFree(idx->d_slab_head);
-    if (idx->d_off) (void)hipFree(idx->d_off);
-    if (idx->d_adj) (void)hipFree(idx->d_adj);
-    if (idx->d_emb) (void)hipFree(idx->d_emb);
-    if (idx->d_norm2) (void)hipFree(idx->d_norm2);
-    if (idx->d_codes) (void)hipFree(idx->d_codes);
-    for (void* q : idx->hnsw_owned) (void)hipFree(q);
-    if (idx->d_layer_off) (void)hipFree((void*)idx->d_layer_off);
-    if (idx->d_layer_adj) (void)hipFree((void*)idx->d_layer_adj);
-    for (auto& w : idx->ws) free_workspace(w);
-    free_exact_pool(idx->pool);
+    for (auto& w : idx->ws) free_workspace(w);  // (their events)
   }
-  delete idx;
+  delete idx;  // every device array is a member that frees itself
 }
 
 uint64_t isl_index_len(const isl_index* idx) { return idx ? idx->num_nodes : 0; }
@@ -557,12 +531,13 @@ isl_status materialise_host_csr(const isl_index* cidx) {
   return ISL_OK;
 }
 
-static isl_status scan_device_csr(isl_index* idx, uint32_t* d_flags, uint32_t* flags_out) {
+static isl_status scan_device_csr(isl_index* idx, const uint64_t* d_off, const uint32_t* d_adj, uint32_t* d_flags,
+                                  uint32_t* flags_out) {
   uint32_t* d_maxdeg = d_flags + 1;
   if (idx->num_nodes) {
     uint32_t blocks = (uint32_t)((idx->num_nodes + 255) / 256);
-    hipLaunchKernelGGL(row_stats_kernel, dim3(blocks), dim3(256), 0, 0, idx->d_off, idx->d_adj,
-                       idx->num_nodes, d_flags, d_maxdeg);
+    hipLaunchKernelGGL(row_stats_kernel, dim3(blocks), dim3(256), 0, 0, d_off, d_adj, idx->num_nodes, d_flags,
+                       d_maxdeg);
     ISL_HIP(hipGetLastError());
   }
   uint32_t host[2] = {0, 0};
@@ -587,7 +562,6 @@ isl_status isl_index_upload(isl_index* idx, int32_t device) {
   if (idx->num_nodes >= kMaxDeviceId)
     return fail(ISL_ERR_UNSUPPORTED, "num_nodes %llu exceeds the device id range",
                 (unsigned long long)idx->num_nodes);
-  idx->device = device;
   uint64_t nnz = idx->num_nodes ? idx->node_offsets[idx->num_nodes] : 0;
 
   // Duplicate ids inside one adjacency row are always "already visited" at their
@@ -597,38 +571,33 @@ isl_status isl_index_upload(isl_index* idx, int32_t device) {
   const uint64_t* nb_src = idx->neighbors.data();
   std::vector<uint64_t> dedup;
 
-  uint32_t* d_flags = nullptr;
-  ISL_HIP(hipMalloc(&d_flags, 16));
-  ISL_HIP(hipMemset(d_flags, 0, 16));
+  // the copy joins the handle only once it is complete: a failed upload leaves the index not uploaded
+  DeviceBuffer<uint64_t> d_off;
+  DeviceBuffer<uint32_t> d_adj, d_flags;
+  ISL_TRY(d_flags.reserve(4));
   for (int pass = 0; pass < 2; pass++) {
-    ISL_HIP(hipMalloc(&idx->d_off, (idx->num_nodes + 1) * 8));
-    ISL_HIP(hipMemcpy(idx->d_off, off.data(), (idx->num_nodes + 1) * 8, hipMemcpyHostToDevice));
-    ISL_HIP(hipMalloc(&idx->d_adj, (nnz ? nnz : 1) * 4));
+    ISL_HIP(hipMemset(d_flags, 0, 16));
+    ISL_TRY(d_off.reserve(idx->num_nodes + 1));
+    ISL_HIP(hipMemcpy(d_off, off.data(), (idx->num_nodes + 1) * 8, hipMemcpyHostToDevice));
+    ISL_TRY(d_adj.reserve(nnz ? nnz : 1));
     if (nnz) {
-      uint64_t* d_tmp = nullptr;
-      ISL_HIP(hipMalloc(&d_tmp, nnz * 8));
+      DeviceBuffer<uint64_t> d_tmp;
+      ISL_TRY(d_tmp.reserve(nnz));
       ISL_HIP(hipMemcpy(d_tmp, nb_src, nnz * 8, hipMemcpyHostToDevice));
-      hipLaunchKernelGGL(convert_adj_kernel, dim3(2048), dim3(256), 0, 0, d_tmp, idx->d_adj, nnz,
-                         d_flags);
+      hipLaunchKernelGGL(convert_adj_kernel, dim3(2048), dim3(256), 0, 0, d_tmp.get(), d_adj.get(), nnz,
+                         d_flags.get());
       ISL_HIP(hipGetLastError());
       ISL_HIP(hipDeviceSynchronize());
-      ISL_HIP(hipFree(d_tmp));
     }
-    idx->nnz = nnz;
     uint32_t flags = 0;
-    ISL_TRY(scan_device_csr(idx, d_flags, &flags));
-    if (flags & 1u) {
-      (void)hipFree(d_flags);
+    ISL_TRY(scan_device_csr(idx, d_off, d_adj, d_flags, &flags));
+    if (flags & 1u)
       return fail(ISL_ERR_UNSUPPORTED, "neighbour ids above 0x%x are not representable on device",
                   kMaxDeviceId);
-    }
     if (!(flags & 6u) || pass == 1) break;
     // rebuild without in-row duplicates on the host, then upload again
-    (void)hipFree(idx->d_off);
-    (void)hipFree(idx->d_adj);
-    idx->d_off = nullptr;
-    idx->d_adj = nullptr;
-    ISL_HIP(hipMemset(d_flags, 0, 16));
+    d_off.reset();
+    d_adj.reset();
     dedup.clear();
     dedup.reserve(nnz);
     std::vector<uint64_t> row;
@@ -655,7 +624,10 @@ isl_status isl_index_upload(isl_index* idx, int32_t device) {
     nnz = dedup.size();
     nb_src = dedup.data();
   }
-  (void)hipFree(d_flags);
+  idx->d_off = std::move(d_off);
+  idx->d_adj = std::move(d_adj);
+  idx->nnz = nnz;
+  idx->device = device;
   return ensure_padded_adjacency(idx);
 }
 
@@ -683,19 +655,17 @@ isl_status isl_index_from_device_csr(const isl_leann_config* cfg, int32_t device
   if (hipMemcpy(&nnz, d_node_offsets + num_nodes, 8, hipMemcpyDeviceToHost) != hipSuccess)
     return bail(fail(ISL_ERR_DEVICE, "cannot read node_offsets[num_nodes] from the device"));
   idx->nnz = nnz;
-  if (hipMalloc(&idx->d_off, (num_nodes + 1) * 8) != hipSuccess ||
-      hipMalloc(&idx->d_adj, (nnz ? nnz : 1) * 4) != hipSuccess)
+  if (idx->d_off.reserve(num_nodes + 1) != ISL_OK || idx->d_adj.reserve(nnz ? nnz : 1) != ISL_OK)
     return bail(fail(ISL_ERR_DEVICE, "hipMalloc failed for the CSR copy"));
   if (hipMemcpy(idx->d_off, d_node_offsets, (num_nodes + 1) * 8, hipMemcpyDeviceToDevice) !=
           hipSuccess ||
       (nnz && hipMemcpy(idx->d_adj, d_neighbors, nnz * 4, hipMemcpyDeviceToDevice) != hipSuccess))
     return bail(fail(ISL_ERR_DEVICE, "device copy of the CSR failed"));
-  uint32_t* d_flags = nullptr;
-  if (hipMalloc(&d_flags, 16) != hipSuccess || hipMemset(d_flags, 0, 16) != hipSuccess)
+  DeviceBuffer<uint32_t> d_flags;
+  if (d_flags.reserve(4) != ISL_OK || hipMemset(d_flags, 0, 16) != hipSuccess)
     return bail(fail(ISL_ERR_DEVICE, "hipMalloc failed"));
   uint32_t flags = 0;
-  isl_status st = scan_device_csr(idx, d_flags, &flags);
-  (void)hipFree(d_flags);
+  isl_status st = scan_device_csr(idx, idx->d_off, idx->d_adj, d_flags, &flags);
   if (st != ISL_OK) return bail(st);
   if (flags & 6u)
     return bail(fail(ISL_ERR_UNSUPPORTED,
@@ -719,8 +689,8 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
   std::lock_guard<std::mutex> lock(idx->mu);
   if (any_lane_busy(idx))  // their kernels read the tables freed below
     return fail(ISL_ERR_SEARCH, "Search error: the embedding provider cannot be swapped while searches are in flight");
-  if (idx->d_emb) { (void)hipFree(idx->d_emb); idx->d_emb = nullptr; }
-  if (idx->d_emb16) { (void)hipFree(idx->d_emb16); idx->d_emb16 = nullptr; }
+  idx->d_emb.reset();
+  idx->d_emb16.reset();
   free_exact_pool(idx->pool);  // sized by the row count: rebuilt by the next prepare / search
   idx->recompute = false;  // back to the in-memory provider
   if (dtype == ISL_DTYPE_BF16) {
@@ -729,39 +699,38 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
     if (idx->is_hnsw) return fail(ISL_ERR_UNSUPPORTED, "the HnswGraph facade keeps f32 vectors");
     const uint64_t stride16 = (d + 7) / 8 * 8;
     const size_t bytes16 = (size_t)(n * stride16 + 512) * 2;
-    ISL_HIP(hipMalloc(&idx->d_emb16, bytes16));
+    ISL_TRY(idx->d_emb16.reserve(n * stride16 + 512));
     ISL_HIP(hipMemset(idx->d_emb16, 0, bytes16));
     hipMemcpyKind kind16 = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     ISL_HIP(hipMemcpy2D(idx->d_emb16, stride16 * 2, rows, d * 2, d * 2, n, kind16));
     idx->nvec = n;
     idx->emb_d = d;
     idx->emb_stride = stride16;
-    if (idx->d_norm2) { (void)hipFree(idx->d_norm2); idx->d_norm2 = nullptr; }
-    ISL_HIP(hipMalloc(&idx->d_norm2, (size_t)n * 4));
+    idx->d_norm2.reset();
+    ISL_TRY(idx->d_norm2.reserve(n));
     // norm_b in the reference's order: widen a chunk of rows to f32 and reuse the f32 kernel
     using namespace isl_dev;
     const uint64_t stride32 = (d + 3) / 4 * 4;
     const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, (256ull << 20) / (stride32 * 4)));
-    float* tmp = nullptr;
-    ISL_HIP(hipMalloc(&tmp, (size_t)(chunk * stride32 + 256) * 4));
+    DeviceBuffer<float> tmp;
+    ISL_TRY(tmp.reserve(chunk * stride32 + 256));
     ISL_HIP(hipMemset(tmp, 0, (size_t)(chunk * stride32 + 256) * 4));
     const size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
     for (uint64_t o = 0; o < n; o += chunk) {
       const uint64_t c = std::min(chunk, n - o);
       hipLaunchKernelGGL(widen_bf16_kernel, dim3((uint32_t)((c * d + 255) / 256)), dim3(256), 0, 0,
-                         idx->d_emb16 + o * stride16, stride16, (uint32_t)d, c, tmp, stride32);
+                         idx->d_emb16 + o * stride16, stride16, (uint32_t)d, c, tmp.get(), stride32);
       hipLaunchKernelGGL(row_norm2_kernel, dim3((uint32_t)std::min<uint64_t>((c + 63) / 64, 8192)), dim3(64), lds,
-                         0, tmp, c, (uint32_t)d, stride32, idx->d_norm2 + o);
+                         0, tmp.get(), c, (uint32_t)d, stride32, idx->d_norm2 + o);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(tmp);
     if (e != hipSuccess) return fail(ISL_ERR_DEVICE, "bf16 row upload failed: %s", hipGetErrorString(e));
     return ISL_OK;
   }
   uint64_t stride = (d + 3) / 4 * 4;  // rows start 16-byte aligned
   size_t bytes = (size_t)(n * stride + 256) * sizeof(float);  // slack for whole-slab reads
-  ISL_HIP(hipMalloc(&idx->d_emb, bytes));
+  ISL_TRY(idx->d_emb.reserve(n * stride + 256));
   if (stride != d) ISL_HIP(hipMemset(idx->d_emb, 0, bytes));
   else ISL_HIP(hipMemset(idx->d_emb + n * stride, 0, 256 * sizeof(float)));
   hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -772,14 +741,14 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
   idx->emb_stride = stride;
   // norm_b of cosine_distance (distance.rs:79) depends on the row alone: computed once, in the
   // reference's left-to-right order, and reused by every search
-  if (idx->d_norm2) { (void)hipFree(idx->d_norm2); idx->d_norm2 = nullptr; }
-  ISL_HIP(hipMalloc(&idx->d_norm2, (size_t)n * 4));
+  idx->d_norm2.reset();
+  ISL_TRY(idx->d_norm2.reserve(n));
   {
     using namespace isl_dev;
     size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
     uint32_t grid = (uint32_t)std::min<uint64_t>((n + 63) / 64, 8192);
-    hipLaunchKernelGGL(row_norm2_kernel, dim3(grid), dim3(64), lds, 0, idx->d_emb, n, (uint32_t)d,
-                       stride, idx->d_norm2);
+    hipLaunchKernelGGL(row_norm2_kernel, dim3(grid), dim3(64), lds, 0, idx->d_emb.get(), n, (uint32_t)d,
+                       stride, idx->d_norm2.get());
     ISL_HIP(hipGetLastError());
     ISL_HIP(hipDeviceSynchronize());
   }
@@ -788,25 +757,23 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
 
 // (re)allocates the recompute provider's row cache: slab, per-slot norms, slot map, owners
 static isl_status alloc_recompute_cache(isl_index* idx, uint64_t rows) {
-  void* olds[] = {idx->d_emb, idx->d_norm2, idx->d_slot_of, idx->d_owner, idx->d_stamp, idx->d_slab_head};
-  for (void* p : olds)
-    if (p) (void)hipFree(p);
-  idx->d_emb = nullptr; idx->d_norm2 = nullptr; idx->d_slot_of = nullptr; idx->d_owner = nullptr;
-  idx->d_stamp = nullptr; idx->d_slab_head = nullptr;
+  // the old cache goes before the new one is allocated: the slab may be most of the card
+  idx->d_emb.reset(); idx->d_norm2.reset(); idx->d_slot_of.reset();
+  idx->d_owner.reset(); idx->d_stamp.reset(); idx->d_slab_head.reset();
   idx->slab_rows = 0;
   const uint64_t stride = idx->emb_stride, n = idx->nvec;
-  ISL_HIP(hipMalloc(&idx->d_emb, (size_t)(rows * stride + 256) * sizeof(float)));
-  ISL_HIP(hipMemset(idx->d_emb, 0, (size_t)(rows * stride + 256) * sizeof(float)));
-  ISL_HIP(hipMalloc(&idx->d_norm2, (size_t)rows * 4));
-  ISL_HIP(hipMemset(idx->d_norm2, 0, (size_t)rows * 4));
-  ISL_HIP(hipMalloc(&idx->d_slot_of, (size_t)(n + 1) * 4));
-  ISL_HIP(hipMemset(idx->d_slot_of, 0xFF, (size_t)(n + 1) * 4));
-  ISL_HIP(hipMalloc(&idx->d_owner, (size_t)rows * 4));
-  ISL_HIP(hipMemset(idx->d_owner, 0xFF, (size_t)rows * 4));
-  ISL_HIP(hipMalloc(&idx->d_stamp, (size_t)rows * 4));
-  ISL_HIP(hipMemset(idx->d_stamp, 0, (size_t)rows * 4));
-  ISL_HIP(hipMalloc(&idx->d_slab_head, 8));  // [0] clock hand, [1] slots used so far
-  ISL_HIP(hipMemset(idx->d_slab_head, 0, 8));
+  // a block of `count` elements, every byte `fill`
+  auto fresh = [](auto& buf, uint64_t count, int fill) -> isl_status {
+    ISL_TRY(buf.reserve(count));
+    ISL_HIP(hipMemset(buf, fill, count * sizeof(*buf.get())));
+    return ISL_OK;
+  };
+  ISL_TRY(fresh(idx->d_emb, rows * stride + 256, 0));
+  ISL_TRY(fresh(idx->d_norm2, rows, 0));
+  ISL_TRY(fresh(idx->d_slot_of, n + 1, 0xFF));
+  ISL_TRY(fresh(idx->d_owner, rows, 0xFF));
+  ISL_TRY(fresh(idx->d_stamp, rows, 0));
+  ISL_TRY(fresh(idx->d_slab_head, 2, 0));  // [0] clock hand, [1] slots used so far
   idx->slab_rows = rows;
   return ISL_OK;
 }
@@ -848,13 +815,9 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
   const uint64_t d = enc->cfg.hidden, stride = (d + 3) / 4 * 4;
   // (d_emb16 too: bf16 rows of an earlier in-memory provider would otherwise stay the table the
   // searches read)
-  void* olds[] = {idx->d_emb, idx->d_emb16, idx->d_norm2, idx->d_tokens, idx->d_lens, idx->d_slot_of, idx->d_owner,
-                  idx->d_stamp, idx->d_slab_head};
-  for (void* p : olds)
-    if (p) (void)hipFree(p);
-  idx->d_emb = nullptr; idx->d_emb16 = nullptr; idx->d_norm2 = nullptr; idx->d_tokens = nullptr;
-  idx->d_lens = nullptr; idx->d_slot_of = nullptr; idx->d_owner = nullptr; idx->d_stamp = nullptr;
-  idx->d_slab_head = nullptr;
+  idx->d_emb16.reset();
+  idx->d_tokens.reset();
+  idx->d_lens.reset();
   free_exact_pool(idx->pool);
   idx->recompute = false;
   // Recompute mode does not store embeddings (leann.rs:366-371): what is resident is the token
@@ -866,10 +829,10 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
   idx->emb_stride = stride;
   ISL_TRY(alloc_recompute_cache(idx, std::min<uint64_t>(n, 1ull << 20)));
   hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  ISL_HIP(hipMalloc(&idx->d_tokens, (size_t)n * L * 2));
+  ISL_TRY(idx->d_tokens.reserve(n * L));
   ISL_HIP(hipMemcpy(idx->d_tokens, tokens, (size_t)n * L * 2, kind));
   if (lengths) {
-    ISL_HIP(hipMalloc(&idx->d_lens, (size_t)n * 2));
+    ISL_TRY(idx->d_lens.reserve(n));
     ISL_HIP(hipMemcpy(idx->d_lens, lengths, (size_t)n * 2, kind));
   }
   idx->enc = enc;

@@ -532,14 +532,13 @@ isl_status Scaffold::table_to_csr(const Table& t, uint64_t n, bool kept, uint64_
 }
 
 void Scaffold::hand_rows_to(isl_index* r) {
-  r->d_emb = g->d_emb; r->d_norm2 = g->d_norm2;
+  r->d_emb = std::move(g->d_emb); r->d_norm2 = std::move(g->d_norm2);
   r->nvec = g->nvec; r->emb_d = g->emb_d; r->emb_stride = g->emb_stride;
-  g->d_emb = nullptr; g->d_norm2 = nullptr;
 }
 
 isl_index* Scaffold::release() {
   isl_index* r = res;
-  r->hnsw_owned.insert(r->hnsw_owned.end(), keep.begin(), keep.end());
+  for (void* q : keep) r->hnsw_owned.emplace_back().adopt(static_cast<unsigned char*>(q), 0);
   keep.clear();
   res = nullptr;
   return r;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/islands_amd.h"
+#include "device_buffer.hpp"
 
 namespace isl {
 
@@ -53,35 +54,30 @@ int device_cu_count(int32_t device);
 // pinned host mirrors and (host-pointer entry points) staging buffers.  A lane is claimed under
 // isl_index::mu and then touched by its owner alone until it is released, so the entry points do
 // not hold the index mutex while they enqueue, wait or copy.
+// Every array is a buffer that knows its capacity and frees itself with the lane.
 struct SearchWorkspace {
   uint32_t slots = 0;          // resident waves the scratch is sized for
   uint32_t ovf_bits = 0;       // log2 entries of the per-slot overflow visited table
-  uint32_t* ovf_tab = nullptr; // [slots][1 << ovf_bits], EMPTY-filled between queries
-  uint32_t cap_q = 0;          // per-query arrays sized for this many queries
-  uint32_t* status = nullptr;  // [cap_q]
-  uint64_t* payload = nullptr; // [cap_q]
-  uint32_t* ctr = nullptr;     // [cap_q][4]  H,E,V,pushes
-  uint32_t* ticket = nullptr;  // work-queue heads (fast, exact)
-  uint32_t* redo = nullptr;    // [cap_q] query ids routed to the exact kernel
-  uint32_t* replay = nullptr;  // [cap_q] query ids routed to the replay kernel
-  uint32_t* qsel = nullptr;    // [cap_q] bf16 rows: queries whose elements are not all bf16 values
-  uint32_t* qsel_h = nullptr;  // [cap_q] ... and the queries whose elements are
-  uint64_t* plog = nullptr;    // [cap_q][plog_cap] push log (distance bits, id)
-  uint64_t plog_entries = 0;
+  DeviceBuffer<uint32_t> ovf_tab;  // [slots][1 << ovf_bits], EMPTY-filled between queries
+  DeviceBuffer<uint32_t> status;  // one entry per query, at least 1024 (prepare_workspace)
+  DeviceBuffer<uint64_t> payload;  // [status.capacity()]
+  DeviceBuffer<uint32_t> ctr;     // [status.capacity()][4]  H,E,V,pushes
+  DeviceBuffer<uint32_t> ticket;  // work-queue heads (fast, exact)
+  DeviceBuffer<uint32_t> redo;    // [status.capacity()] query ids routed to the exact kernel
+  DeviceBuffer<uint32_t> replay;  // [status.capacity()] query ids routed to the replay kernel
+  DeviceBuffer<uint32_t> qsel;    // [status.capacity()] bf16 rows: queries whose elements are not all bf16 values
+  DeviceBuffer<uint32_t> qsel_h;  // [status.capacity()] ... and the queries whose elements are
+  DeviceBuffer<uint64_t> plog;    // [status.capacity()][plog_cap] push log (distance bits, id)
   // staging for the host-pointer entry points: device side ...
-  float* q_stage = nullptr;
-  uint64_t q_stage_bytes = 0;
-  uint64_t* ids_stage = nullptr;
-  float* dist_stage = nullptr;
-  uint32_t* count_stage = nullptr;
-  uint64_t out_stage_slots = 0;
+  DeviceBuffer<float> q_stage;
+  DeviceBuffer<uint64_t> ids_stage;
+  DeviceBuffer<float> dist_stage;
+  DeviceBuffer<uint32_t> count_stage;
   // ... and pinned host side (the caller's buffers are pageable: copied through these)
-  float* h_q = nullptr;
-  uint64_t h_q_bytes = 0;
-  uint64_t* h_ids = nullptr;
-  float* h_dist = nullptr;
-  uint32_t* h_count = nullptr;
-  uint64_t h_out_slots = 0;
+  PinnedBuffer<float> h_q;
+  PinnedBuffer<uint64_t> h_ids;
+  PinnedBuffer<float> h_dist;
+  PinnedBuffer<uint32_t> h_count;
   hipStream_t stream = nullptr;  // from the device's stream pool (search.hip): shared, never destroyed here
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_in = nullptr, ev_done = nullptr;
   // call in flight on this lane (claim .. release)
@@ -99,43 +95,34 @@ struct SearchWorkspace {
   uint64_t* u_ids = nullptr;
   float* u_dist = nullptr;
   uint32_t* u_count = nullptr;
-  uint32_t* h_status = nullptr;  // pinned host mirrors of status / ctr / ticket
-  uint32_t* h_ctr = nullptr;
-  uint32_t* h_head = nullptr;
-  uint64_t h_cap = 0;
-  uint64_t* d_prof = nullptr;    // ISL_DEBUG phase timers of the call in flight
-  uint64_t* d_tline = nullptr;   // ISL_TIMELINE: [nq][2] start / end ticks of every query of the call in flight
-  uint32_t* q_entry = nullptr;   // HnswGraph: [2][nq] layer-0 entry and descent evaluations per query
-  uint64_t q_entry_cap = 0;
+  PinnedBuffer<uint32_t> h_status;  // pinned host mirrors of status / ctr / ticket
+  PinnedBuffer<uint32_t> h_ctr;
+  PinnedBuffer<uint32_t> h_head;
+  DeviceBuffer<uint64_t> d_prof;    // ISL_DEBUG phase timers of the call in flight
+  DeviceBuffer<uint64_t> d_tline;   // ISL_TIMELINE: [nq][2] start / end ticks of every query of the call in flight
+  DeviceBuffer<uint32_t> q_entry;   // HnswGraph: [2][nq] layer-0 entry and descent evaluations per query
   // recompute provider: the union of the calls this lane answers as one (search.hip, recompute_coalesced)
-  float* co_q = nullptr;
-  uint64_t co_q_cap = 0;
-  uint64_t* co_ids = nullptr;
-  uint64_t co_ids_cap = 0;
-  float* co_dist = nullptr;
-  uint64_t co_dist_cap = 0;
-  uint32_t* co_cnt = nullptr;
-  uint64_t co_cnt_cap = 0;
+  DeviceBuffer<float> co_q;
+  DeviceBuffer<uint64_t> co_ids;
+  DeviceBuffer<float> co_dist;
+  DeviceBuffer<uint32_t> co_cnt;
   // recompute provider: node ids whose rows a search round found absent, and their unique set
-  uint32_t* miss = nullptr;
-  uint32_t* uniq = nullptr;
-  uint32_t* uniq_count = nullptr;
+  DeviceBuffer<uint32_t> miss;
+  DeviceBuffer<uint32_t> uniq;
+  DeviceBuffer<uint32_t> uniq_count;
   uint64_t miss_cap = 0;
   uint64_t pref_cap = 0;         // entries behind miss[miss_cap]: ids a parked two-level query expects to promote next
   // ... and, for the searches that park and resume (fast kernel over the recompute provider): the
   // parked state of every query, its flag, the list of queries a round runs
-  uint32_t* qstate = nullptr;
-  uint64_t qstate_words = 0;     // allocated, in words
-  uint32_t* qflag = nullptr;     // [qlist_cap]
-  uint32_t* qlist = nullptr;     // [qlist_cap] device
-  uint32_t* h_qlist = nullptr;   // [qlist_cap] pinned
-  uint32_t* uslots = nullptr;    // [miss_cap] slab slots of the round's unique misses
-  uint64_t qlist_cap = 0;
-  uint32_t* xslot = nullptr;     // [qlist_cap] 1 + pool slot of a query parked in the heap-exact kernel
-  uint32_t* h_xlist = nullptr;   // [qlist_cap] pinned: the parked queries the next round hands to that kernel directly
+  DeviceBuffer<uint32_t> qstate;    // [nq][state words of the call]
+  DeviceBuffer<uint32_t> qflag;     // [qlist.capacity()]
+  DeviceBuffer<uint32_t> qlist;     // [qlist.capacity()] device
+  PinnedBuffer<uint32_t> h_qlist;   // [qlist.capacity()] pinned
+  DeviceBuffer<uint32_t> uslots;    // [miss_cap] slab slots of the round's unique misses
+  DeviceBuffer<uint32_t> xslot;     // [qlist.capacity()] 1 + pool slot of a query parked in the heap-exact kernel
+  PinnedBuffer<uint32_t> h_xlist;   // [qlist.capacity()] pinned: the parked queries the next round hands to that kernel directly
   // two-level search: per-query PQ distance tables [nq][m * K]
-  float* tl_tables = nullptr;
-  uint64_t tl_tables_cap = 0;
+  DeviceBuffer<float> tl_tables;
   // Asynchronous calls that cannot be split into "enqueue now, finish at wait" -- the rounds of the
   // recompute provider, the two-level search with its per-query retries -- run their synchronous form
   // on a host thread of their own; whoever waits for the token joins it and takes its status and
@@ -159,14 +146,14 @@ constexpr int kSearchLanes = 32;  // independent workspaces = searches that may 
 struct ExactPool {
   uint32_t slots = 0;
   uint64_t cand_cap = 0;        // entries per slot in the candidate heap
-  float* cand_d = nullptr;      // [slots][cand_cap]
-  uint32_t* cand_id = nullptr;
-  uint32_t* vis_bits = nullptr; // [slots][vis_words] visited bitmap
+  DeviceBuffer<float> cand_d;       // [slots][cand_cap]
+  DeviceBuffer<uint32_t> cand_id;
+  DeviceBuffer<uint32_t> vis_bits;  // [slots][vis_words] visited bitmap
   uint64_t vis_words = 0;
-  uint32_t* ulist = nullptr;    // [slots][ulist_cap] unvisited ids of one hop
+  DeviceBuffer<uint32_t> ulist;     // [slots][ulist_cap] unvisited ids of one hop
   uint32_t ulist_cap = 0;
-  uint32_t* locks = nullptr;    // [slots] 0 = free, 1 = held by a workgroup (or by a query parked in the slot)
-  uint32_t* xstate = nullptr;   // [slots][xstate_words] recompute provider: result heap + scalars of a parked query
+  DeviceBuffer<uint32_t> locks;     // [slots] 0 = free, 1 = held by a workgroup (or by a query parked in the slot)
+  DeviceBuffer<uint32_t> xstate;    // [slots][xstate_words] recompute provider: result heap + scalars of a parked query
   uint32_t xstate_words = 0;
 };
 
@@ -177,7 +164,7 @@ struct isl_pq {
   uint64_t dimension = 0, m = 0, K = 0, dsub = 0, cstride = 0;
   int32_t metric = ISL_METRIC_EUCLIDEAN;
   int32_t device = 0;
-  float* d_codebooks = nullptr;  // [m][K][cstride], rows 16-byte aligned, slack at the end
+  isl::DeviceBuffer<float> d_codebooks;  // [m][K][cstride], rows 16-byte aligned, slack at the end
 };
 
 // The opaque handle of the ABI.  Host side mirrors LeannIndex (leann.rs:492-500).
@@ -198,8 +185,8 @@ struct isl_index {
 
   // device residency
   int32_t device = -1;
-  uint64_t* d_off = nullptr;  // [num_nodes + 1]
-  uint32_t* d_adj = nullptr;  // [nnz] (duplicates within a row removed, first occurrence kept)
+  isl::DeviceBuffer<uint64_t> d_off;  // [num_nodes + 1]
+  isl::DeviceBuffer<uint32_t> d_adj;  // [nnz] (duplicates within a row removed, first occurrence kept)
   uint64_t nnz = 0;
   uint32_t max_degree = 0;
   // distance evaluations per query of the most recent in-memory search call and the ef it ran with, packed
@@ -207,16 +194,16 @@ struct isl_index {
   // (search.hip, fast_geometry)
   mutable std::atomic<uint64_t> evals_hint{0};
   // in-memory provider (leann.rs:104-159): nvec rows, `stride` floats apart
-  float* d_emb = nullptr;
-  uint16_t* d_emb16 = nullptr;  // bf16 rows (ISL_DTYPE_BF16) instead of d_emb
-  float* d_norm2 = nullptr;  // [nvec] sum of squares of every row, reference summation order
+  isl::DeviceBuffer<float> d_emb;
+  isl::DeviceBuffer<uint16_t> d_emb16;  // bf16 rows (ISL_DTYPE_BF16) instead of d_emb
+  isl::DeviceBuffer<float> d_norm2;  // [nvec] sum of squares of every row, reference summation order
   uint64_t nvec = 0, emb_d = 0, emb_stride = 0;
 
   // graph under construction (build.hip): fixed-width adjacency rows, searched in place
-  uint32_t* d_ell = nullptr;      // [num_nodes][ell_w]
+  uint32_t* d_ell = nullptr;      // [num_nodes][ell_w]: the builder's rows (borrowed) or ell_copy
   uint32_t* d_ell_deg = nullptr;  // [num_nodes]
   uint32_t ell_w = 0;
-  bool ell_owned = false;         // the padded copy made at the first search (freed with the index)
+  isl::DeviceBuffer<uint32_t> ell_copy, ell_deg_copy;  // the padded copy made at the first search
 
   // HnswGraph under construction (hnsw_build.hip): [nq] entry node of every query of the next construction
   // search on the layer in d_ell, and the evaluations its counters start from (device arrays, borrowed);
@@ -229,16 +216,16 @@ struct isl_index {
   // not stored (leann.rs:366-371); the search reports the rows it misses and the provider encodes
   // them from the resident token table into a bounded row cache
   struct isl_encoder* enc = nullptr;   // borrowed
-  uint16_t* d_tokens = nullptr;        // [nvec][tok_L]
-  uint16_t* d_lens = nullptr;          // [nvec] or NULL
+  isl::DeviceBuffer<uint16_t> d_tokens; // [nvec][tok_L]
+  isl::DeviceBuffer<uint16_t> d_lens;   // [nvec] or NULL
   uint32_t tok_L = 0;
   // the rows live in a bounded slab (d_emb / d_norm2 indexed by SLOT): slot_of[id] = the node's
   // slot or 0xFFFFFFFF, owner[slot] = the node in it; slots are handed out round-robin, so the
   // oldest rows make room once the slab is full
-  uint32_t* d_slot_of = nullptr;       // [nvec]
-  uint32_t* d_owner = nullptr;         // [slab_rows]
-  uint32_t* d_stamp = nullptr;         // [slab_rows] round in which a row was last asked for
-  uint32_t* d_slab_head = nullptr;     // [1] where the clock hand of the slot allocator stands
+  isl::DeviceBuffer<uint32_t> d_slot_of;    // [nvec]
+  isl::DeviceBuffer<uint32_t> d_owner;      // [slab_rows]
+  isl::DeviceBuffer<uint32_t> d_stamp;      // [slab_rows] round in which a row was last asked for
+  isl::DeviceBuffer<uint32_t> d_slab_head;  // [1] where the clock hand of the slot allocator stands
   uint64_t slab_rows = 0;
   mutable uint32_t round_no = 1;       // rounds of recompute searches so far (under recompute_mu)
   bool recompute = false, keep_rows = false;
@@ -247,14 +234,15 @@ struct isl_index {
   // HnswGraph facade (hnsw.rs): distance-only heap order + upper layers for the greedy descent
   bool is_hnsw = false;
   uint64_t hnsw_layers = 0;
-  const uint64_t** d_layer_off = nullptr;  // device array of device pointers, [max_level + 1]
-  const uint32_t** d_layer_adj = nullptr;
-  std::vector<void*> hnsw_owned;           // device allocations of the upper layers
+  isl::DeviceBuffer<const uint64_t*> d_layer_off;  // device array of device pointers, [max_level + 1]
+  isl::DeviceBuffer<const uint32_t*> d_layer_adj;
+  // the upper layers' arrays (u64 offsets and u32 ids alike), held as bytes only to be freed with the index
+  std::vector<isl::DeviceBuffer<unsigned char>> hnsw_owned;
 
   // two-level search (extension): PQ codes of every node, [ncodes][pq->m] u16 as ProductQuantizer::encode
   // writes them (pq.rs:221-244); the quantizer is borrowed
   const isl_pq* pq = nullptr;
-  uint16_t* d_codes = nullptr;
+  isl::DeviceBuffer<uint16_t> d_codes;
   uint64_t ncodes = 0;
 
   mutable std::mutex mu;  // lane claims, the exact pool, index mutation -- never held across a search

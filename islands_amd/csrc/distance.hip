@@ -74,35 +74,23 @@ isl_status run_distance(int32_t metric, const float* query, uint64_t d, const fl
   if (n == 0) return ISL_OK;
   if (d == 0 || d > 65536) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "dimension out of range");
   const uint64_t stride = (d + 3) / 4 * 4;
-  float *dq = nullptr, *drows = nullptr, *dout = nullptr;
-  auto cleanup = [&]() {
-    if (dq) (void)hipFree(dq);
-    if (drows) (void)hipFree(drows);
-    if (dout && mem == ISL_MEM_HOST) (void)hipFree(dout);
-  };
+  isl::TempScope tmp;
   hipMemcpyKind kin = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   // private padded copies keep the kernel's whole-slab reads inside the allocation
   size_t rbytes = (size_t)(n * stride + 256) * 4;
-  if (hipMalloc(&dq, (size_t)stride * 4) != hipSuccess ||
-      hipMalloc(&drows, rbytes) != hipSuccess) {
-    cleanup();
-    return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed in isl_distance_batch");
-  }
+  float* dq = tmp.alloc<float>(stride);
+  float* drows = tmp.alloc<float>(n * stride + 256);
+  float* dout = out;
+  if (!dq || !drows) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed in isl_distance_batch");
   hipError_t e = hipMemsetAsync(drows, 0, rbytes, st);
   if (e == hipSuccess) e = hipMemcpyAsync(dq, query, d * 4, kin, st);
   if (e == hipSuccess) {
     if (stride == d) e = hipMemcpyAsync(drows, rows, (size_t)n * d * 4, kin, st);
     else e = hipMemcpy2DAsync(drows, stride * 4, rows, d * 4, d * 4, n, kin, st);
   }
-  if (e == hipSuccess) {
-    if (mem == ISL_MEM_DEVICE) dout = out;
-    else e = hipMalloc(&dout, n * 4);
-  }
-  if (e != hipSuccess) {
-    cleanup();
-    return isl::fail(ISL_ERR_DEVICE, "staging failed in isl_distance_batch: %s",
-                     hipGetErrorString(e));
-  }
+  if (e == hipSuccess && mem == ISL_MEM_HOST && !(dout = tmp.alloc<float>(n))) e = hipErrorOutOfMemory;
+  if (e != hipSuccess)
+    return isl::fail(ISL_ERR_DEVICE, "staging failed in isl_distance_batch: %s", hipGetErrorString(e));
   uint32_t grid = (uint32_t)std::min<uint64_t>((n + 63) / 64, 4096);
   switch (metric) {
     case ISL_METRIC_COSINE: launch_dist<ISL_METRIC_COSINE>(grid, st, dq, drows, n, (uint32_t)d, stride, dout); break;
@@ -111,14 +99,12 @@ isl_status run_distance(int32_t metric, const float* query, uint64_t d, const fl
     case ISL_METRIC_MANHATTAN: launch_dist<ISL_METRIC_MANHATTAN>(grid, st, dq, drows, n, (uint32_t)d, stride, dout); break;
     case METRIC_EUCLID_SQ: launch_dist<METRIC_EUCLID_SQ>(grid, st, dq, drows, n, (uint32_t)d, stride, dout); break;
     default:
-      cleanup();
       return isl::fail(ISL_ERR_INVALID_ARGUMENT, "unknown metric %d", metric);
   }
   e = hipGetLastError();
   if (e == hipSuccess && mem == ISL_MEM_HOST)
     e = hipMemcpyAsync(out, dout, n * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
   if (e != hipSuccess)
     return isl::fail(ISL_ERR_DEVICE, "isl_distance_batch failed: %s", hipGetErrorString(e));
   return ISL_OK;
@@ -172,9 +158,9 @@ isl_status isl_normalize_rows(float* rows, uint64_t n, uint64_t d, int32_t mem, 
     return isl::fail(ISL_ERR_UNSUPPORTED, "isl_normalize_rows needs d to be a multiple of 4");
   ISL_TRY(isl::use_device(device));
   hipStream_t st = (hipStream_t)stream;
-  float* dr = nullptr;
-  size_t bytes = (size_t)(n * d + 256) * 4;
-  ISL_HIP(hipMalloc(&dr, bytes));
+  isl::TempScope tmp;
+  float* dr = tmp.alloc<float>(n * d + 256);
+  if (!dr) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed in isl_normalize_rows");
   hipMemcpyKind kin = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   hipMemcpyKind kout = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   hipError_t e = hipMemsetAsync(dr + n * d, 0, 256 * 4, st);
@@ -189,7 +175,6 @@ isl_status isl_normalize_rows(float* rows, uint64_t n, uint64_t d, int32_t mem, 
   }
   if (e == hipSuccess) e = hipMemcpyAsync(rows, dr, (size_t)n * d * 4, kout, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(dr);
   if (e != hipSuccess)
     return isl::fail(ISL_ERR_DEVICE, "isl_normalize_rows failed: %s", hipGetErrorString(e));
   return ISL_OK;

@@ -145,24 +145,13 @@ __global__ __launch_bounds__(64) void topk_chunk_kernel(const float* __restrict_
   if (lane == 0) best_n[q] = cnt;
 }
 
-struct Staged {
-  std::vector<void*> owned;
-  ~Staged() { for (void* p : owned) (void)hipFree(p); }
-  void* alloc(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-    owned.push_back(p);
-    return p;
-  }
-};
-
 // device copy of a [n][d] matrix with rows padded to a multiple of 4 floats (GEMM loads 16 B)
-isl_status stage_matrix(Staged& s, const float* src, uint64_t n, uint64_t d, int32_t mem, hipStream_t st,
+isl_status stage_matrix(isl::TempScope& s, const float* src, uint64_t n, uint64_t d, int32_t mem, hipStream_t st,
                         const float** out, uint64_t* stride) {
   const uint64_t ld = (d + 3) / 4 * 4;
   *stride = ld;
   if (mem == ISL_MEM_DEVICE && ld == d) { *out = src; return ISL_OK; }
-  float* p = (float*)s.alloc(n * ld * 4);
+  float* p = s.alloc<float>(n * ld);
   if (!p) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
   if (ld != d) ISL_HIP(hipMemsetAsync(p, 0, n * ld * 4, st));
   ISL_HIP(hipMemcpy2DAsync(p, ld * 4, src, d * 4, d * 4, n,
@@ -223,12 +212,12 @@ isl_status isl_row_sumsq_bf16(const uint16_t* rows, uint64_t n, uint64_t d, floa
   if (d == 0) return isl::fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
   ISL_TRY(isl::use_device(device));
   hipStream_t st = (hipStream_t)stream;
-  Staged s;
+  isl::TempScope s;
   const uint16_t* dr = rows;
   float* dout = out;
   if (mem == ISL_MEM_HOST) {
-    uint16_t* b = (uint16_t*)s.alloc(n * d * 2);
-    dout = (float*)s.alloc(n * 4);
+    uint16_t* b = s.alloc<uint16_t>(n * d);
+    dout = s.alloc<float>(n);
     if (!b || !dout) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     ISL_HIP(hipMemcpyAsync(b, rows, n * d * 2, hipMemcpyHostToDevice, st));
     dr = b;
@@ -255,13 +244,13 @@ isl_status isl_distance_matrix_bf16_norms(int32_t metric, const uint16_t* querie
     return isl::fail(ISL_ERR_UNSUPPORTED, "matrix too large for one launch: split the rows");
   ISL_TRY(isl::use_device(device));
   hipStream_t st = (hipStream_t)stream;
-  Staged s;
+  isl::TempScope s;
   const uint16_t *dq = queries, *dr = rows;
   float* dout = out;
   if (mem == ISL_MEM_HOST) {
-    uint16_t* a = (uint16_t*)s.alloc(nq * d * 2);
-    uint16_t* b = (uint16_t*)s.alloc(n * d * 2);
-    dout = (float*)s.alloc(nq * n * 4);
+    uint16_t* a = s.alloc<uint16_t>(nq * d);
+    uint16_t* b = s.alloc<uint16_t>(n * d);
+    dout = s.alloc<float>(nq * n);
     if (!a || !b || !dout) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     ISL_HIP(hipMemcpyAsync(a, queries, nq * d * 2, hipMemcpyHostToDevice, st));
     ISL_HIP(hipMemcpyAsync(b, rows, n * d * 2, hipMemcpyHostToDevice, st));
@@ -272,8 +261,8 @@ isl_status isl_distance_matrix_bf16_norms(int32_t metric, const uint16_t* querie
     return isl::fail(ISL_ERR_INVALID_ARGUMENT, "bf16 matrices must be 16-byte aligned");
   const float *qn = nullptr, *rn = nullptr;
   if (metric != ISL_METRIC_DOT) {  // (the dot epilogue reads no norms)
-    float* qbuf = (q_sumsq && mem == ISL_MEM_DEVICE) ? nullptr : (float*)s.alloc(nq * 4);
-    float* rbuf = (row_sumsq && mem == ISL_MEM_DEVICE) ? nullptr : (float*)s.alloc(n * 4);
+    float* qbuf = (q_sumsq && mem == ISL_MEM_DEVICE) ? nullptr : s.alloc<float>(nq);
+    float* rbuf = (row_sumsq && mem == ISL_MEM_DEVICE) ? nullptr : s.alloc<float>(n);
     if ((!qbuf && !(q_sumsq && mem == ISL_MEM_DEVICE)) || (!rbuf && !(row_sumsq && mem == ISL_MEM_DEVICE)))
       return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     if (q_sumsq && mem == ISL_MEM_HOST) ISL_HIP(hipMemcpyAsync(qbuf, q_sumsq, nq * 4, hipMemcpyHostToDevice, st));
@@ -321,14 +310,14 @@ isl_status isl_distance_matrix(int32_t metric, const float* queries, uint64_t nq
   if (nq > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return isl::fail(ISL_ERR_UNSUPPORTED, "matrix side above 2^32");
   ISL_TRY(isl::use_device(device));
   hipStream_t st = (hipStream_t)stream;
-  Staged s;
+  isl::TempScope s;
   const float *dq, *dr;
   uint64_t ldq, ldr;
   ISL_TRY(stage_matrix(s, queries, nq, d, mem, st, &dq, &ldq));
   ISL_TRY(stage_matrix(s, rows, n, d, mem, st, &dr, &ldr));
-  float* qn = (float*)s.alloc(nq * 4);
-  float* rn = (float*)s.alloc(n * 4);
-  float* dout = mem == ISL_MEM_DEVICE ? out : (float*)s.alloc(nq * n * 4);
+  float* qn = s.alloc<float>(nq);
+  float* rn = s.alloc<float>(n);
+  float* dout = mem == ISL_MEM_DEVICE ? out : s.alloc<float>(nq * n);
   if (!qn || !rn || !dout) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
   hipLaunchKernelGGL(sumsq_rows_kernel, dim3((uint32_t)((nq + 3) / 4)), dim3(256), 0, st, dq, nq, (uint32_t)d, ldq, qn);
   hipLaunchKernelGGL(sumsq_rows_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, st, dr, n, (uint32_t)d, ldr, rn);
@@ -348,11 +337,11 @@ isl_status isl_bruteforce_topk(int32_t metric, const float* queries, uint64_t nq
   if (nq > 0xFFFFFFFFull) return isl::fail(ISL_ERR_UNSUPPORTED, "too many queries");
   ISL_TRY(isl::use_device(device));
   hipStream_t st = (hipStream_t)stream;
-  Staged s;
+  isl::TempScope s;
   const uint64_t kk = k ? k : 1;
-  float* bd = (float*)s.alloc(nq * kk * 4);
-  uint64_t* bi = (uint64_t*)s.alloc(nq * kk * 8);
-  uint32_t* bn = (uint32_t*)s.alloc(nq * 4);
+  float* bd = s.alloc<float>(nq * kk);
+  uint64_t* bi = s.alloc<uint64_t>(nq * kk);
+  uint32_t* bn = s.alloc<uint32_t>(nq);
   if (!bd || !bi || !bn) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
   ISL_HIP(hipMemsetAsync(bn, 0, nq * 4, st));
   if (n && k && d) {
@@ -362,9 +351,9 @@ isl_status isl_bruteforce_topk(int32_t metric, const float* queries, uint64_t nq
     ISL_TRY(stage_matrix(s, rows, n, d, mem, st, &dr, &ldr));
     // column chunks sized so that the distance block stays near 1 GiB
     const uint64_t chunk = std::max<uint64_t>(4096, std::min<uint64_t>(n, (1ull << 28) / std::max<uint64_t>(nq, 1)));
-    float* qn = (float*)s.alloc(nq * 4);
-    float* rn = (float*)s.alloc(n * 4);
-    float* blk = (float*)s.alloc(nq * chunk * 4);
+    float* qn = s.alloc<float>(nq);
+    float* rn = s.alloc<float>(n);
+    float* blk = s.alloc<float>(nq * chunk);
     if (!qn || !rn || !blk) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     hipLaunchKernelGGL(sumsq_rows_kernel, dim3((uint32_t)((nq + 3) / 4)), dim3(256), 0, st, dq, nq, (uint32_t)d, ldq, qn);
     for (uint64_t r0 = 0; r0 < n; r0 += 0x7FFFFFFCull)  // grid.x limit (four rows per workgroup)
@@ -404,18 +393,18 @@ isl_status isl_bruteforce_topk_bf16(int32_t metric, const uint16_t* queries, uin
   if (d % 64) return isl::fail(ISL_ERR_UNSUPPORTED, "bf16 distance matrix: the dimension must be a multiple of 64");
   ISL_TRY(isl::use_device(device));
   hipStream_t st = (hipStream_t)stream;
-  Staged s;
+  isl::TempScope s;
   const uint64_t kk = k ? k : 1;
-  float* bd = (float*)s.alloc(nq * kk * 4);
-  uint64_t* bi = (uint64_t*)s.alloc(nq * kk * 8);
-  uint32_t* bn = (uint32_t*)s.alloc(nq * 4);
+  float* bd = s.alloc<float>(nq * kk);
+  uint64_t* bi = s.alloc<uint64_t>(nq * kk);
+  uint32_t* bn = s.alloc<uint32_t>(nq);
   if (!bd || !bi || !bn) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
   ISL_HIP(hipMemsetAsync(bn, 0, nq * 4, st));
   if (n && k) {
     const uint16_t *dq = queries, *dr = rows;
     if (mem == ISL_MEM_HOST) {
-      uint16_t* a = (uint16_t*)s.alloc(nq * d * 2);
-      uint16_t* b = (uint16_t*)s.alloc(n * d * 2);
+      uint16_t* a = s.alloc<uint16_t>(nq * d);
+      uint16_t* b = s.alloc<uint16_t>(n * d);
       if (!a || !b) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
       ISL_HIP(hipMemcpyAsync(a, queries, nq * d * 2, hipMemcpyHostToDevice, st));
       ISL_HIP(hipMemcpyAsync(b, rows, n * d * 2, hipMemcpyHostToDevice, st));
@@ -428,9 +417,9 @@ isl_status isl_bruteforce_topk_bf16(int32_t metric, const uint16_t* queries, uin
     // GEMM's tile, and the top-k scan's 16-byte loads stay aligned in every row)
     const uint64_t chunk = std::max<uint64_t>(4096, std::min<uint64_t>((n + 255) / 256 * 256,
                                                                       ((1ull << 28) / std::max<uint64_t>(nq, 1)) / 256 * 256));
-    float* qn = (float*)s.alloc(nq * 4);
-    float* rn = (float*)s.alloc(n * 4);
-    float* blk = (float*)s.alloc(nq * chunk * 4);
+    float* qn = s.alloc<float>(nq);
+    float* rn = s.alloc<float>(n);
+    float* blk = s.alloc<float>(nq * chunk);
     if (!qn || !rn || !blk) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     if (metric != ISL_METRIC_DOT) {
       hipLaunchKernelGGL(sumsq_rows_bf16_kernel, dim3((uint32_t)((nq + 3) / 4)), dim3(256), 0, st, dq, nq, (uint32_t)d, qn);

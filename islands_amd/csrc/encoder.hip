@@ -355,32 +355,26 @@ __global__ __launch_bounds__(64) void pool_kernel(const float* __restrict__ hid,
   }
 }
 
-// the buffers one model pass works in: the encoder's own, or its side set
-struct EncWs {
-  float *x, *x1, *t, *qkv, *ctx, *inter;
-  void *x16, *x1_16;
-  float* d_mask;
-  int64_t *d_ids, *d_tt;
-  uint32_t* d_flag;
-};
-EncWs main_ws(const isl_encoder* e) {
-  return EncWs{e->x, e->x1, e->t, e->qkv, e->ctx, e->inter, e->x16, e->x1_16, e->d_mask, e->d_ids, e->d_tt, e->d_flag};
-}
-EncWs side_ws(const isl_encoder* e) {
-  const auto& s = e->side;
-  return EncWs{s.x, s.x1, s.t, s.qkv, s.ctx, s.inter, s.x16, s.x1_16, s.d_mask, s.d_ids, s.d_tt, s.d_flag};
-}
+using EncWs = isl_encoder::Workspace;
 
-void free_side(isl_encoder* e) {
-  auto& s = e->side;
-  void* olds[] = {s.x, s.x1, s.t, s.qkv, s.ctx, s.inter, s.d_mask, s.d_ids, s.d_tt, s.x16, s.x1_16};
-  for (void* p : olds)
-    if (p) (void)hipFree(p);
-  s.x = s.x1 = s.t = s.qkv = s.ctx = s.inter = s.d_mask = nullptr;
-  s.x16 = s.x1_16 = nullptr;
-  s.d_ids = s.d_tt = nullptr;
-  s.ws_tokens = 0;
+// a workspace (`which`: "" = the encoder's own, "'s side") for B sequences of padded length L
+isl_status ensure_ws(isl_encoder* e, EncWs& w, const char* which, uint64_t B, uint64_t L) {
+  const uint64_t tokens = B * L;
+  if (tokens <= w.tokens) return ISL_OK;
+  w = EncWs{};  // the old arrays go before the new ones are allocated
+  const uint64_t h = e->cfg.hidden, I = e->cfg.intermediate;
+  if (w.x.reserve(tokens * h) != ISL_OK || w.x1.reserve(tokens * h) != ISL_OK || w.t.reserve(tokens * h) != ISL_OK ||
+      w.qkv.reserve(tokens * 3 * h) != ISL_OK || w.ctx.reserve(tokens * h) != ISL_OK ||
+      w.inter.reserve(tokens * I) != ISL_OK || w.d_mask.reserve(tokens) != ISL_OK || w.d_ids.reserve(tokens) != ISL_OK ||
+      w.d_tt.reserve(tokens) != ISL_OK || w.x16.reserve(tokens * h) != ISL_OK || w.x1_16.reserve(tokens * h) != ISL_OK) {
+    w = EncWs{};
+    return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed for the encoder%s workspace (%llu tokens)", which,
+                     (unsigned long long)tokens);
+  }
+  w.tokens = tokens;
+  return ISL_OK;
 }
+isl_status ensure_ws(isl_encoder* e, uint64_t B, uint64_t L) { return ensure_ws(e, e->ws, "", B, L); }
 
 // the side workspace for B sequences of padded length L, its stream and its two events
 isl_status ensure_side(isl_encoder* e, uint64_t B, uint64_t L) {
@@ -392,46 +386,8 @@ isl_status ensure_side(isl_encoder* e, uint64_t B, uint64_t L) {
   }
   if (!s.ev_in) { hipEvent_t ev = nullptr; ISL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); s.ev_in = ev; }
   if (!s.ev_out) { hipEvent_t ev = nullptr; ISL_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); s.ev_out = ev; }
-  if (!s.d_flag && hipMalloc(&s.d_flag, 4) != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
-  const uint64_t tokens = B * L;
-  if (tokens <= s.ws_tokens) return ISL_OK;
-  free_side(e);
-  const uint64_t h = e->cfg.hidden, I = e->cfg.intermediate;
-  if (hipMalloc(&s.x, tokens * h * 4) != hipSuccess || hipMalloc(&s.x1, tokens * h * 4) != hipSuccess ||
-      hipMalloc(&s.t, tokens * h * 4) != hipSuccess || hipMalloc(&s.qkv, tokens * 3 * h * 4) != hipSuccess ||
-      hipMalloc(&s.ctx, tokens * h * 4) != hipSuccess || hipMalloc(&s.inter, tokens * I * 4) != hipSuccess ||
-      hipMalloc(&s.d_mask, tokens * 4) != hipSuccess || hipMalloc(&s.d_ids, tokens * 8) != hipSuccess ||
-      hipMalloc(&s.d_tt, tokens * 8) != hipSuccess || hipMalloc(&s.x16, tokens * h * 2) != hipSuccess ||
-      hipMalloc(&s.x1_16, tokens * h * 2) != hipSuccess) {
-    free_side(e);
-    return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed for the encoder's side workspace (%llu tokens)",
-                     (unsigned long long)tokens);
-  }
-  s.ws_tokens = tokens;
-  return ISL_OK;
-}
-
-isl_status ensure_ws(isl_encoder* e, uint64_t B, uint64_t L) {
-  const uint64_t tokens = B * L;
-  if (tokens <= e->ws_tokens) return ISL_OK;
-  void* olds[] = {e->x, e->x1, e->t, e->qkv, e->ctx, e->inter, e->d_mask, e->d_ids, e->d_tt, e->x16, e->x1_16};
-  for (void* p : olds)
-    if (p) (void)hipFree(p);
-  e->x = e->x1 = e->t = e->qkv = e->ctx = e->inter = e->d_mask = nullptr;
-  e->x16 = e->x1_16 = nullptr;
-  e->d_ids = e->d_tt = nullptr;
-  e->ws_tokens = 0;
-  const uint64_t h = e->cfg.hidden, I = e->cfg.intermediate;
-  if (hipMalloc(&e->x, tokens * h * 4) != hipSuccess || hipMalloc(&e->x1, tokens * h * 4) != hipSuccess ||
-      hipMalloc(&e->t, tokens * h * 4) != hipSuccess || hipMalloc(&e->qkv, tokens * 3 * h * 4) != hipSuccess ||
-      hipMalloc(&e->ctx, tokens * h * 4) != hipSuccess || hipMalloc(&e->inter, tokens * I * 4) != hipSuccess ||
-      hipMalloc(&e->d_mask, tokens * 4) != hipSuccess || hipMalloc(&e->d_ids, tokens * 8) != hipSuccess ||
-      hipMalloc(&e->d_tt, tokens * 8) != hipSuccess || hipMalloc(&e->x16, tokens * h * 2) != hipSuccess ||
-      hipMalloc(&e->x1_16, tokens * h * 2) != hipSuccess)
-    return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed for the encoder workspace (%llu tokens)",
-                     (unsigned long long)tokens);
-  e->ws_tokens = tokens;
-  return ISL_OK;
+  if (s.d_flag.reserve(1) != ISL_OK) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
+  return ensure_ws(e, s.ws, "'s side", B, L);
 }
 
 __global__ void fill_f32(float* p, uint64_t n, float v) {
@@ -441,26 +397,27 @@ __global__ void fill_f32(float* p, uint64_t n, float v) {
 
 // The model on B sequences of padded length L whose ids / types / mask already sit in the
 // workspace (w.d_ids, w.d_tt when has_tt, w.d_mask); the last hidden state is left in w.x.
-isl_status compute_forward(isl_encoder* enc, const EncWs& w, bool has_tt, uint64_t B, uint64_t L, hipStream_t st) {
+isl_status compute_forward(isl_encoder* enc, const EncWs& w, uint32_t* d_flag, bool has_tt, uint64_t B, uint64_t L,
+                           hipStream_t st) {
   const EncWs* e = &w;  // (the body below reads its buffers through `e`)
   const isl_bert_config& c = enc->cfg;
   const uint64_t M = B * L, h = c.hidden, I = c.intermediate;
-  ISL_HIP(hipMemsetAsync(e->d_flag, 0, 4, st));
+  ISL_HIP(hipMemsetAsync(d_flag, 0, 4, st));
   const uint32_t dh = c.hidden / c.heads;
   static const bool valu_attention = getenv("ISL_ATTENTION_VALU") != nullptr;
   // bf16 mode: every GEMM input is kept as a bf16 copy written by its producer (LayerNorm,
   // attention, the GELU epilogue); ctx and inter only exist in bf16 then (in their f32 buffers)
   const bool half = enc->precision == ISL_DTYPE_BF16 && !enc->layers16.empty() && h % 8 == 0 && I % 8 == 0 &&
                     (dh == 64 || dh == 32) && !valu_attention;
-  __bf16* x16 = half ? reinterpret_cast<__bf16*>(e->x16) : nullptr;
-  __bf16* x1_16 = half ? reinterpret_cast<__bf16*>(e->x1_16) : nullptr;
-  __bf16* ctx16 = half ? reinterpret_cast<__bf16*>(e->ctx) : nullptr;
+  __bf16* x16 = half ? reinterpret_cast<__bf16*>(e->x16.get()) : nullptr;
+  __bf16* x1_16 = half ? reinterpret_cast<__bf16*>(e->x1_16.get()) : nullptr;
+  __bf16* ctx16 = half ? reinterpret_cast<__bf16*>(e->ctx.get()) : nullptr;
   hipLaunchKernelGGL(embed_ln_kernel, dim3((uint32_t)M), dim3(64), h * 4, st, e->d_ids,
                      has_tt ? e->d_tt : nullptr, (uint32_t)L, (uint32_t)h, c.vocab_size, c.type_vocab,
-                     enc->word, enc->pos, enc->type, enc->eln_w, enc->eln_b, c.layer_norm_eps, e->x, e->d_flag, x16);
+                     enc->word, enc->pos, enc->type, enc->eln_w, enc->eln_b, c.layer_norm_eps, e->x, d_flag, x16);
   for (size_t li = 0; li < enc->layers.size(); ++li) {
     const auto& ly = enc->layers[li];
-    if (half) launch_gemm_bf16<0, false, true, false>(x16, (const __bf16*)enc->layers16[li].wqkv, ly.bqkv, nullptr, e->qkv, M, 3 * h, h, st);
+    if (half) launch_gemm_bf16<0, false, true, false>(x16, (const __bf16*)enc->layers16[li].wqkv.get(), ly.bqkv, nullptr, e->qkv, M, 3 * h, h, st);
     else launch_gemm<0, false>(e->x, ly.wqkv, ly.bqkv, nullptr, e->qkv, M, 3 * h, h, st);
     dim3 ag((uint32_t)(B * c.heads), (uint32_t)((L + 63) / 64));
     if (dh == 64 && !valu_attention) hipLaunchKernelGGL(attention_mfma_kernel<64>, ag, dim3(64), 0, st, e->qkv, e->d_mask, (uint32_t)L, c.heads, e->ctx, ctx16);
@@ -468,13 +425,13 @@ isl_status compute_forward(isl_encoder* enc, const EncWs& w, bool has_tt, uint64
     else if (dh == 64) hipLaunchKernelGGL(attention_kernel<64>, ag, dim3(64), 0, st, e->qkv, e->d_mask, (uint32_t)L, c.heads, e->ctx);
     else if (dh == 32) hipLaunchKernelGGL(attention_kernel<32>, ag, dim3(64), 0, st, e->qkv, e->d_mask, (uint32_t)L, c.heads, e->ctx);
     else hipLaunchKernelGGL(attention_kernel<16>, ag, dim3(64), 0, st, e->qkv, e->d_mask, (uint32_t)L, c.heads, e->ctx);
-    if (half) launch_gemm_bf16<0, true, true, false>(ctx16, (const __bf16*)enc->layers16[li].wo, ly.bo, e->x, e->t, M, h, h, st);
+    if (half) launch_gemm_bf16<0, true, true, false>(ctx16, (const __bf16*)enc->layers16[li].wo.get(), ly.bo, e->x, e->t, M, h, h, st);
     else launch_gemm<0, true>(e->ctx, ly.wo, ly.bo, e->x, e->t, M, h, h, st);
     hipLaunchKernelGGL(ln_kernel, dim3((uint32_t)M), dim3(64), h * 4, st, e->t, (uint32_t)h, ly.ln1w, ly.ln1b, c.layer_norm_eps, e->x1, x1_16);
     if (half) {
-      if (c.gelu_tanh) launch_gemm_bf16<2, false, true, true>(x1_16, (const __bf16*)enc->layers16[li].wi, ly.bi, nullptr, e->inter, M, I, h, st);
-      else launch_gemm_bf16<1, false, true, true>(x1_16, (const __bf16*)enc->layers16[li].wi, ly.bi, nullptr, e->inter, M, I, h, st);
-      launch_gemm_bf16<0, true, true, false>(e->inter, (const __bf16*)enc->layers16[li].wo2, ly.bo2, e->x1, e->t, M, h, I, st);
+      if (c.gelu_tanh) launch_gemm_bf16<2, false, true, true>(x1_16, (const __bf16*)enc->layers16[li].wi.get(), ly.bi, nullptr, e->inter, M, I, h, st);
+      else launch_gemm_bf16<1, false, true, true>(x1_16, (const __bf16*)enc->layers16[li].wi.get(), ly.bi, nullptr, e->inter, M, I, h, st);
+      launch_gemm_bf16<0, true, true, false>(e->inter, (const __bf16*)enc->layers16[li].wo2.get(), ly.bo2, e->x1, e->t, M, h, I, st);
     } else {
       if (c.gelu_tanh) launch_gemm<2, false>(e->x1, ly.wi, ly.bi, nullptr, e->inter, M, I, h, st);
       else launch_gemm<1, false>(e->x1, ly.wi, ly.bi, nullptr, e->inter, M, I, h, st);
@@ -495,11 +452,11 @@ isl_status run_forward(isl_encoder* e, const int64_t* ids, const int64_t* tt, co
   ISL_TRY(ensure_ws(e, B, L));
   const uint64_t M = B * L;
   hipMemcpyKind kind = mem == ISL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  ISL_HIP(hipMemcpyAsync(e->d_ids, ids, M * 8, kind, st));
-  if (tt) ISL_HIP(hipMemcpyAsync(e->d_tt, tt, M * 8, kind, st));
-  if (mask) ISL_HIP(hipMemcpyAsync(e->d_mask, mask, M * 4, kind, st));
-  else hipLaunchKernelGGL(fill_f32, dim3((uint32_t)((M + 255) / 256)), dim3(256), 0, st, e->d_mask, M, 1.0f);
-  return compute_forward(e, main_ws(e), tt != nullptr, B, L, st);
+  ISL_HIP(hipMemcpyAsync(e->ws.d_ids, ids, M * 8, kind, st));
+  if (tt) ISL_HIP(hipMemcpyAsync(e->ws.d_tt, tt, M * 8, kind, st));
+  if (mask) ISL_HIP(hipMemcpyAsync(e->ws.d_mask, mask, M * 4, kind, st));
+  else hipLaunchKernelGGL(fill_f32, dim3((uint32_t)((M + 255) / 256)), dim3(256), 0, st, e->ws.d_mask.get(), M, 1.0f);
+  return compute_forward(e, e->ws, e->d_flag, tt != nullptr, B, L, st);
 }
 
 // token table row -> the int64 ids / f32 mask the model kernels read
@@ -568,11 +525,11 @@ isl_status encoder_embed_nodes(isl_encoder* e, const uint16_t* d_tokens, const u
   // this stays a switch (read per call).
   const char* se = getenv("ISL_ENCODER_SPLIT");
   const uint64_t split_min = se ? (uint64_t)std::max(0, atoi(se)) : 0;  // 0 = never
-  auto half = [&](const EncWs& w, uint64_t o, uint64_t B, hipStream_t s) -> isl_status {
+  auto half = [&](const EncWs& w, uint32_t* d_flag, uint64_t o, uint64_t B, hipStream_t s) -> isl_status {
     hipLaunchKernelGGL(gather_tokens_kernel, dim3((uint32_t)((B * L + 255) / 256)), dim3(256), 0, s, d_tokens,
-                       d_lens, L, d_node_ids + o, B, w.d_ids, w.d_mask);
-    ISL_TRY(compute_forward(e, w, false, B, L, s));
-    hipLaunchKernelGGL(pool_kernel, dim3((uint32_t)B), dim3(64), 0, s, w.x, w.d_mask, L,
+                       d_lens, L, d_node_ids + o, B, w.d_ids.get(), w.d_mask.get());
+    ISL_TRY(compute_forward(e, w, d_flag, false, B, L, s));
+    hipLaunchKernelGGL(pool_kernel, dim3((uint32_t)B), dim3(64), 0, s, w.x.get(), w.d_mask.get(), L,
                        (uint32_t)e->cfg.hidden, normalize, d_rows, d_out_rows + o, stride);
     ISL_HIP(hipGetLastError());
     return ISL_OK;
@@ -586,15 +543,15 @@ isl_status encoder_embed_nodes(isl_encoder* e, const uint16_t* d_tokens, const u
       hipStream_t side = (hipStream_t)e->side.stream;
       ISL_HIP(hipEventRecord((hipEvent_t)e->side.ev_in, st));     // what the caller enqueued so far (the node lists)
       ISL_HIP(hipStreamWaitEvent(side, (hipEvent_t)e->side.ev_in, 0));
-      isl_status rc = half(side_ws(e), o + B0, B1, side);
-      if (rc == ISL_OK) rc = half(main_ws(e), o, B0, st);
+      isl_status rc = half(e->side.ws, e->side.d_flag, o + B0, B1, side);
+      if (rc == ISL_OK) rc = half(e->ws, e->d_flag, o, B0, st);
       (void)hipEventRecord((hipEvent_t)e->side.ev_out, side);     // joined whatever happened: nothing stays behind on the side stream
       (void)hipStreamWaitEvent(st, (hipEvent_t)e->side.ev_out, 0);
       if (rc != ISL_OK) { (void)hipStreamSynchronize(st); return rc; }
       ISL_TRY(check_ids_flag(e, st, true));
     } else {
       ISL_TRY(ensure_ws(e, std::min(n, chunk), L));
-      ISL_TRY(half(main_ws(e), o, B, st));
+      ISL_TRY(half(e->ws, e->d_flag, o, B, st));
       ISL_TRY(check_ids_flag(e, st));
     }
   }
@@ -608,17 +565,11 @@ void isl_encoder_free(isl_encoder* e) {
   if (!e) return;
   if (e->device >= 0) {
     (void)hipSetDevice(e->device);
-    for (void* p : e->owned) (void)hipFree(p);
-    void* ws[] = {e->x, e->x1, e->t, e->qkv, e->ctx, e->inter, e->d_mask, e->d_ids, e->d_tt, e->d_flag, e->x16, e->x1_16};
-    for (void* p : ws)
-      if (p) (void)hipFree(p);
-    free_side(e);
-    if (e->side.d_flag) (void)hipFree(e->side.d_flag);
     if (e->side.ev_in) (void)hipEventDestroy((hipEvent_t)e->side.ev_in);
     if (e->side.ev_out) (void)hipEventDestroy((hipEvent_t)e->side.ev_out);
     if (e->side.stream) (void)hipStreamDestroy((hipStream_t)e->side.stream);
   }
-  delete e;
+  delete e;  // weights and workspaces are members that free themselves
 }
 
 isl_status isl_encoder_new(const isl_bert_config* cfg, int32_t device, isl_encoder** out) {
@@ -638,28 +589,25 @@ isl_status isl_encoder_new(const isl_bert_config* cfg, int32_t device, isl_encod
   e->cfg = c;
   e->device = device;
   bool ok = true;
-  auto alloc = [&](uint64_t n) -> float* {
-    void* p = nullptr;
-    if (hipMalloc(&p, n * 4) != hipSuccess || hipMemset(p, 0, n * 4) != hipSuccess) { ok = false; return nullptr; }
-    e->owned.push_back(p);
-    return (float*)p;
+  auto alloc = [&](isl::DeviceBuffer<float>& w, uint64_t n) {  // zeros until the weight is set
+    if (w.reserve(n) != ISL_OK || hipMemset(w, 0, n * 4) != hipSuccess) ok = false;
   };
   const uint64_t h = c.hidden, I = c.intermediate;
-  e->word = alloc((uint64_t)c.vocab_size * h);
-  e->pos = alloc((uint64_t)c.max_position * h);
-  e->type = alloc((uint64_t)c.type_vocab * h);
-  e->eln_w = alloc(h);
-  e->eln_b = alloc(h);
+  alloc(e->word, (uint64_t)c.vocab_size * h);
+  alloc(e->pos, (uint64_t)c.max_position * h);
+  alloc(e->type, (uint64_t)c.type_vocab * h);
+  alloc(e->eln_w, h);
+  alloc(e->eln_b, h);
   e->layers.resize(c.layers);
   for (auto& ly : e->layers) {
-    ly.wqkv = alloc(3 * h * h); ly.bqkv = alloc(3 * h);
-    ly.wo = alloc(h * h); ly.bo = alloc(h);
-    ly.ln1w = alloc(h); ly.ln1b = alloc(h);
-    ly.wi = alloc(I * h); ly.bi = alloc(I);
-    ly.wo2 = alloc(h * I); ly.bo2 = alloc(h);
-    ly.ln2w = alloc(h); ly.ln2b = alloc(h);
+    alloc(ly.wqkv, 3 * h * h); alloc(ly.bqkv, 3 * h);
+    alloc(ly.wo, h * h); alloc(ly.bo, h);
+    alloc(ly.ln1w, h); alloc(ly.ln1b, h);
+    alloc(ly.wi, I * h); alloc(ly.bi, I);
+    alloc(ly.wo2, h * I); alloc(ly.bo2, h);
+    alloc(ly.ln2w, h); alloc(ly.ln2b, h);
   }
-  if (ok && hipMalloc(&e->d_flag, 4) != hipSuccess) ok = false;
+  if (ok && e->d_flag.reserve(1) != ISL_OK) ok = false;
   if (!ok) {
     isl_encoder_free(e);
     return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed for the encoder weights");
@@ -731,14 +679,12 @@ isl_status isl_encoder_set_precision(isl_encoder* e, int32_t dtype) {
     for (size_t li = 0; li < e->layers.size(); ++li) {
       const float* src[4] = {e->layers[li].wqkv, e->layers[li].wo, e->layers[li].wi, e->layers[li].wo2};
       const uint64_t cnt[4] = {3 * h * h, h * h, I * h, h * I};
-      void** dst[4] = {&e->layers16[li].wqkv, &e->layers16[li].wo, &e->layers16[li].wi, &e->layers16[li].wo2};
+      isl::DeviceBuffer<uint16_t>* dst[4] = {&e->layers16[li].wqkv, &e->layers16[li].wo, &e->layers16[li].wi,
+                                             &e->layers16[li].wo2};
       for (int t = 0; t < 4; ++t) {
-        if (!*dst[t]) {
-          ISL_HIP(hipMalloc(dst[t], cnt[t] * 2));
-          e->owned.push_back(*dst[t]);
-        }
+        ISL_TRY(dst[t]->reserve(cnt[t]));
         hipLaunchKernelGGL(f32_to_bf16_kernel, dim3((uint32_t)((cnt[t] + 255) / 256)), dim3(256), 0, 0, src[t],
-                           (__bf16*)*dst[t], cnt[t]);
+                           (__bf16*)dst[t]->get(), cnt[t]);
       }
     }
     ISL_HIP(hipGetLastError());
@@ -757,7 +703,7 @@ isl_status isl_encoder_forward(isl_encoder* e, const int64_t* input_ids, const i
   std::lock_guard<std::mutex> lock(e->mu);
   hipStream_t st = (hipStream_t)stream;
   ISL_TRY(run_forward(e, input_ids, token_type_ids, attention_mask, B, L, mem, st));
-  ISL_HIP(hipMemcpyAsync(out_hidden, e->x, B * L * e->cfg.hidden * 4,
+  ISL_HIP(hipMemcpyAsync(out_hidden, e->ws.x, B * L * e->cfg.hidden * 4,
                          mem == ISL_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, st));
   return check_ids_flag(e, st);
 }
@@ -774,8 +720,8 @@ isl_status isl_encoder_embed(isl_encoder* e, const int64_t* input_ids, const int
   ISL_TRY(run_forward(e, input_ids, token_type_ids, attention_mask, B, L, mem, st));
   const uint64_t h = e->cfg.hidden;
   float* d_out = out;
-  if (mem == ISL_MEM_HOST) d_out = e->t;  // B*h <= tokens*h
-  hipLaunchKernelGGL(pool_kernel, dim3((uint32_t)B), dim3(64), 0, st, e->x, e->d_mask, (uint32_t)L, (uint32_t)h,
+  if (mem == ISL_MEM_HOST) d_out = e->ws.t;  // B*h <= tokens*h
+  hipLaunchKernelGGL(pool_kernel, dim3((uint32_t)B), dim3(64), 0, st, e->ws.x.get(), e->ws.d_mask.get(), (uint32_t)L, (uint32_t)h,
                      normalize, d_out, (const uint32_t*)nullptr, h);
   ISL_HIP(hipGetLastError());
   if (mem == ISL_MEM_HOST) ISL_HIP(hipMemcpyAsync(out, d_out, B * h * 4, hipMemcpyDeviceToHost, st));

@@ -7,35 +7,30 @@
 struct isl_encoder {
   isl_bert_config cfg{};
   int device = -1;
-  float *word = nullptr, *pos = nullptr, *type = nullptr, *eln_w = nullptr, *eln_b = nullptr;
+  isl::DeviceBuffer<float> word, pos, type, eln_w, eln_b;
   struct Layer {
-    float *wqkv = nullptr, *bqkv = nullptr, *wo = nullptr, *bo = nullptr, *ln1w = nullptr,
-          *ln1b = nullptr, *wi = nullptr, *bi = nullptr, *wo2 = nullptr, *bo2 = nullptr,
-          *ln2w = nullptr, *ln2b = nullptr;
+    isl::DeviceBuffer<float> wqkv, bqkv, wo, bo, ln1w, ln1b, wi, bi, wo2, bo2, ln2w, ln2b;
   };
   std::vector<Layer> layers;
   // optional reduced-precision mode: bf16 copies of the Linear weights (same order as `layers`)
-  struct Layer16 { void *wqkv = nullptr, *wo = nullptr, *wi = nullptr, *wo2 = nullptr; };
+  struct Layer16 { isl::DeviceBuffer<uint16_t> wqkv, wo, wi, wo2; };
   std::vector<Layer16> layers16;
   int32_t precision = 0;  // ISL_DTYPE_F32 / ISL_DTYPE_BF16
-  std::vector<void*> owned;
-  // workspace, grown on demand (tokens = sequences * padded length)
-  uint64_t ws_tokens = 0;
-  float *x = nullptr, *x1 = nullptr, *t = nullptr, *qkv = nullptr, *ctx = nullptr, *inter = nullptr;
-  void *x16 = nullptr, *x1_16 = nullptr;  // bf16 copies of x / x1 (bf16 mode)
-  float* d_mask = nullptr;
-  int64_t *d_ids = nullptr, *d_tt = nullptr;
-  uint32_t* d_flag = nullptr;
+  // the buffers one model pass works in, grown on demand (tokens = sequences * padded length)
+  struct Workspace {
+    uint64_t tokens = 0;
+    isl::DeviceBuffer<float> x, x1, t, qkv, ctx, inter;
+    isl::DeviceBuffer<uint16_t> x16, x1_16;  // bf16 copies of x / x1 (bf16 mode)
+    isl::DeviceBuffer<float> d_mask;
+    isl::DeviceBuffer<int64_t> d_ids, d_tt;
+  } ws;
+  isl::DeviceBuffer<uint32_t> d_flag;  // an id out of range was met in a pass over ws
   // second workspace + stream (round 4): encoder_embed_nodes runs the two halves of a batch side by side,
   // so that one half's last, partly filled wave of GEMM tiles and its LayerNorm / attention kernels lie
   // beside the other half's GEMMs (a sequence's embedding does not depend on what it is batched with)
   struct Side {
-    uint64_t ws_tokens = 0;
-    float *x = nullptr, *x1 = nullptr, *t = nullptr, *qkv = nullptr, *ctx = nullptr, *inter = nullptr;
-    void *x16 = nullptr, *x1_16 = nullptr;
-    float* d_mask = nullptr;
-    int64_t *d_ids = nullptr, *d_tt = nullptr;
-    uint32_t* d_flag = nullptr;
+    Workspace ws;
+    isl::DeviceBuffer<uint32_t> d_flag;
     void* stream = nullptr;   // hipStream_t (non-blocking)
     void* ev_in = nullptr;    // hipEvent_t: the caller's stream up to the call
     void* ev_out = nullptr;   // hipEvent_t: the side stream's half is done

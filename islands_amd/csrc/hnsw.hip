@@ -81,9 +81,9 @@ isl_status isl::attach_upper_layers(isl_hnsw* h, const std::vector<const uint64_
                                     const std::vector<const uint32_t*>& adjs) {
   isl_index* c = h->core;
   const size_t bytes = offs.size() * sizeof(void*);
-  if (hipMalloc((void**)&c->d_layer_off, bytes) != hipSuccess || hipMalloc((void**)&c->d_layer_adj, bytes) != hipSuccess ||
-      hipMemcpy((void*)c->d_layer_off, offs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy((void*)c->d_layer_adj, adjs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+  if (c->d_layer_off.reserve(offs.size()) != ISL_OK || c->d_layer_adj.reserve(offs.size()) != ISL_OK ||
+      hipMemcpy(c->d_layer_off, offs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->d_layer_adj, adjs.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
     return fail(ISL_ERR_DEVICE, "layer table upload failed");
   c->hnsw_layers = offs.size();
   h->layer_off = offs;
@@ -139,29 +139,27 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
   isl_index* c = h->core;
   std::vector<const uint64_t*> offs(max_level + 1, nullptr);
   std::vector<const uint32_t*> adjs(max_level + 1, nullptr);
-  uint32_t* d_flag = nullptr;
-  if (hipMalloc(&d_flag, 4) != hipSuccess || hipMemset(d_flag, 0, 4) != hipSuccess)
+  isl::DeviceBuffer<uint32_t> d_flag;
+  if (d_flag.reserve(1) != ISL_OK || hipMemset(d_flag, 0, 4) != hipSuccess)
     return bail(isl::fail(ISL_ERR_DEVICE, "hipMalloc failed"));
-  c->hnsw_owned.push_back(d_flag);
   for (uint64_t L = 1; L <= max_level; ++L) {
     const uint64_t* off = layer_offsets[L];
     uint64_t nnz = off[num_nodes];
-    uint64_t* d_off = nullptr;
-    uint32_t* d_adj = nullptr;
-    uint64_t* d_tmp = nullptr;
-    if (hipMalloc(&d_off, (num_nodes + 1) * 8) != hipSuccess ||
-        hipMalloc(&d_adj, (nnz ? nnz : 1) * 4) != hipSuccess ||
-        hipMalloc(&d_tmp, (nnz ? nnz : 1) * 8) != hipSuccess)
+    auto layer_array = [&](uint64_t bytes) -> void* {  // owned by the index from the start
+      auto& b = c->hnsw_owned.emplace_back();
+      return b.reserve(bytes) == ISL_OK ? b.get() : nullptr;
+    };
+    uint64_t* d_off = static_cast<uint64_t*>(layer_array((num_nodes + 1) * 8));
+    uint32_t* d_adj = static_cast<uint32_t*>(layer_array((nnz ? nnz : 1) * 4));
+    isl::DeviceBuffer<uint64_t> d_tmp;
+    if (!d_off || !d_adj || d_tmp.reserve(nnz ? nnz : 1) != ISL_OK)
       return bail(isl::fail(ISL_ERR_DEVICE, "hipMalloc failed for layer %llu", (unsigned long long)L));
-    c->hnsw_owned.push_back(d_off);
-    c->hnsw_owned.push_back(d_adj);
     hipError_t e = hipMemcpy(d_off, off, (num_nodes + 1) * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) e = hipMemcpy(d_tmp, layer_neighbors[L], nnz * 8, hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz) {
-      hipLaunchKernelGGL(hnsw_convert_adj, dim3(256), dim3(256), 0, 0, d_tmp, d_adj, nnz, d_flag);
+      hipLaunchKernelGGL(hnsw_convert_adj, dim3(256), dim3(256), 0, 0, d_tmp.get(), d_adj, nnz, d_flag.get());
       e = hipDeviceSynchronize();
     }
-    (void)hipFree(d_tmp);
     if (e != hipSuccess) return bail(isl::fail(ISL_ERR_DEVICE, "layer upload failed: %s", hipGetErrorString(e)));
     offs[L] = d_off;
     adjs[L] = d_adj;

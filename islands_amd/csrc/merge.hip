@@ -102,38 +102,28 @@ static isl_status merge_lists(uint32_t service, uint64_t nlists, uint64_t nq, ui
   uint64_t* d_oi = out_ids;
   float* d_os = out_scores;
   uint32_t *d_osrc = out_src, *d_oc = out_count, *d_flags = nullptr;
-  std::vector<void*> owned;
-  auto cleanup = [&]() { for (void* p : owned) (void)hipFree(p); };
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-    owned.push_back(p);
-    return p;
-  };
+  isl::TempScope tmp;
   hipError_t e = hipSuccess;
-  d_flags = (uint32_t*)dalloc(4);
-  if (!d_flags) { cleanup(); return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed"); }
+  d_flags = tmp.alloc<uint32_t>(1);
+  if (!d_flags) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
   e = hipMemsetAsync(d_flags, 0, 4, st);
-  void* tmp_base = nullptr;
   if (id_base) {  // id_base is always a host array (one entry per list)
-    tmp_base = dalloc(nlists * 8);
+    uint64_t* tmp_base = tmp.alloc<uint64_t>(nlists);
     if (tmp_base && e == hipSuccess)
       e = hipMemcpyAsync(tmp_base, id_base, nlists * 8, hipMemcpyHostToDevice, st);
-    d_base = (const uint64_t*)tmp_base;
+    d_base = tmp_base;
   }
   if (mem == ISL_MEM_HOST) {
-    void* a = dalloc(nin * 8); void* b = dalloc(nin * 4); void* c = dalloc(nlists * nq * 4);
-    void* oi = dalloc(nout * 8); void* os = dalloc(nout * 4); void* osrc = dalloc(nout * 4);
-    void* oc = dalloc(nq * 4);
-    if (!a || !b || !c || !oi || !os || !osrc || !oc) {
-      cleanup();
-      return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
-    }
+    uint64_t* a = tmp.alloc<uint64_t>(nin);
+    float* b = tmp.alloc<float>(nin);
+    uint32_t* c = tmp.alloc<uint32_t>(nlists * nq);
+    d_oi = tmp.alloc<uint64_t>(nout); d_os = tmp.alloc<float>(nout); d_osrc = tmp.alloc<uint32_t>(nout);
+    d_oc = tmp.alloc<uint32_t>(nq);
+    if (!a || !b || !c || !d_oi || !d_os || !d_osrc || !d_oc) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     if (e == hipSuccess) e = hipMemcpyAsync(a, ids, nin * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(b, scores, nin * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(c, counts, nlists * nq * 4, hipMemcpyHostToDevice, st);
-    d_ids = (const uint64_t*)a; d_sc = (const float*)b; d_cnt = (const uint32_t*)c;
-    d_oi = (uint64_t*)oi; d_os = (float*)os; d_osrc = (uint32_t*)osrc; d_oc = (uint32_t*)oc;
+    d_ids = a; d_sc = b; d_cnt = c;
   }
   if (e == hipSuccess) {
     uint32_t blocks = (uint32_t)((nq + 63) / 64);
@@ -154,7 +144,6 @@ static isl_status merge_lists(uint32_t service, uint64_t nlists, uint64_t nq, ui
     if (e == hipSuccess) e = hipMemcpyAsync(out_count, d_oc, nq * 4, hipMemcpyDeviceToHost, st);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
   if (e != hipSuccess)
     return isl::fail(ISL_ERR_DEVICE, "merge failed: %s", hipGetErrorString(e));
   if (flags & 1u)

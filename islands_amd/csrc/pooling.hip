@@ -44,19 +44,13 @@ extern "C" isl_status isl_mean_pool_normalize(const float* hidden, const float* 
   hipStream_t st = (hipStream_t)stream;
   const float *dh = hidden, *dm = mask;
   float* dout = out;
-  float *th = nullptr, *tm = nullptr, *to = nullptr;
-  auto cleanup = [&]() {
-    if (th) (void)hipFree(th);
-    if (tm) (void)hipFree(tm);
-    if (to) (void)hipFree(to);
-  };
+  isl::TempScope tmp;
   hipError_t e = hipSuccess;
   if (mem == ISL_MEM_HOST) {
-    if (hipMalloc(&th, B * L * H * 4 + 4) != hipSuccess || hipMalloc(&tm, B * L * 4 + 4) != hipSuccess ||
-        hipMalloc(&to, B * H * 4) != hipSuccess) {
-      cleanup();
-      return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed in isl_mean_pool_normalize");
-    }
+    float* th = tmp.alloc<float>(B * L * H + 1);
+    float* tm = tmp.alloc<float>(B * L + 1);
+    float* to = tmp.alloc<float>(B * H);
+    if (!th || !tm || !to) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed in isl_mean_pool_normalize");
     e = hipMemcpyAsync(th, hidden, B * L * H * 4, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(tm, mask, B * L * 4, hipMemcpyHostToDevice, st);
     dh = th; dm = tm; dout = to;
@@ -73,7 +67,6 @@ extern "C" isl_status isl_mean_pool_normalize(const float* hidden, const float* 
   if (e == hipSuccess && mem == ISL_MEM_HOST)
     e = hipMemcpyAsync(out, dout, B * H * 4, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
   if (e != hipSuccess)
     return isl::fail(ISL_ERR_DEVICE, "isl_mean_pool_normalize failed: %s", hipGetErrorString(e));
   return ISL_OK;

@@ -115,17 +115,6 @@ size_t pq_lds(uint32_t dsub) {
   return (size_t)TILE_ROWS * TILE_LD * 4 + (size_t)((dsub + 3) / 4 * 4) * 4 + 64;
 }
 
-struct Staged {
-  std::vector<void*> owned;
-  ~Staged() { for (void* p : owned) (void)hipFree(p); }
-  void* alloc(size_t bytes) {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-    owned.push_back(p);
-    return p;
-  }
-};
-
 isl_status launch_tables(const isl_pq* pq, const float* d_queries, uint64_t nq, float* d_tables,
                          hipStream_t st) {
   size_t lds = pq_lds((uint32_t)pq->dsub);
@@ -185,7 +174,7 @@ isl_status isl_pq_new(uint64_t dimension, uint64_t m, uint64_t K, const float* c
   pq->metric = metric;
   pq->device = device;
   size_t bytes = (size_t)(m * K * pq->cstride + 256) * 4;
-  if (hipMalloc(&pq->d_codebooks, bytes) != hipSuccess ||
+  if (pq->d_codebooks.reserve(m * K * pq->cstride + 256) != ISL_OK ||
       hipMemset(pq->d_codebooks, 0, bytes) != hipSuccess ||
       hipMemcpy2D(pq->d_codebooks, pq->cstride * 4, codebooks, pq->dsub * 4, pq->dsub * 4, m * K,
                   hipMemcpyHostToDevice) != hipSuccess) {
@@ -198,7 +187,6 @@ isl_status isl_pq_new(uint64_t dimension, uint64_t m, uint64_t K, const float* c
 
 void isl_pq_free(isl_pq* pq) {
   if (!pq) return;
-  if (pq->d_codebooks) (void)hipFree(pq->d_codebooks);
   delete pq;
 }
 
@@ -210,17 +198,16 @@ isl_status isl_pq_build_distance_tables(const isl_pq* pq, const float* queries, 
   if (!queries || !tables) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
   ISL_TRY(isl::use_device(pq->device));
   hipStream_t st = (hipStream_t)stream;
-  Staged sg;
+  isl::TempScope sg;
   const float* dq = queries;
   float* dt = tables;
   size_t tbytes = (size_t)nq * pq->m * pq->K * 4;
   if (mem == ISL_MEM_HOST) {
-    void* a = sg.alloc((size_t)nq * d * 4);
-    void* b = sg.alloc(tbytes);
-    if (!a || !b) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
+    float* a = sg.alloc<float>(nq * d);
+    dt = sg.alloc<float>(nq * pq->m * pq->K);
+    if (!a || !dt) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     ISL_HIP(hipMemcpyAsync(a, queries, (size_t)nq * d * 4, hipMemcpyHostToDevice, st));
-    dq = (const float*)a;
-    dt = (float*)b;
+    dq = a;
   }
   ISL_TRY(launch_tables(pq, dq, nq, dt, st));
   if (mem == ISL_MEM_HOST) ISL_HIP(hipMemcpyAsync(tables, dt, tbytes, hipMemcpyDeviceToHost, st));
@@ -231,18 +218,17 @@ isl_status isl_pq_build_distance_tables(const isl_pq* pq, const float* queries, 
 static isl_status table_distance_impl(const isl_pq* pq, const float* d_tables,
                                       const uint16_t* codes, uint64_t n, float* out, int32_t mem,
                                       hipStream_t st) {
-  Staged sg;
+  isl::TempScope sg;
   const uint16_t* dc = codes;
   float* dout = out;
   if (mem == ISL_MEM_HOST) {
-    void* a = sg.alloc((size_t)n * pq->m * 2);
-    void* b = sg.alloc((size_t)n * 4);
-    if (!a || !b) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
+    uint16_t* a = sg.alloc<uint16_t>(n * pq->m);
+    dout = sg.alloc<float>(n);
+    if (!a || !dout) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     ISL_HIP(hipMemcpyAsync(a, codes, (size_t)n * pq->m * 2, hipMemcpyHostToDevice, st));
-    dc = (const uint16_t*)a;
-    dout = (float*)b;
+    dc = a;
   }
-  uint32_t* d_flags = (uint32_t*)sg.alloc(4);
+  uint32_t* d_flags = sg.alloc<uint32_t>(1);
   if (!d_flags) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
   ISL_HIP(hipMemsetAsync(d_flags, 0, 4, st));
   uint32_t blocks = (uint32_t)((n + 255) / 256);
@@ -266,13 +252,13 @@ isl_status isl_pq_table_distance(const isl_pq* pq, const float* tables, const ui
   if (!tables || !codes || !out) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
   ISL_TRY(isl::use_device(pq->device));
   hipStream_t st = (hipStream_t)stream;
-  Staged sg;
+  isl::TempScope sg;
   const float* dt = tables;
   if (mem == ISL_MEM_HOST) {
-    void* a = sg.alloc((size_t)pq->m * pq->K * 4);
+    float* a = sg.alloc<float>(pq->m * pq->K);
     if (!a) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     ISL_HIP(hipMemcpyAsync(a, tables, (size_t)pq->m * pq->K * 4, hipMemcpyHostToDevice, st));
-    dt = (const float*)a;
+    dt = a;
   }
   return table_distance_impl(pq, dt, codes, n, out, mem, st);
 }
@@ -288,15 +274,15 @@ isl_status isl_pq_asymmetric_distance(const isl_pq* pq, const float* query, uint
   if (!query || !codes || !out) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
   ISL_TRY(isl::use_device(pq->device));
   hipStream_t st = (hipStream_t)stream;
-  Staged sg;
-  float* dt = (float*)sg.alloc((size_t)pq->m * pq->K * 4);
+  isl::TempScope sg;
+  float* dt = sg.alloc<float>(pq->m * pq->K);
   if (!dt) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
   const float* dq = query;
   if (mem == ISL_MEM_HOST) {
-    void* a = sg.alloc((size_t)d * 4);
+    float* a = sg.alloc<float>(d);
     if (!a) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     ISL_HIP(hipMemcpyAsync(a, query, (size_t)d * 4, hipMemcpyHostToDevice, st));
-    dq = (const float*)a;
+    dq = a;
   }
   ISL_TRY(launch_tables(pq, dq, 1, dt, st));
   return table_distance_impl(pq, dt, codes, n, out, mem, st);
@@ -310,16 +296,15 @@ isl_status isl_pq_encode(const isl_pq* pq, const float* vectors, uint64_t n, uin
   if (!vectors || !codes) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL buffer");
   ISL_TRY(isl::use_device(pq->device));
   hipStream_t st = (hipStream_t)stream;
-  Staged sg;
+  isl::TempScope sg;
   const float* dv = vectors;
   uint16_t* dc = codes;
   if (mem == ISL_MEM_HOST) {
-    void* a = sg.alloc((size_t)n * d * 4);
-    void* b = sg.alloc((size_t)n * pq->m * 2);
-    if (!a || !b) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
+    float* a = sg.alloc<float>(n * d);
+    dc = sg.alloc<uint16_t>(n * pq->m);
+    if (!a || !dc) return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed");
     ISL_HIP(hipMemcpyAsync(a, vectors, (size_t)n * d * 4, hipMemcpyHostToDevice, st));
-    dv = (const float*)a;
-    dc = (uint16_t*)b;
+    dv = a;
   }
   size_t lds = pq_lds((uint32_t)pq->dsub);
   for (uint64_t v0 = 0; v0 < n; v0 += 65535) {

@@ -73,32 +73,9 @@ constexpr uint32_t kExactSlots = 32;
 constexpr uint32_t kTlPrefetchDefault = 0;  // (set from the measurement: DESIGN.md section 3.4)
 constexpr uint32_t kOvfBits = 15;
 
-// Every allocation of the search path goes through these: a lane counts what it had to set up,
-// and a call reports its share in isl_search_stats::allocations (0 once isl_index_prepare has run).
-template <typename T>
-isl_status lane_malloc(isl::SearchWorkspace& ws, T*& ptr, size_t bytes) {
-  ptr = nullptr;
-  ISL_HIP(hipMalloc(&ptr, bytes ? bytes : 4));
-  ws.alloc_events++;
-  return ISL_OK;
-}
-template <typename T>
-isl_status lane_host_malloc(isl::SearchWorkspace& ws, T*& ptr, size_t bytes) {
-  ptr = nullptr;
-  ISL_HIP(hipHostMalloc(&ptr, bytes ? bytes : 4));
-  ws.alloc_events++;
-  return ISL_OK;
-}
-template <typename T>
-isl_status ensure(isl::SearchWorkspace& ws, T*& ptr, uint64_t& have, uint64_t want) {
-  if (have >= want && ptr) return ISL_OK;
-  if (ptr) (void)hipFree(ptr);
-  ptr = nullptr;
-  have = 0;
-  ISL_TRY(lane_malloc(ws, ptr, want * sizeof(T)));
-  have = want;
-  return ISL_OK;
-}
+// Every allocation of the search path is a reserve() that counts into the lane's alloc_events: a
+// lane counts what it had to set up, and a call reports its share in isl_search_stats::allocations
+// (0 once isl_index_prepare has run).
 
 // Streams, events, per-query arrays, overflow table, push log of one lane, sized for nq queries
 // on `slots` resident waves.
@@ -139,10 +116,10 @@ isl_status ensure_lane_stream(const isl_index* idx, isl::SearchWorkspace& ws) {
   if (!ws.ev1) { ISL_HIP(hipEventCreate(&ws.ev1)); ws.alloc_events++; }
   if (!ws.ev_in) { ISL_HIP(hipEventCreateWithFlags(&ws.ev_in, hipEventDisableTiming)); ws.alloc_events++; }
   if (!ws.ticket) {
-    ISL_TRY(lane_malloc(ws, ws.ticket, 64));
+    ISL_TRY(ws.ticket.reserve(16, &ws.alloc_events));
     ws.ticket_clean = false;
   }
-  if (!ws.h_head) ISL_TRY(lane_host_malloc(ws, ws.h_head, 64));
+  ISL_TRY(ws.h_head.reserve(16, &ws.alloc_events));
   ws.stream = st;
   return ISL_OK;
 }
@@ -150,19 +127,12 @@ isl_status ensure_lane_stream(const isl_index* idx, isl::SearchWorkspace& ws) {
 isl_status prepare_workspace(const isl_index* idx, isl::SearchWorkspace& ws, uint32_t nq, uint32_t slots,
                              uint32_t plog_cap) {
   ISL_TRY(ensure_lane_stream(idx, ws));
-  if (ws.h_cap < nq) {
-    if (ws.h_status) (void)hipHostFree(ws.h_status);
-    if (ws.h_ctr) (void)hipHostFree(ws.h_ctr);
-    ws.h_status = ws.h_ctr = nullptr;
-    ws.h_cap = 0;
-    uint64_t cap = nq < 1024 ? 1024 : nq;
-    ISL_TRY(lane_host_malloc(ws, ws.h_status, cap * 4));
-    ISL_TRY(lane_host_malloc(ws, ws.h_ctr, cap * 16));
-    ws.h_cap = cap;
-  }
+  uint64_t* const ev = &ws.alloc_events;
+  const uint64_t cap = nq < 1024 ? 1024 : nq;  // the per-query arrays' floor
+  ISL_TRY(ws.h_status.reserve(cap, ev));
+  ISL_TRY(ws.h_ctr.reserve(cap * 4, ev));
   if (ws.slots < slots || !ws.ovf_tab) {
-    if (ws.ovf_tab) (void)hipFree(ws.ovf_tab);
-    ws.ovf_tab = nullptr;
+    ws.ovf_tab.reset();
     ws.slots = 0;
     // (ISL_OVF_BITS: the overflow table's size for measurements; a query that fills 3/4 of it goes to the heap-exact kernel)
     static const uint32_t ovf_bits_cfg = [] {
@@ -172,81 +142,34 @@ isl_status prepare_workspace(const isl_index* idx, isl::SearchWorkspace& ws, uin
     }();
     ws.ovf_bits = ovf_bits_cfg;
     uint64_t n = (uint64_t)slots << ovf_bits_cfg;
-    ISL_TRY(lane_malloc(ws, ws.ovf_tab, n * 4));
+    ISL_TRY(ws.ovf_tab.reserve(n, ev));
     hipLaunchKernelGGL(fill_u32_kernel, dim3(2048), dim3(256), 0, ws.stream, ws.ovf_tab, n, EMPTY);
     ISL_HIP(hipGetLastError());
     ISL_HIP(hipStreamSynchronize(ws.stream));
     ws.slots = slots;
   }
-  if (ws.cap_q < nq) {
-    void* ptrs[] = {ws.status, ws.payload, ws.ctr, ws.redo, ws.replay, ws.qsel, ws.qsel_h};
-    for (void* q : ptrs)
-      if (q) (void)hipFree(q);
-    ws.status = nullptr; ws.payload = nullptr; ws.ctr = nullptr; ws.redo = nullptr;
-    ws.replay = nullptr; ws.qsel = nullptr; ws.qsel_h = nullptr;
-    ws.cap_q = 0;
-    uint32_t cap = nq < 1024 ? 1024 : nq;
-    ISL_TRY(lane_malloc(ws, ws.status, (size_t)cap * 4));
-    ISL_TRY(lane_malloc(ws, ws.payload, (size_t)cap * 8));
-    ISL_TRY(lane_malloc(ws, ws.ctr, (size_t)cap * 16));
-    ISL_TRY(lane_malloc(ws, ws.redo, (size_t)cap * 4));
-    ISL_TRY(lane_malloc(ws, ws.replay, (size_t)cap * 4));
-    ISL_TRY(lane_malloc(ws, ws.qsel, (size_t)cap * 4));
-    ISL_TRY(lane_malloc(ws, ws.qsel_h, (size_t)cap * 4));
-    ws.cap_q = cap;
-  }
-  uint64_t want_log = (uint64_t)ws.cap_q * plog_cap;
-  if (ws.plog_entries < want_log) {
-    if (ws.plog) (void)hipFree(ws.plog);
-    ws.plog = nullptr;
-    ws.plog_entries = 0;
-    ISL_TRY(lane_malloc(ws, ws.plog, want_log * 8));
-    ws.plog_entries = want_log;
-  }
-  return ISL_OK;
+  ISL_TRY(ws.status.reserve(cap, ev));
+  ISL_TRY(ws.payload.reserve(cap, ev));
+  ISL_TRY(ws.ctr.reserve(cap * 4, ev));
+  ISL_TRY(ws.redo.reserve(cap, ev));
+  ISL_TRY(ws.replay.reserve(cap, ev));
+  ISL_TRY(ws.qsel.reserve(cap, ev));
+  ISL_TRY(ws.qsel_h.reserve(cap, ev));
+  return ws.plog.reserve(ws.status.capacity() * plog_cap, ev);
 }
 
 // Staging of the host-pointer entry points: device buffers + pinned host mirrors.
 isl_status prepare_host_staging(isl::SearchWorkspace& ws, uint64_t nq, uint64_t d, uint64_t k) {
-  const uint64_t qbytes = nq * d * 4;
-  if (ws.q_stage_bytes < qbytes) {
-    if (ws.q_stage) (void)hipFree(ws.q_stage);
-    ws.q_stage = nullptr;
-    ws.q_stage_bytes = 0;
-    ISL_TRY(lane_malloc(ws, ws.q_stage, qbytes));
-    ws.q_stage_bytes = qbytes;
-  }
-  if (ws.h_q_bytes < qbytes) {
-    if (ws.h_q) (void)hipHostFree(ws.h_q);
-    ws.h_q = nullptr;
-    ws.h_q_bytes = 0;
-    ISL_TRY(lane_host_malloc(ws, ws.h_q, qbytes));
-    ws.h_q_bytes = qbytes;
-  }
+  uint64_t* const ev = &ws.alloc_events;
+  ISL_TRY(ws.q_stage.reserve(nq * d, ev));
+  ISL_TRY(ws.h_q.reserve(nq * d, ev));
   const uint64_t slots = nq * std::max<uint64_t>(k, 1);
-  if (ws.out_stage_slots < slots) {
-    void* ptrs[] = {ws.ids_stage, ws.dist_stage, ws.count_stage};
-    for (void* q : ptrs)
-      if (q) (void)hipFree(q);
-    ws.ids_stage = nullptr; ws.dist_stage = nullptr; ws.count_stage = nullptr;
-    ws.out_stage_slots = 0;
-    ISL_TRY(lane_malloc(ws, ws.ids_stage, slots * 8));
-    ISL_TRY(lane_malloc(ws, ws.dist_stage, slots * 4));
-    ISL_TRY(lane_malloc(ws, ws.count_stage, slots * 4));
-    ws.out_stage_slots = slots;
-  }
-  if (ws.h_out_slots < slots) {
-    void* ptrs[] = {ws.h_ids, ws.h_dist, ws.h_count};
-    for (void* q : ptrs)
-      if (q) (void)hipHostFree(q);
-    ws.h_ids = nullptr; ws.h_dist = nullptr; ws.h_count = nullptr;
-    ws.h_out_slots = 0;
-    ISL_TRY(lane_host_malloc(ws, ws.h_ids, slots * 8));
-    ISL_TRY(lane_host_malloc(ws, ws.h_dist, slots * 4));
-    ISL_TRY(lane_host_malloc(ws, ws.h_count, slots * 4));
-    ws.h_out_slots = slots;
-  }
-  return ISL_OK;
+  ISL_TRY(ws.ids_stage.reserve(slots, ev));
+  ISL_TRY(ws.dist_stage.reserve(slots, ev));
+  ISL_TRY(ws.count_stage.reserve(slots, ev));
+  ISL_TRY(ws.h_ids.reserve(slots, ev));
+  ISL_TRY(ws.h_dist.reserve(slots, ev));
+  return ws.h_count.reserve(slots, ev);
 }
 
 // The shared scratch pool of the heap-exact kernel (under idx->mu).  Its sizes follow the index
@@ -259,13 +182,14 @@ isl_status ensure_pool(const isl_index* idx, isl::SearchWorkspace& ws) {
   pl.cand_cap = std::min<uint64_t>(max_id + 1, 1ull << 21);
   pl.ulist_cap = std::max<uint32_t>(idx->max_degree, 64);
   isl_status st = ISL_OK;
-  if ((st = lane_malloc(ws, pl.cand_d, (size_t)kExactSlots * pl.cand_cap * 4)) == ISL_OK &&
-      (st = lane_malloc(ws, pl.cand_id, (size_t)kExactSlots * pl.cand_cap * 4)) == ISL_OK &&
-      (st = lane_malloc(ws, pl.vis_bits, (size_t)kExactSlots * pl.vis_words * 4)) == ISL_OK &&
-      (st = lane_malloc(ws, pl.ulist, (size_t)kExactSlots * pl.ulist_cap * 4)) == ISL_OK &&
-      (st = lane_malloc(ws, pl.locks, (size_t)kExactSlots * 4)) == ISL_OK &&
-      (st = lane_malloc(ws, pl.xstate, (size_t)kExactSlots * (16 + 2 * (kMaxExactEf + 1)) * 4)) == ISL_OK) {
-    pl.xstate_words = 16 + 2 * (kMaxExactEf + 1);
+  uint64_t* const ev = &ws.alloc_events;
+  pl.xstate_words = 16 + 2 * (kMaxExactEf + 1);
+  if ((st = pl.cand_d.reserve(kExactSlots * pl.cand_cap, ev)) == ISL_OK &&
+      (st = pl.cand_id.reserve(kExactSlots * pl.cand_cap, ev)) == ISL_OK &&
+      (st = pl.vis_bits.reserve(kExactSlots * pl.vis_words, ev)) == ISL_OK &&
+      (st = pl.ulist.reserve((uint64_t)kExactSlots * pl.ulist_cap, ev)) == ISL_OK &&
+      (st = pl.locks.reserve(kExactSlots, ev)) == ISL_OK &&
+      (st = pl.xstate.reserve((uint64_t)kExactSlots * pl.xstate_words, ev)) == ISL_OK) {
     if (hipMemset(pl.locks, 0, (size_t)kExactSlots * 4) == hipSuccess) {
       pl.slots = kExactSlots;
       return ISL_OK;
@@ -430,24 +354,24 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.ctr = ws.ctr;
   p.ticket = ws.ticket;
   p.redo = ws.redo;
-  if (ws.d_prof) { (void)hipFree(ws.d_prof); ws.d_prof = nullptr; }
+  ws.d_prof.reset();
   static const bool debug_env = getenv("ISL_DEBUG") != nullptr;
   if (debug_env && !warm) {
-    ISL_HIP(hipMalloc(&ws.d_prof, nq * 64));
+    ISL_TRY(ws.d_prof.reserve(nq * 8));
     ISL_HIP(hipMemset(ws.d_prof, 0, nq * 64));
   }
   p.prof = ws.d_prof;
   // ISL_TIMELINE=<file>: start / end tick of every query of every call, appended at wait time
   // (measurement aid: where a run's fill and drain go; tools/timeline.py reads the file)
   static const char* tline_env = getenv("ISL_TIMELINE");
-  if (ws.d_tline) { (void)hipFree(ws.d_tline); ws.d_tline = nullptr; }
+  ws.d_tline.reset();
   if (tline_env && !warm) {
-    ISL_HIP(hipMalloc(&ws.d_tline, nq * 16));
+    ISL_TRY(ws.d_tline.reserve(nq * 2));
     ISL_HIP(hipMemset(ws.d_tline, 0, nq * 16));
   }
   p.tline = ws.d_tline;
   p.replay = ws.replay;
-  p.plog = reinterpret_cast<uint2*>(ws.plog);
+  p.plog = reinterpret_cast<uint2*>(ws.plog.get());
   p.plog_cap = cg.plog_cap;
   p.hbits = cg.fg.hbits;
   p.hcap = cg.fg.hcap;
@@ -500,7 +424,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   if (tl) {
     const isl_pq* pq = idx->pq;
     const uint64_t want = std::max<uint64_t>(nq, 1) * pq->m * pq->K;
-    ISL_TRY(ensure(ws, ws.tl_tables, ws.tl_tables_cap, want));
+    ISL_TRY(ws.tl_tables.reserve(want, &ws.alloc_events));
     p.tl_tables = ws.tl_tables;
     p.tl_codes = idx->d_codes;
     p.tl_ncodes = idx->ncodes;
@@ -548,7 +472,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   if (use_fast && idx->is_hnsw && p.max_level > 0) {
     // HnswGraph::search: greedy descent through the upper layers first (its own kernel, so that
     // the traversal kernel keeps its register budget)
-    ISL_TRY(ensure(ws, ws.q_entry, ws.q_entry_cap, std::max<uint64_t>(nq, 1) * 2));
+    ISL_TRY(ws.q_entry.reserve(std::max<uint64_t>(nq, 1) * 2, &ws.alloc_events));
     p.q_entry = ws.q_entry;
     p.q_evals = ws.q_entry + nq;
     const uint32_t dgrid = (uint32_t)std::min<uint64_t>(nq_grid, 8192);
@@ -654,8 +578,7 @@ isl_status search_finish(const isl_index* idx, isl::SearchWorkspace& ws, uint32_
   const uint32_t* status = ws.h_status;
   const uint32_t* ctr = ws.h_ctr;
   const uint32_t* head = ws.h_head;
-  uint64_t* d_prof = ws.d_prof;
-  ws.d_prof = nullptr;
+  isl::DeviceBuffer<uint64_t> d_prof = std::move(ws.d_prof);
   float ms = 0.0f;
   (void)hipEventElapsedTime(&ms, ws.ev0, ws.ev1);
 
@@ -681,8 +604,7 @@ isl_status search_finish(const isl_index* idx, isl::SearchWorkspace& ws, uint32_
     tl[0] = 0x154C494E45ull;  // record header: magic, query count
     tl[1] = nq;
     ISL_HIP(hipMemcpy(tl.data() + 2, ws.d_tline, nq * 16, hipMemcpyDeviceToHost));
-    (void)hipFree(ws.d_tline);
-    ws.d_tline = nullptr;
+    ws.d_tline.reset();
     static std::mutex tl_mu;
     std::lock_guard<std::mutex> lock(tl_mu);
     if (FILE* f = fopen(getenv("ISL_TIMELINE"), "ab")) {
@@ -693,7 +615,6 @@ isl_status search_finish(const isl_index* idx, isl::SearchWorkspace& ws, uint32_
   if (d_prof) {
     std::vector<uint64_t> pr(nq * 8);
     ISL_HIP(hipMemcpy(pr.data(), d_prof, nq * 64, hipMemcpyDeviceToHost));
-    (void)hipFree(d_prof);
     double sum[4] = {0, 0, 0, 0}, grp = 0, hr = 0;
     for (uint64_t i = 0; i < nq; i++) {
       for (int j = 0; j < 4; j++) sum[j] += pr[i * 8 + j] / 100.0;
@@ -854,22 +775,13 @@ __global__ __launch_bounds__(64) void row_norm2_list_kernel(const float* __restr
 
 // query lists of a lane (rounds of the recompute provider, retries of the two-level search)
 isl_status ensure_qlist(isl::SearchWorkspace& ws, uint64_t nq) {
-  if (ws.qlist_cap >= nq && ws.qlist && ws.h_qlist && ws.qflag && ws.xslot && ws.h_xlist) return ISL_OK;
-  if (ws.qflag) (void)hipFree(ws.qflag);
-  if (ws.qlist) (void)hipFree(ws.qlist);
-  if (ws.xslot) (void)hipFree(ws.xslot);
-  if (ws.h_qlist) (void)hipHostFree(ws.h_qlist);
-  if (ws.h_xlist) (void)hipHostFree(ws.h_xlist);
-  ws.qflag = ws.qlist = ws.xslot = ws.h_qlist = ws.h_xlist = nullptr;
-  ws.qlist_cap = 0;
+  uint64_t* const ev = &ws.alloc_events;
   const uint64_t c = nq < 1024 ? 1024 : nq;
-  ISL_TRY(lane_malloc(ws, ws.qflag, c * 4));
-  ISL_TRY(lane_malloc(ws, ws.qlist, c * 4));
-  ISL_TRY(lane_malloc(ws, ws.xslot, c * 4));
-  ISL_TRY(lane_host_malloc(ws, ws.h_qlist, c * 4));
-  ISL_TRY(lane_host_malloc(ws, ws.h_xlist, c * 4));
-  ws.qlist_cap = c;
-  return ISL_OK;
+  ISL_TRY(ws.qflag.reserve(c, ev));
+  ISL_TRY(ws.qlist.reserve(c, ev));
+  ISL_TRY(ws.xslot.reserve(c, ev));
+  ISL_TRY(ws.h_qlist.reserve(c, ev));
+  return ws.h_xlist.reserve(c, ev);
 }
 
 // Two-level search: the queries of the finished launch whose approximate-queue window was too small
@@ -893,22 +805,20 @@ isl_status prepare_recompute(isl::SearchWorkspace& ws, uint64_t nq, uint64_t sta
   const uint64_t cap = std::min<uint64_t>(nq * 128 + 64, 0xFFFFFFF0ull);  // a hop keeps up to 128 rows
   const uint64_t pcap = nq * 8 + 64;  // + the ids parked two-level queries expect to promote next (behind miss[cap])
   if (ws.miss_cap < cap || ws.pref_cap < pcap) {
-    void* ptrs[] = {ws.miss, ws.uniq, ws.uniq_count, ws.uslots};
-    for (void* q : ptrs)
-      if (q) (void)hipFree(q);
-    ws.miss = ws.uniq = ws.uniq_count = ws.uslots = nullptr;
+    // the prefetch ids sit behind miss[miss_cap]: a new split means new arrays
+    ws.miss.reset(); ws.uniq.reset(); ws.uslots.reset(); ws.uniq_count.reset();
     ws.miss_cap = 0;
     ws.pref_cap = 0;
-    ISL_TRY(lane_malloc(ws, ws.miss, (cap + pcap) * 4));
-    ISL_TRY(lane_malloc(ws, ws.uniq, (cap + pcap) * 4));
-    ISL_TRY(lane_malloc(ws, ws.uslots, (cap + pcap) * 4));
-    ISL_TRY(lane_malloc(ws, ws.uniq_count, 4));
+    uint64_t* const ev = &ws.alloc_events;
+    ISL_TRY(ws.miss.reserve(cap + pcap, ev));
+    ISL_TRY(ws.uniq.reserve(cap + pcap, ev));
+    ISL_TRY(ws.uslots.reserve(cap + pcap, ev));
+    ISL_TRY(ws.uniq_count.reserve(1, ev));
     ws.miss_cap = cap;
     ws.pref_cap = pcap;
   }
   ISL_TRY(ensure_qlist(ws, nq));
-  ISL_TRY(ensure(ws, ws.qstate, ws.qstate_words, std::max<uint64_t>(nq, 1) * state_words_per_query));
-  return ISL_OK;
+  return ws.qstate.reserve(std::max<uint64_t>(nq, 1) * state_words_per_query, &ws.alloc_events);
 }
 
 // One synchronous search on a claimed lane.  With the in-memory provider: enqueue + finish.  With
@@ -1078,8 +988,8 @@ isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const Sea
           const TwoLevelCall tl1{c.ratio, plan.window_scale};
           CallGeometry cg1;
           ISL_TRY(call_geometry(idx, c.d, c.k, c.ef, &tl1, cg1));
-          ISL_TRY(ensure(ws, ws.qstate, ws.qstate_words, std::max<uint64_t>(nq, 1) * cg1.state_words));
-          again.assign(ws.h_qlist, ws.h_qlist + nshort);
+          ISL_TRY(ws.qstate.reserve(std::max<uint64_t>(nq, 1) * cg1.state_words, &ws.alloc_events));
+          again.assign(ws.h_qlist.get(), ws.h_qlist + nshort);
           while (na < max_active && !again.empty()) { ws.h_qlist[na++] = again.back(); again.pop_back(); }
         }
       }
@@ -1198,8 +1108,9 @@ isl_status recompute_coalesced(const isl_index* idx, isl::SearchWorkspace& ws, c
       if (m != &me) { alone(m); m->done = true; }
     return search_sync(idx, ws, c);
   };
-  if (ensure(ws, ws.co_q, ws.co_q_cap, total * d) != ISL_OK || ensure(ws, ws.co_ids, ws.co_ids_cap, total * std::max<uint64_t>(k, 1)) != ISL_OK ||
-      ensure(ws, ws.co_dist, ws.co_dist_cap, total * std::max<uint64_t>(k, 1)) != ISL_OK || ensure(ws, ws.co_cnt, ws.co_cnt_cap, total) != ISL_OK ||
+  uint64_t* const ev = &ws.alloc_events;
+  if (ws.co_q.reserve(total * d, ev) != ISL_OK || ws.co_ids.reserve(total * std::max<uint64_t>(k, 1), ev) != ISL_OK ||
+      ws.co_dist.reserve(total * std::max<uint64_t>(k, 1), ev) != ISL_OK || ws.co_cnt.reserve(total, ev) != ISL_OK ||
       ensure_lane_stream(idx, ws) != ISL_OK)
     return fall_back();
   hipStream_t st = ws.stream;
@@ -1397,11 +1308,11 @@ isl_status host_stage_in(const isl_index* idx, isl::SearchWorkspace& ws, SearchC
   const uint64_t bytes = c.nq * c.d * 4;
   memcpy(ws.h_q, c.queries, bytes);
   if (bytes % 16 == 0)
-    hipLaunchKernelGGL(copy_u128_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint4*)ws.h_q, (uint4*)ws.q_stage,
+    hipLaunchKernelGGL(copy_u128_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint4*)ws.h_q.get(), (uint4*)ws.q_stage.get(),
                        bytes / 16);
   else
-    hipLaunchKernelGGL(copy_u32_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint32_t*)ws.h_q,
-                       (uint32_t*)ws.q_stage, bytes / 4);
+    hipLaunchKernelGGL(copy_u32_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint32_t*)ws.h_q.get(),
+                       (uint32_t*)ws.q_stage.get(), bytes / 4);
   ISL_HIP(hipGetLastError());
   ws.publish_results = true;
   // from here on the call runs over the lane's staging buffers, on the lane's stream
@@ -1487,12 +1398,7 @@ bool any_lane_busy(const isl_index* idx) {
   return false;
 }
 
-void free_exact_pool(ExactPool& pl) {
-  void* ptrs[] = {pl.cand_d, pl.cand_id, pl.vis_bits, pl.ulist, pl.locks, pl.xstate};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  pl = ExactPool{};
-}
+void free_exact_pool(ExactPool& pl) { pl = ExactPool{}; }
 
 // padded copy of the adjacency (64 ids per node + a degree array): 260 bytes per node buy the
 // traversal one dependent memory round trip per hop.  Built where the CSR becomes resident
@@ -1502,26 +1408,21 @@ isl_status ensure_padded_adjacency(isl_index* idx) {
   if (idx->d_ell || !idx->d_off || !idx->num_nodes || idx->max_degree > 128) return ISL_OK;
   const uint64_t n = idx->num_nodes;
   const uint32_t W = idx->max_degree > 64 ? 128u : 64u;
-  uint32_t* ell = nullptr;
-  uint32_t* deg = nullptr;
-  if (hipMalloc(&ell, n * W * 4) != hipSuccess || hipMalloc(&deg, n * 4) != hipSuccess) {
+  DeviceBuffer<uint32_t> ell, deg;
+  if (ell.reserve(n * W) != ISL_OK || deg.reserve(n) != ISL_OK) {
     (void)hipGetLastError();
-    if (ell) (void)hipFree(ell);
     return ISL_OK;
   }
   hipLaunchKernelGGL(pad_rows_kernel, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, nullptr, idx->d_off, idx->d_adj, n,
                      W, ell, deg);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e != hipSuccess) {
-    (void)hipFree(ell);
-    (void)hipFree(deg);
-    return fail(ISL_ERR_DEVICE, "padded adjacency: %s", hipGetErrorString(e));
-  }
-  idx->d_ell = ell;
-  idx->d_ell_deg = deg;
+  if (e != hipSuccess) return fail(ISL_ERR_DEVICE, "padded adjacency: %s", hipGetErrorString(e));
+  idx->ell_copy = std::move(ell);
+  idx->ell_deg_copy = std::move(deg);
+  idx->d_ell = idx->ell_copy;
+  idx->d_ell_deg = idx->ell_deg_copy;
   idx->ell_w = W;
-  idx->ell_owned = true;
   return ISL_OK;
 }
 
@@ -1598,9 +1499,9 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
     ISL_TRY(prepare_workspace(idx, ws, (uint32_t)max_nq, idx->recompute ? (uint32_t)max_nq : ovf_slots, cg_max.plog_cap));
     ISL_TRY(prepare_host_staging(ws, max_nq, d, std::max<uint64_t>(max_k, 1)));
     if (idx->recompute) ISL_TRY(prepare_recompute(ws, max_nq, cg_max.state_words));
-    if (idx->is_hnsw) ISL_TRY(ensure(ws, ws.q_entry, ws.q_entry_cap, max_nq * 2));
+    if (idx->is_hnsw) ISL_TRY(ws.q_entry.reserve(max_nq * 2, &ws.alloc_events));
     if (idx->pq && idx->d_codes && !idx->is_hnsw && d == idx->pq->dimension)
-      ISL_TRY(ensure(ws, ws.tl_tables, ws.tl_tables_cap, max_nq * idx->pq->m * idx->pq->K));
+      ISL_TRY(ws.tl_tables.reserve(max_nq * idx->pq->m * idx->pq->K, &ws.alloc_events));
     memset(ws.h_q, 0, max_nq * d * 4);
   }
   // The kernels this index will launch, over zero queries, and one staged copy each way, on all
@@ -1611,8 +1512,8 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
   for (int round = 0; round < 2; ++round) {
     for (int i = 0; i < lanes; ++i) {
       isl::SearchWorkspace& ws = idx->ws[i];
-      hipLaunchKernelGGL(copy_u128_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint4*)ws.h_q,
-                         (uint4*)ws.q_stage, max_nq * d * 4 / 16);
+      hipLaunchKernelGGL(copy_u128_kernel, dim3(256), dim3(256), 0, ws.stream, (const uint4*)ws.h_q.get(),
+                         (uint4*)ws.q_stage.get(), max_nq * d * 4 / 16);
       const uint64_t efs[] = {max_ef, std::min<uint64_t>(max_ef, 64)};
       SearchCall warm_call;  // no queries, no buffers, on the lane's stream
       warm_call.d = d;
@@ -1811,27 +1712,24 @@ isl_status isl_index_set_pq_codes(isl_index* idx, const isl_pq* pq, const uint16
   std::lock_guard<std::mutex> lock(idx->mu);
   if (isl::any_lane_busy(idx))
     return isl::fail(ISL_ERR_SEARCH, "Search error: PQ codes cannot be swapped while searches are in flight");
-  if (idx->d_codes) { (void)hipFree(idx->d_codes); idx->d_codes = nullptr; }
+  idx->d_codes.reset();
   idx->pq = nullptr;
   idx->ncodes = 0;
   const size_t bytes = (size_t)n * pq->m * 2;
-  ISL_HIP(hipMalloc(&idx->d_codes, bytes));
-  ISL_HIP(hipMemcpy(idx->d_codes, codes, bytes, mem == ISL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
+  isl::DeviceBuffer<uint16_t> d_codes;  // joins the index once checked
+  isl::DeviceBuffer<uint32_t> d_flag;
+  ISL_TRY(d_codes.reserve(n * pq->m));
+  ISL_HIP(hipMemcpy(d_codes, codes, bytes, mem == ISL_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice));
   // tables[sq][code] of table_distance (pq.rs:345) would index out of bounds (panic) for a code >= K
-  uint32_t* d_flag = nullptr;
-  ISL_HIP(hipMalloc(&d_flag, 4));
+  ISL_TRY(d_flag.reserve(1));
   ISL_HIP(hipMemset(d_flag, 0, 4));
-  hipLaunchKernelGGL(check_codes_kernel, dim3(1024), dim3(256), 0, nullptr, idx->d_codes, (uint64_t)n * pq->m,
-                     (uint32_t)pq->K, d_flag);
+  hipLaunchKernelGGL(check_codes_kernel, dim3(1024), dim3(256), 0, nullptr, d_codes.get(), (uint64_t)n * pq->m,
+                     (uint32_t)pq->K, d_flag.get());
   uint32_t flag = 0;
   hipError_t e = hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost);
-  (void)hipFree(d_flag);
-  if (e != hipSuccess || flag) {
-    (void)hipFree(idx->d_codes);
-    idx->d_codes = nullptr;
-    if (e != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "code check failed: %s", hipGetErrorString(e));
-    return isl::fail(ISL_ERR_PQ, "PQ error: a code is not below num_centroids = %llu", (unsigned long long)pq->K);
-  }
+  if (e != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "code check failed: %s", hipGetErrorString(e));
+  if (flag) return isl::fail(ISL_ERR_PQ, "PQ error: a code is not below num_centroids = %llu", (unsigned long long)pq->K);
+  idx->d_codes = std::move(d_codes);
   idx->pq = pq;
   idx->ncodes = n;
   return ISL_OK;

@@ -83,14 +83,14 @@ struct Slot {
   uint64_t handle = 0, token = 0;
   uint64_t nq = 0, k = 0;
   uint64_t released_at = 0;   // free slots are reused least-recently-released first
-  uint8_t* rec = nullptr;    // this rank's record, written in place by the search kernels
-  uint8_t* gath = nullptr;   // [world][B]
-  uint64_t* ids = nullptr;   // merged answers
-  float* dist = nullptr;
-  uint32_t* src = nullptr;
-  uint32_t* cnt = nullptr;
-  uint8_t* h_rec = nullptr;  // host transport: pinned mirrors
-  uint8_t* h_gath = nullptr;
+  isl::DeviceBuffer<uint8_t> rec;    // this rank's record, written in place by the search kernels
+  isl::DeviceBuffer<uint8_t> gath;   // [world][B]
+  isl::DeviceBuffer<uint64_t> ids;   // merged answers
+  isl::DeviceBuffer<float> dist;
+  isl::DeviceBuffer<uint32_t> src;
+  isl::DeviceBuffer<uint32_t> cnt;
+  isl::PinnedBuffer<uint8_t> h_rec;  // host transport: pinned mirrors
+  isl::PinnedBuffer<uint8_t> h_gath;
   uint32_t* d_flags = nullptr;  // this batch's merge flags (one word of the searcher's array)
   uint32_t* h_flags = nullptr;  // ... and their pinned mirror, written on the side stream behind the merge
   hipEvent_t done = nullptr;  // behind the merge of the batch in this slot
@@ -114,20 +114,19 @@ struct isl_sharded_searcher {
   int32_t device = 0, world = 1, rank = 0;
   uint64_t n_total = 0;
   std::vector<uint64_t> id_base;
-  uint64_t* d_base = nullptr;
-  uint32_t* d_flags = nullptr;   // [depth] one word per slot, cleared on the side stream before the slot's merge
-  uint32_t* h_flags = nullptr;   // [depth] pinned mirrors
+  isl::DeviceBuffer<uint64_t> d_base;
+  isl::DeviceBuffer<uint32_t> d_flags;   // [depth] one word per slot, cleared on the side stream before the slot's merge
+  isl::PinnedBuffer<uint32_t> h_flags;   // [depth] pinned mirrors
   uint32_t flags_seen = 0;       // OR of the flags of every completed batch (isl_sharded_flags)
-  uint8_t* d_warm = nullptr;     // [16 + 16 * world] the 16-byte status exchange of isl_sharded_prepare
-  uint8_t* h_warm = nullptr;     // pinned, same size
+  isl::DeviceBuffer<uint8_t> d_warm;     // [16 + 16 * world] the 16-byte status exchange of isl_sharded_prepare
+  isl::PinnedBuffer<uint8_t> h_warm;     // pinned, same size
   hipStream_t side = nullptr;
   int32_t depth = 1;
   std::vector<Slot> slots;
   uint64_t cap_nq = 0, cap_k = 0;
   uint64_t release_clock = 1, next_handle = 1;
   // staging of the host-buffer entry point (one such call at a time: host_mu spans the whole call)
-  float* d_q = nullptr;
-  uint64_t d_q_bytes = 0;
+  isl::DeviceBuffer<float> d_q;
   std::mutex mu;
   std::mutex host_mu;
 };
@@ -135,11 +134,6 @@ struct isl_sharded_searcher {
 namespace {
 
 void free_slot(Slot& s) {
-  void* dev[] = {s.rec, s.gath, s.ids, s.dist, s.src, s.cnt};
-  for (void* p : dev)
-    if (p) (void)hipFree(p);
-  if (s.h_rec) (void)hipHostFree(s.h_rec);
-  if (s.h_gath) (void)hipHostFree(s.h_gath);
   if (s.done) (void)hipEventDestroy(s.done);
   s = Slot{};
 }
@@ -168,21 +162,22 @@ isl_status size_slots(isl_sharded_searcher* s, uint64_t nq, uint64_t k) {
                        "while batches are in flight");
   const uint64_t cnq = std::max(nq, s->cap_nq), ck = std::max<uint64_t>(std::max(k, s->cap_k), 1);
   for (Slot& sl : s->slots) free_slot(sl);
-  s->slots.assign((size_t)s->depth, Slot{});
+  s->slots.clear();
+  s->slots.resize((size_t)s->depth);
   s->cap_nq = s->cap_k = 0;
   const uint64_t B = isl_shard_record_bytes(cnq, ck);
   size_t i = 0;
   for (Slot& sl : s->slots) {
-    ISL_HIP(hipMalloc(&sl.rec, B));
-    ISL_HIP(hipMalloc(&sl.gath, B * (uint64_t)s->world));
-    ISL_HIP(hipMalloc(&sl.ids, cnq * ck * 8));
-    ISL_HIP(hipMalloc(&sl.dist, cnq * ck * 4));
-    ISL_HIP(hipMalloc(&sl.src, cnq * ck * 4));
-    ISL_HIP(hipMalloc(&sl.cnt, cnq * 4));
+    ISL_TRY(sl.rec.reserve(B));
+    ISL_TRY(sl.gath.reserve(B * (uint64_t)s->world));
+    ISL_TRY(sl.ids.reserve(cnq * ck));
+    ISL_TRY(sl.dist.reserve(cnq * ck));
+    ISL_TRY(sl.src.reserve(cnq * ck));
+    ISL_TRY(sl.cnt.reserve(cnq));
     ISL_HIP(hipMemset(sl.rec, 0, B));
     if (s->grp && s->grp->host_fn) {
-      ISL_HIP(hipHostMalloc(&sl.h_rec, B));
-      ISL_HIP(hipHostMalloc(&sl.h_gath, B * (uint64_t)s->world));
+      ISL_TRY(sl.h_rec.reserve(B));
+      ISL_TRY(sl.h_gath.reserve(B * (uint64_t)s->world));
     }
     ISL_HIP(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
     sl.d_flags = s->d_flags + i;
@@ -372,9 +367,8 @@ isl_status isl_sharded_searcher_new(const isl_index* shard, isl_shard_group* grp
     s->id_base[(size_t)r] = id_base ? id_base[r] : n_total * (uint64_t)r / (uint64_t)s->world;
   auto bail = [&](isl_status st) { isl_sharded_searcher_free(s); return st; };
   const size_t warm = 16 + 16 * (size_t)s->world;
-  if (hipMalloc(&s->d_base, (size_t)s->world * 8) != hipSuccess || hipMalloc(&s->d_flags, (size_t)depth * 4) != hipSuccess ||
-      hipHostMalloc(&s->h_flags, (size_t)depth * 4) != hipSuccess ||
-      hipMalloc(&s->d_warm, warm) != hipSuccess || hipHostMalloc(&s->h_warm, warm) != hipSuccess ||
+  if (s->d_base.reserve((uint64_t)s->world) != ISL_OK || s->d_flags.reserve((uint64_t)depth) != ISL_OK ||
+      s->h_flags.reserve((uint64_t)depth) != ISL_OK || s->d_warm.reserve(warm) != ISL_OK || s->h_warm.reserve(warm) != ISL_OK ||
       hipMemcpy(s->d_base, s->id_base.data(), (size_t)s->world * 8, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(s->d_flags, 0, (size_t)depth * 4) != hipSuccess || hipMemset(s->d_warm, 0, warm) != hipSuccess ||
       hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking) != hipSuccess)
@@ -397,14 +391,11 @@ void isl_sharded_searcher_free(isl_sharded_searcher* s) {
   for (Slot& sl : s->slots) {
     // a batch nobody asked the result of: its search still holds a lane of the index
     if ((sl.busy || sl.zombie) && sl.token) (void)isl_search_wait(s->idx, sl.token);
-    if (!sl.lost) free_slot(sl);  // (a lost slot's buffers may still be written by a late collective: leaked on purpose)
+    // a lost slot's buffers may still be written by a late collective: it moves out of the searcher
+    // and is leaked on purpose, buffers and event
+    if (sl.lost) new Slot(std::move(sl));
+    else free_slot(sl);
   }
-  if (s->d_base) (void)hipFree(s->d_base);
-  if (s->d_flags) (void)hipFree(s->d_flags);
-  if (s->h_flags) (void)hipHostFree(s->h_flags);
-  if (s->d_warm) (void)hipFree(s->d_warm);
-  if (s->h_warm) (void)hipHostFree(s->h_warm);
-  if (s->d_q) (void)hipFree(s->d_q);
   if (s->side) (void)hipStreamDestroy(s->side);
   delete s;
 }
@@ -476,7 +467,7 @@ isl_status isl_sharded_submit(isl_sharded_searcher* s, const float* d_queries, u
   sl.recorded = false;
   sl.local_st = ISL_OK;
   uint64_t tok = 0;
-  isl_status local = isl_search_batch_device_async(s->idx, d_queries, nq, d, k, ef, (uint64_t*)sl.rec,
+  isl_status local = isl_search_batch_device_async(s->idx, d_queries, nq, d, k, ef, (uint64_t*)sl.rec.get(),
                                                    (float*)(sl.rec + nq * k * 8), rec_counts, stream, &tok);
   sl.token = tok;
   if (local == ISL_OK) {
@@ -600,13 +591,7 @@ isl_status isl_sharded_search_batch(isl_sharded_searcher* s, const float* querie
   // other's queries or free the buffer under a search in flight)
   std::lock_guard<std::mutex> host_lock(s->host_mu);
   const uint64_t bytes = nq * d * 4;
-  if (s->d_q_bytes < bytes) {
-    if (s->d_q) (void)hipFree(s->d_q);
-    s->d_q = nullptr;
-    s->d_q_bytes = 0;
-    ISL_HIP(hipMalloc(&s->d_q, bytes));
-    s->d_q_bytes = bytes;
-  }
+  ISL_TRY(s->d_q.reserve(nq * d));
   ISL_HIP(hipMemcpy(s->d_q, queries, bytes, hipMemcpyHostToDevice));
   uint64_t h = 0;
   ISL_TRY(isl_sharded_submit(s, s->d_q, nq, d, k, ef, nullptr, &h));

@@ -41,7 +41,8 @@ int main() {
       for (uint32_t d : {100u, 768u, 4096u})
         for (const Variant& v : variants) {
           idx->max_degree = deg;
-          idx->d_emb16 = v.bf16 ? &bf16_rows : nullptr;
+          (void)idx->d_emb16.release();  // (not a device block: it must never reach the buffer's free)
+          if (v.bf16) idx->d_emb16.adopt(&bf16_rows, 1);
           idx->recompute = v.recompute;
           idx->evals_hint.store(v.bf16 ? ((uint64_t)ef << 32) | 3100u : 0u);
           TwoLevelCall t{0.5f, v.tl == 2 ? 4u : 1u};
@@ -55,5 +56,6 @@ int main() {
           printf(" | %d %d %u %zu %u %u | %u %u %zu %zu\n", cg.segments, (int)cg.qh, cg.fgq.hbits, cg.fgq.lds,
                  cg.fgq.hcap, cg.slots_q, cg.state_words, cg.lane_slots, cg.exact_lds, cg.descent_lds);
         }
+  (void)idx->d_emb16.release();  // whatever the last variant was, no host address stays in an owning member
   return 0;
 }
