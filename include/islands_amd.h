@@ -639,6 +639,42 @@ isl_status isl_hnsw_random_levels(uint64_t seed, uint64_t n, double ml, uint64_t
 isl_status isl_hnsw_build(const isl_hnsw_config* cfg, const isl_build_options* opts, const float* vectors,
                           uint64_t n, uint64_t d, const uint64_t* levels, uint64_t level_seed, int32_t mem,
                           int32_t device, isl_hnsw** out);
+/* HnswGraph::insert (hnsw.rs:214-251) for n_new more rows: nodes len .. len + n_new - 1 enter `h` in id order,
+ * in place, under the config the handle carries (m, m0, ef_construction, metric, ml, max_layers).  `h` may
+ * have been built here, read by isl_hnsw_from_bytes or handed over with isl_hnsw_from_layers.  *first_id
+ * (may be NULL) = the old len, written only where the call returns ISL_OK.  `opts` is the rule and batch of THIS call, as for isl_hnsw_build (NULL = the
+ * defaults; the rule is still not recorded in the graph).  `levels[i]` stands for random_level() of node
+ * len + i; NULL: positions len .. len + n_new - 1 of the `level_seed` stream of isl_hnsw_random_levels (the
+ * stream is addressed by position), so isl_hnsw_build(v, seed) equals isl_hnsw_build(v[:n0], seed) followed
+ * by isl_hnsw_insert(v[n0:], seed).
+ * opts->batch == 1, either rule: the graph after the call is the graph isl_hnsw_build makes of all
+ * len + n_new rows with the concatenated levels -- the same lists on every layer, levels, entry point, max
+ * level and isl_hnsw_to_bytes image.  batch > 1: the throughput mode of isl_hnsw_build (a step takes
+ * min(batch, n - id0, max(1, id0 / 8)) nodes, id0 starting at the old len; a node above the current max
+ * level is alone in its step), same rules, no parity claim.
+ * An empty handle (len 0, no entry point, no dimension) takes the rows as isl_hnsw_build would with the
+ * handle's config, on the device it was made for; d becomes its dimension.
+ * Strong guarantee: on any failure `h` is unchanged (lists, rows, bytes, search answers).  The grown graph
+ * is built beside the old one and swapped into the handle at the end.  Peak device memory is therefore the
+ * old graph, plus one row table of len + n_new rows, plus the per-layer construction tables ([n][m0 + 1]
+ * ids on layer 0, [n][m + 1] per layer above): about twice the rows for the duration of the call.
+ * The call is the `&mut self` of the reference: it must not run beside searches on the same handle; if a
+ * lane of the handle's index is busy it returns ISL_ERR_SEARCH, as the provider setters do.  Lanes and the
+ * padded adjacency of the grown graph are set up again at its first search.
+ * Checked in this order before any device call: NULL h, or NULL vectors with n_new > 0 ->
+ * ISL_ERR_INVALID_ARGUMENT; opts as in isl_hnsw_build; n_new == 0 -> ISL_OK, nothing changed; a non-empty
+ * graph and d != its dimension -> ISL_ERR_DIMENSION_MISMATCH (payload expected, actual: hnsw.rs:216-222);
+ * d == 0 -> ISL_ERR_EMPTY_COLLECTION; levels[i] >= max_layers -> ISL_ERR_INVALID_ARGUMENT; m0 > 128,
+ * ef_construction > 512, len + n_new beyond the device id range or more than 64 layers ->
+ * ISL_ERR_UNSUPPORTED; and ISL_ERR_UNSUPPORTED, with a message that says which, for a handle whose rows are
+ * not resident f32 rows, a handle with a list longer than its layer's M_L (isl_hnsw_from_bytes accepts such
+ * images; the tables hold M_L + 1 ids -- lists above layer 0 are measured while they are imported), a
+ * handle whose layer-0 device copy is not the list verbatim because ids repeated inside a list were removed
+ * at upload, and a handle whose levels do not match its layers (the entry point's level is not max_level,
+ * or a level exceeds it: isl_hnsw_from_layers with levels == NULL and layers above 0). */
+isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts, const float* vectors, uint64_t n_new,
+                           uint64_t d, const uint64_t* levels, uint64_t level_seed, int32_t mem,
+                           uint64_t* first_id);
 /* Read-back into host buffers, for every isl_hnsw handle (built, from_layers, from_bytes). */
 isl_status isl_hnsw_info(const isl_hnsw* h, int32_t* has_entry, uint64_t* entry, uint64_t* max_level,
                          uint64_t* dim);

@@ -300,6 +300,18 @@ class HnswGraph {
                          level_seed, ISL_MEM_HOST, device, &g.h_));
     return g;
   }
+  // HnswGraph::insert (hnsw.rs:214-251) for more rows, in place (isl_hnsw_insert): nodes len .. len + n - 1 under
+  // the config the graph carries; returns the first new id.  `levels` empty = the level_seed stream continued at
+  // position len; opts NULL = the reference rule, one node per step.  On an error the graph is unchanged.
+  uint64_t insert(const std::vector<float>& vectors, uint64_t dim, const std::vector<uint64_t>& levels = {},
+                  uint64_t level_seed = 0, const isl_build_options* opts = nullptr) {
+    const uint64_t n = dim ? vectors.size() / dim : 0;
+    uint64_t first = 0;
+    check(isl_hnsw_insert(h_, opts, n ? vectors.data() : nullptr, n, dim, levels.empty() ? nullptr : levels.data(),
+                          level_seed, ISL_MEM_HOST, &first));
+    if (n) vectors_.clear();  // the host copy of the smaller graph's rows: get_vector asks the device now
+    return first;
+  }
   // HnswGraph::to_bytes, hnsw.rs:507-509 (nodes in ascending id)
   std::vector<uint8_t> to_bytes() const {
     uint8_t* p = nullptr;

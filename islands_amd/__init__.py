@@ -924,6 +924,44 @@ class HnswGraph:
         g.m, g.m0, g.ef_construction, g.metric = m, m0, ef_construction, DistanceMetric(metric)
         return g
 
+    def insert(self, vectors, levels=None, level_seed: int = 0, batch: int = 1, select="reference",
+               alpha: float = 1.0, keep_pruned: bool = True) -> int:
+        """HnswGraph::insert (hnsw.rs:214-251) for more rows, in place (isl_hnsw_insert): they become nodes
+        len .. len + n - 1 under the config the graph carries; returns the first new id.  `levels`, `batch`
+        and the rule are those of this call, as for `build`; levels = None continues the `level_seed` stream
+        at position len, so build(v, level_seed=s) equals build(v[:n0], level_seed=s) then
+        insert(v[n0:], level_seed=s).  With batch = 1 the graph afterwards is the one `build` makes of all
+        rows.  On an error the graph is unchanged.  `vectors`: an array, or a float32 torch tensor resident
+        on the graph's device.  Not beside searches on the same graph."""
+        on_device = hasattr(vectors, "data_ptr") and getattr(vectors, "is_cuda", False)
+        if on_device:
+            v = vectors.contiguous()
+            if str(v.dtype) != "torch.float32":
+                raise TypeError("device rows must be float32")
+            if v.dim() == 1:
+                v = v.reshape(1, -1)
+            n, d = int(v.shape[0]), int(v.shape[1])
+            vp = C.c_void_p(v.data_ptr())
+        else:
+            v = _f32(vectors)
+            if v.ndim == 1:
+                v = v.reshape(1, -1)
+            n, d = v.shape
+            vp = _ptr(v)
+        lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint64).reshape(-1)
+        if lv is not None and lv.size != n:
+            raise ValueError("one level per row")
+        o = LeannIndex._build_options(select, alpha, keep_pruned, batch)
+        first = u64()
+        _check(_ffi.lib().isl_hnsw_insert(self._h, C.byref(o), vp if n else None, n, d,
+                                          None if lv is None or not n else _ptr(lv), level_seed,
+                                          MEM_DEVICE if on_device else MEM_HOST, C.byref(first)))
+        # what the object kept of the smaller graph: the library answers for the grown one
+        self._levels = None
+        self.vectors = None
+        self._keep = None
+        return int(first.value)
+
     @staticmethod
     def random_levels(n: int, ml: float | None = None, max_layers: int = 16, seed: int = 0) -> np.ndarray:
         """isl_hnsw_random_levels: random_level (hnsw.rs:206-211) for n nodes from a seeded generator."""
@@ -952,7 +990,7 @@ class HnswGraph:
 
     def level(self, node: int) -> int | None:
         """get_node(id).level"""
-        if getattr(self, "_levels", None) is None:  # a handle's levels never change: read once
+        if getattr(self, "_levels", None) is None:  # read once; insert() drops the copy
             self._levels = self.levels()
         return int(self._levels[node]) if 0 <= node < self._levels.size else None
 

@@ -675,6 +675,28 @@ isl_status isl_index_from_device_csr(const isl_leann_config* cfg, int32_t device
   return ISL_OK;
 }
 
+// Rows [first, nvec) of the f32 provider's table (allocated for nvec rows of emb_d floats at emb_stride, plus
+// the slack) from `rows` (host or device, `mem`), the padding and the slack zeroed, and their norms.
+static isl_status upload_f32_rows(isl_index* idx, uint64_t first, const float* rows, int32_t mem) {
+  const uint64_t n = idx->nvec, cnt = n - first, d = idx->emb_d, stride = idx->emb_stride;
+  float* at = idx->d_emb + first * stride;
+  if (stride != d) ISL_HIP(hipMemset(at, 0, (size_t)(cnt * stride + 256) * sizeof(float)));
+  else ISL_HIP(hipMemset(idx->d_emb + n * stride, 0, 256 * sizeof(float)));
+  hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (stride == d) ISL_HIP(hipMemcpy(at, rows, (size_t)cnt * d * 4, kind));
+  else ISL_HIP(hipMemcpy2D(at, stride * 4, rows, d * 4, d * 4, cnt, kind));
+  // norm_b of cosine_distance (distance.rs:79) depends on the row alone: computed once, in the
+  // reference's left-to-right order, and reused by every search
+  using namespace isl_dev;
+  size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
+  uint32_t grid = (uint32_t)std::min<uint64_t>((cnt + 63) / 64, 8192);
+  hipLaunchKernelGGL(row_norm2_kernel, dim3(grid), dim3(64), lds, 0, at, cnt, (uint32_t)d, stride,
+                     idx->d_norm2 + first);
+  ISL_HIP(hipGetLastError());
+  ISL_HIP(hipDeviceSynchronize());
+  return ISL_OK;
+}
+
 // InMemoryEmbeddingProvider::new, leann.rs:111-120
 isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
                               int32_t dtype, int32_t mem) {
@@ -729,30 +751,13 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
     return ISL_OK;
   }
   uint64_t stride = (d + 3) / 4 * 4;  // rows start 16-byte aligned
-  size_t bytes = (size_t)(n * stride + 256) * sizeof(float);  // slack for whole-slab reads
-  ISL_TRY(idx->d_emb.reserve(n * stride + 256));
-  if (stride != d) ISL_HIP(hipMemset(idx->d_emb, 0, bytes));
-  else ISL_HIP(hipMemset(idx->d_emb + n * stride, 0, 256 * sizeof(float)));
-  hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (stride == d) ISL_HIP(hipMemcpy(idx->d_emb, rows, (size_t)n * d * 4, kind));
-  else ISL_HIP(hipMemcpy2D(idx->d_emb, stride * 4, rows, d * 4, d * 4, n, kind));
+  ISL_TRY(idx->d_emb.reserve(n * stride + 256));  // slack for whole-slab reads
+  idx->d_norm2.reset();
+  ISL_TRY(idx->d_norm2.reserve(n));
   idx->nvec = n;
   idx->emb_d = d;
   idx->emb_stride = stride;
-  // norm_b of cosine_distance (distance.rs:79) depends on the row alone: computed once, in the
-  // reference's left-to-right order, and reused by every search
-  idx->d_norm2.reset();
-  ISL_TRY(idx->d_norm2.reserve(n));
-  {
-    using namespace isl_dev;
-    size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
-    uint32_t grid = (uint32_t)std::min<uint64_t>((n + 63) / 64, 8192);
-    hipLaunchKernelGGL(row_norm2_kernel, dim3(grid), dim3(64), lds, 0, idx->d_emb.get(), n, (uint32_t)d,
-                       stride, idx->d_norm2.get());
-    ISL_HIP(hipGetLastError());
-    ISL_HIP(hipDeviceSynchronize());
-  }
-  return ISL_OK;
+  return upload_f32_rows(idx, 0, static_cast<const float*>(rows), mem);
 }
 
 // (re)allocates the recompute provider's row cache: slab, per-slot norms, slot map, owners
@@ -849,3 +854,25 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
 }
 
 }  // extern "C"
+
+// The f32 provider of a graph that grows (Scaffold::open over rows from two sources): one table of
+// old->nvec + n_new rows, the first of them copied on the device from `old` together with their norms (a
+// row's norm is a function of the row alone: the copied value is the bits a recomputation would give), the
+// rest taken from `rows` as isl_set_embeddings takes them (upload_f32_rows).  `idx` is a fresh construction graph.
+isl_status isl::set_grown_embeddings(isl_index* idx, const isl_index* old, const float* rows, uint64_t n_new,
+                                     uint64_t d, int32_t mem) {
+  const uint64_t n0 = old->nvec, n = n0 + n_new;
+  const uint64_t stride = (d + 3) / 4 * 4;
+  if (!old->d_emb || !old->d_norm2 || old->emb_d != d || old->emb_stride != stride)
+    return fail(ISL_ERR_UNSUPPORTED, "the graph's rows are not resident f32 rows of this dimension");
+  ISL_TRY(use_device(idx->device));
+  std::lock_guard<std::mutex> lock(idx->mu);
+  ISL_TRY(idx->d_emb.reserve(n * stride + 256));
+  ISL_TRY(idx->d_norm2.reserve(n));
+  ISL_HIP(hipMemcpy(idx->d_emb, old->d_emb, (size_t)n0 * stride * 4, hipMemcpyDeviceToDevice));
+  ISL_HIP(hipMemcpy(idx->d_norm2, old->d_norm2, (size_t)n0 * 4, hipMemcpyDeviceToDevice));
+  idx->nvec = n;
+  idx->emb_d = d;
+  idx->emb_stride = stride;
+  return upload_f32_rows(idx, n0, rows, mem);
+}

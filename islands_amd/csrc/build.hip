@@ -390,6 +390,30 @@ __global__ void ell_to_csr_kernel(const uint32_t* __restrict__ ell, const uint32
   for (uint32_t i = lane; i < deg[row]; i += 64) adj[off[row] + i] = ell[row * W + i];
 }
 
+// The inverse, for a finished graph that takes more nodes (isl_hnsw_insert): one wave per row reads the
+// row's CSR slice, lane after lane, into its table row and leaves the degree.  Lists of up to 128 ids take
+// two slices of 64.  Nothing is written outside the row: what does not fit raises a flag instead.
+__global__ __launch_bounds__(256) void csr_to_table_kernel(const uint64_t* __restrict__ off,
+                                                           const uint32_t* __restrict__ adj, uint64_t nnz,
+                                                           uint64_t n0, uint32_t W, uint32_t* __restrict__ ell,
+                                                           uint32_t* __restrict__ deg, uint32_t* __restrict__ flag) {
+  const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (row >= n0) return;
+  const uint64_t s = off[row], e = off[row + 1];
+  uint32_t dg = 0, bad = 0;
+  if (e < s || e > nnz) bad = 2u;
+  else if (e - s > W - 1) { bad = 1u; dg = W - 1; }
+  else dg = (uint32_t)(e - s);
+  for (uint32_t i = lane; i < dg; i += 64) {
+    uint32_t id = adj[s + i];
+    if (id >= n0) { bad |= 4u; id = 0; }
+    ell[row * W + i] = id;
+  }
+  if (bad) atomicOr(flag, bad);
+  if (lane == 0) deg[row] = dg;
+}
+
 __global__ void gather_rows_kernel(const float* __restrict__ emb, uint64_t stride, uint32_t d,
                                    uint64_t id0, uint32_t B, float* __restrict__ out) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -462,7 +486,8 @@ isl_status Scaffold::alloc_bytes(void** out, uint64_t bytes, bool zero, bool kep
 }
 
 isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw_, const float* vectors,
-                          uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef) {
+                          uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef,
+                          const isl_index* old) {
   ISL_TRY(isl_index_new(&cfg, &g));
   g->cfg.prune_ratio = 0.0f;  // construction searches do not prune (leann.rs:692-749)
   g->is_hnsw = hnsw_;         // HnswGraph heap order: distance alone
@@ -472,7 +497,8 @@ isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& 
   g->has_dimension = true;
   g->dimension = d;
   g->max_degree = m0;  // the widest row a construction search can meet: a row is back at <= m0 ids before the next search
-  ISL_TRY(isl_set_embeddings(g, vectors, n, d, ISL_DTYPE_F32, mem));
+  if (old) ISL_TRY(isl::set_grown_embeddings(g, old, vectors, n - old->nvec, d, mem));
+  else ISL_TRY(isl_set_embeddings(g, vectors, n, d, ISL_DTYPE_F32, mem));
   hnsw = hnsw_;
   diverse = opts.select_rule == ISL_SELECT_DIVERSE;
   ISL_TRY(alloc(&p.lock, n, true));
@@ -511,6 +537,15 @@ isl_status Scaffold::insert(const Table& t, uint32_t cnt, bool locking, uint64_t
     launch_link(metric, false, hnsw, cnt, link_lds(d), p);
   }
   if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "builder launch failed");
+  return ISL_OK;
+}
+
+isl_status Scaffold::csr_to_table(const Table& t, const uint64_t* off, const uint32_t* adj, uint64_t nnz, uint64_t n0,
+                                  uint32_t* d_flag) {
+  if (!n0) return ISL_OK;
+  hipLaunchKernelGGL(csr_to_table_kernel, dim3((uint32_t)((n0 + 3) / 4)), dim3(256), 0, 0, off, adj, nnz, n0, t.M + 1,
+                     t.ell, t.deg, d_flag);
+  if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "table import launch failed");
   return ISL_OK;
 }
 

@@ -93,13 +93,22 @@ struct Scaffold {
   isl_status alloc_bytes(void** out, uint64_t bytes, bool zero, bool kept);
   // The construction graph over `vectors` and the buffers of steps of up to B nodes, rows of up to m0 ids.
   // cfg: metric (and, for LeannIndex::build, the hub rule); opts: the selection rule.
+  // With `old` (a finished graph that grows, isl_hnsw_insert) the rows come from two sources: the first
+  // old->nvec of the n are old's rows and norms, copied on the device; `vectors` holds the n - old->nvec new ones.
   isl_status open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw, const float* vectors,
-                  uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef);
+                  uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef,
+                  const isl_index* old = nullptr);
   // Inserts `cnt` nodes on table `t`, their rows being in qbuf: construction search over the table, selection
   // (truncation / hub rule, or select()), links both ways.  The nodes are id0 .. id0 + cnt - 1, or node_ids[]
   // on `layer` of an HnswGraph.  Returns once the kernels are launched.
   isl_status insert(const Table& t, uint32_t cnt, bool locking, uint64_t id0, const uint32_t* node_ids = nullptr,
                     uint32_t layer = 0);
+  // CSR arrays of a finished layer -> the first n0 rows of table `t` (one wave per row), the way back in
+  // for a graph that grows.  *d_flag (device, zeroed by the caller) collects what the table cannot take:
+  // 1 = a list longer than t.M, 2 = offsets that do not fit `nnz`, 4 = an id that is not below n0; such a
+  // list is cut or left out, never written past its row.
+  isl_status csr_to_table(const Table& t, const uint64_t* off, const uint32_t* adj, uint64_t nnz, uint64_t n0,
+                          uint32_t* d_flag);
   // fixed-width table -> CSR arrays on the device (one wave per row)
   isl_status table_to_csr(const Table& t, uint64_t n, bool kept, uint64_t** off, uint32_t** adj);
   // the finished index takes over the rows (and their norms) of the construction graph

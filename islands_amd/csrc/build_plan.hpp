@@ -37,16 +37,17 @@ struct Step {
   uint32_t top;  // the step's highest level
 };
 
-// ramp() nodes per step from node 1 on (node 0 starts the graph), cut so that a node above the current top
-// layer is the only node of its step.  All-zero levels (LeannIndex::build, whose levels do not shape the
-// graph) are never cut and leave `order` the identity.
-inline void plan_steps(const std::vector<uint32_t>& lv, uint64_t batch, std::vector<Step>& steps,
-                       std::vector<uint32_t>& order) {
+// ramp() nodes per step for nodes n0 .. n-1 of `lv` (all n levels), the graph holding nodes 0 .. n0-1 with top
+// layer max_level0; cut so that a node above the current top layer is the only node of its step.  n0 = 0 is
+// the empty graph: node 0 starts it (no step) and the plan begins at node 1 under lv[0].  All-zero levels
+// (LeannIndex::build, whose levels do not shape the graph) are never cut and leave `order` the identity.
+inline void plan_steps_from(const std::vector<uint32_t>& lv, uint64_t n0, uint32_t max_level0, uint64_t batch,
+                            std::vector<Step>& steps, std::vector<uint32_t>& order) {
   const uint64_t n = lv.size();
   order.resize(n);
   for (uint64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;
-  uint32_t max_level = n ? lv[0] : 0;
-  for (uint64_t id0 = 1; id0 < n;) {
+  uint32_t max_level = n0 ? max_level0 : (n ? lv[0] : 0);
+  for (uint64_t id0 = n0 ? n0 : 1; id0 < n;) {
     uint64_t nb = ramp(batch, n, id0);
     if (lv[id0] > max_level) {
       nb = 1;
@@ -62,6 +63,12 @@ inline void plan_steps(const std::vector<uint32_t>& lv, uint64_t batch, std::vec
     max_level = std::max(max_level, top);
     id0 += nb;
   }
+}
+
+// the whole collection: from node 1 on, node 0 having started the graph
+inline void plan_steps(const std::vector<uint32_t>& lv, uint64_t batch, std::vector<Step>& steps,
+                       std::vector<uint32_t>& order) {
+  plan_steps_from(lv, 1, lv.empty() ? 0 : lv[0], batch, steps, order);
 }
 
 // the most nodes any step inserts (>= 1): what the per-step buffers are sized for

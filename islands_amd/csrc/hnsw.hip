@@ -120,6 +120,7 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
   h->m = m; h->m0 = m0; h->ef_construction = ef_construction; h->dim = d;
   h->ml = 1.0 / std::log(16.0);  // HnswConfig::default(), hnsw.rs:37-48 (from_bytes: as parsed)
   h->max_layers = 16;
+  h->device = device;
   auto bail = [&](isl_status st) { isl_hnsw_free(h); return st; };
   isl_leann_config cfg;
   isl_leann_config_paper_default(&cfg);

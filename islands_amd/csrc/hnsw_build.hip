@@ -1,5 +1,6 @@
-// HnswGraph::insert on the device (src/core/hnsw.rs:214-329): the descent kernel, its gather and isl_hnsw_build.
-// (What reads a finished graph back -- levels, lists, rows, to_bytes -- is hnsw.hip's.)
+// HnswGraph::insert on the device (src/core/hnsw.rs:214-329): the descent kernel, its gather, isl_hnsw_build (a
+// whole collection) and isl_hnsw_insert (more rows into an existing graph) -- one loop, grow(), entered at node 0
+// or at the graph's len.  (What reads a finished graph back -- levels, lists, rows, to_bytes -- is hnsw.hip's.)
 //
 // The graph under construction is one fixed-width table per layer ([n][M_L + 1] ids + a degree array;
 // M_L = m0 on layer 0, m above), the layout the search kernels already read during LeannIndex::build.  A
@@ -16,6 +17,9 @@
 // whole plan is laid out once (plan_steps, build_plan.hpp): the nodes of a step sorted by level, highest first
 // -- the nodes that have layer L are then a prefix of the step.
 // With batch = 1 and ISL_SELECT_REFERENCE this is the reference's construction, list by list.
+// A graph that grows returns to this layout first: its CSR layers are written back into tables of len + n_new
+// rows (Scaffold::csr_to_table), its rows are copied beside the new ones, and the plan starts at node len.  The
+// grown graph is built beside the old one and swapped into the handle at the end.
 #include "device_common.hip.h"
 #include "build_internal.hpp"
 
@@ -123,12 +127,17 @@ void isl_hnsw_config_default(isl_hnsw_config* c) {  // hnsw.rs:37-48
   c->max_layers = 16;
 }
 
-isl_status isl_hnsw_random_levels(uint64_t seed, uint64_t n, double ml, uint64_t max_layers, uint64_t* out) {
+}  // extern "C"
+
+namespace {
+
+// out[i] = the level of position first + i of the `seed` stream (isl_hnsw_random_levels is first = 0)
+isl_status random_levels_at(uint64_t seed, uint64_t first, uint64_t n, double ml, uint64_t max_layers, uint64_t* out) {
   if (!out && n) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   if (max_layers == 0 || !std::isfinite(ml) || ml < 0.0)
     return isl::fail(ISL_ERR_INVALID_ARGUMENT, "isl_hnsw_random_levels: max_layers >= 1 and a finite ml >= 0");
   for (uint64_t i = 0; i < n; ++i) {
-    uint64_t z = seed + (i + 1) * 0x9E3779B97F4A7C15ull;  // splitmix64
+    uint64_t z = seed + (first + i + 1) * 0x9E3779B97F4A7C15ull;  // splitmix64
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z ^= z >> 31;
@@ -139,51 +148,46 @@ isl_status isl_hnsw_random_levels(uint64_t seed, uint64_t n, double ml, uint64_t
   return ISL_OK;
 }
 
-isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options* opts_in, const float* vectors,
-                          uint64_t n, uint64_t d, const uint64_t* levels_in, uint64_t level_seed, int32_t mem,
-                          int32_t device, isl_hnsw** out) {
+// The levels of all n nodes of the graph a call leaves behind: those of `old` (NULL: an empty graph), then
+// the new nodes' -- as handed in, or positions n0 .. n-1 of the seed's stream -- with `top`, the highest layer
+// of that graph, and the checks that need nothing but them.  (isl_hnsw_insert refuses a handle whose levels do
+// not match its layers, such as one made without levels that has layers above 0.)
+isl_status all_levels(const isl_index* old, const isl_hnsw_config& cfg, uint64_t n, const uint64_t* levels_in,
+                      uint64_t level_seed, std::vector<uint64_t>& lv, uint64_t& top) {
   using isl::fail;
-  if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
-  isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
-  isl_hnsw_config cfg;
-  if (cfg_in) cfg = *cfg_in;
-  else isl_hnsw_config_default(&cfg);
-  ISL_TRY(isl::hnsw_config_validate(cfg.m, cfg.m0, cfg.ef_construction, cfg.metric));
-  if (n == 0) {  // HnswGraph::new: no nodes, no entry point, no dimension
-    ISL_TRY(isl_hnsw_from_layers(cfg.m, cfg.m0, cfg.ef_construction, (int32_t)cfg.metric, 0, 0, 0, nullptr, nullptr,
-                                 nullptr, 0, 0, 0, nullptr, device, out));
-    (*out)->ml = cfg.ml;
-    (*out)->max_layers = cfg.max_layers;
-    return ISL_OK;
-  }
-  if (d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
-  std::vector<uint64_t> drawn;
-  if (!levels_in) {
-    drawn.resize(n);
-    ISL_TRY(isl_hnsw_random_levels(level_seed, n, cfg.ml, cfg.max_layers, drawn.data()));
-    levels_in = drawn.data();
-  }
-  uint64_t top = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    if (levels_in[i] >= cfg.max_layers)
-      return fail(ISL_ERR_INVALID_ARGUMENT, "levels[%llu] = %llu is not below max_layers = %llu", (unsigned long long)i,
-                  (unsigned long long)levels_in[i], (unsigned long long)cfg.max_layers);
-    top = std::max(top, levels_in[i]);
+  const uint64_t n0 = old ? old->num_nodes : 0;
+  lv.assign(n, 0);
+  for (uint64_t i = 0; i < n0 && i < old->levels.size(); ++i) lv[i] = old->levels[i];
+  if (levels_in) std::copy(levels_in, levels_in + (n - n0), lv.begin() + n0);
+  else ISL_TRY(random_levels_at(level_seed, n0, n - n0, cfg.ml, cfg.max_layers, lv.data() + n0));
+  top = old ? old->max_level : 0;  // what the old nodes reach: checked when the handle was made
+  for (uint64_t i = n0; i < n; ++i) {
+    if (lv[i] >= cfg.max_layers)
+      return fail(ISL_ERR_INVALID_ARGUMENT, "levels[%llu] = %llu is not below max_layers = %llu",
+                  (unsigned long long)(i - n0), (unsigned long long)lv[i], (unsigned long long)cfg.max_layers);
+    top = std::max(top, lv[i]);
   }
   if (const char* why = isl_plan::shape_limit(cfg.m0, cfg.ef_construction, n)) return fail(ISL_ERR_UNSUPPORTED, "%s", why);
   if (top >= 64) return fail(ISL_ERR_UNSUPPORTED, "the device builder keeps up to 64 layers");
+  return ISL_OK;
+}
+
+// HnswGraph::insert for nodes n0 .. n-1 of a graph that holds n0 (`from`: a finished graph with at least one
+// node, whose CSR layers return to the builder's tables; NULL: nothing, node 0 starts the graph).  One loop
+// over the plan's steps -- descent, per-layer gather, Scaffold::insert -- then compaction and
+// attach_upper_layers.  `from` is only read; the graph of all n nodes leaves in `out`, built beside it.
+isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const isl_hnsw* from, const float* vectors,
+                uint64_t n_new, uint64_t d, const std::vector<uint64_t>& levels, uint64_t top, int32_t mem,
+                int32_t device, std::unique_ptr<isl_hnsw>& out) {
+  using isl::fail;
+  const isl_index* old = from ? from->core : nullptr;
+  const uint64_t n0 = old ? old->num_nodes : 0, n = n0 + n_new;
   ISL_TRY(isl::use_device(device));
 
-  std::vector<uint32_t> lv(n);
-  for (uint64_t i = 0; i < n; ++i) lv[i] = (uint32_t)levels_in[i];
+  const std::vector<uint32_t> lv(levels.begin(), levels.end());  // what the planner and the kernels read
   std::vector<isl_plan::Step> steps;
   std::vector<uint32_t> order;
-  isl_plan::plan_steps(lv, opts.batch ? opts.batch : 1, steps, order);
+  isl_plan::plan_steps_from(lv, n0, old ? (uint32_t)old->max_level : 0u, opts.batch ? opts.batch : 1, steps, order);
   const uint64_t B = isl_plan::largest_step(steps);
 
   const uint32_t m = (uint32_t)cfg.m, m0 = (uint32_t)cfg.m0, ef = (uint32_t)cfg.ef_construction;
@@ -193,7 +197,7 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options
   lcfg.metric = cfg.metric;
   lcfg.prune_ratio = 0.0f;
   isl_build::Scaffold c;
-  ISL_TRY(c.open(lcfg, opts, true, vectors, n, d, mem, device, B, m0, ef));
+  ISL_TRY(c.open(lcfg, opts, true, vectors, n, d, mem, device, B, m0, ef, old));
   isl_index* g = c.g;
 
   // one table per layer, and what the descent and the per-layer gathers read
@@ -205,6 +209,27 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options
     ISL_TRY(c.alloc(&tab[L].deg, n, true));
     h_ell[L] = tab[L].ell;
     h_deg[L] = tab[L].deg;
+  }
+  if (old) {
+    // the finished layers return to the tables: layer 0 from the core index's CSR, the layers above from the
+    // descent's arrays.  Rows n0 .. n-1, nodes that lack a layer and layers the old graph did not have keep
+    // degree 0.
+    uint32_t* d_flag = nullptr;
+    ISL_TRY(c.alloc(&d_flag, 1, true));
+    ISL_TRY(c.csr_to_table(tab[0], old->d_off, old->d_adj, old->nnz, n0, d_flag));
+    for (uint64_t L = 1; L <= old->max_level && L < from->layer_off.size(); ++L) {
+      uint64_t nnz = 0;
+      if (hipMemcpy(&nnz, from->layer_off[L] + n0, 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(ISL_ERR_DEVICE, "cannot read the offsets of layer %llu", (unsigned long long)L);
+      ISL_TRY(c.csr_to_table(tab[L], from->layer_off[L], from->layer_adj[L], nnz, n0, d_flag));
+    }
+    uint32_t flag = 0;
+    if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(ISL_ERR_DEVICE, "importing the graph's layers failed");
+    if (flag & 1u)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the graph has a list longer than its layer keeps (m0 = %u on "
+                  "layer 0, m = %u above)", m0, m);
+    if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the graph's layers name ids or offsets outside it");
   }
   uint32_t **d_tab = nullptr, **d_deg = nullptr;
   uint32_t *d_lv = nullptr, *d_order = nullptr, *cur_of = nullptr, *evals_of = nullptr;
@@ -229,8 +254,9 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options
   c.p.node_levels = d_lv;
   c.p.cur_of = cur_of;
 
-  // node 0: entry point, max_level = its level, every list empty (hnsw.rs:240-245)
-  uint64_t entry = 0, max_level = lv[0];
+  // the graph as the first step finds it: the old one's entry point and top layer, or node 0 alone -- entry
+  // point, max_level = its level, every list empty (hnsw.rs:240-245)
+  uint64_t entry = old ? old->entry_point : 0, max_level = old ? old->max_level : lv[0];
   for (const isl_plan::Step& s : steps) {
     const uint32_t* ids = d_order + s.first;
     dp.node_ids = ids; dp.B = s.count; dp.entry = (uint32_t)entry; dp.max_level = (uint32_t)max_level;
@@ -269,15 +295,132 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options
   }
   c.res->is_hnsw = true;
   c.res->max_level = max_level;
-  c.res->levels.assign(levels_in, levels_in + n);
+  c.res->levels = levels;
   std::unique_ptr<isl_hnsw> h(new isl_hnsw());
   h->core = c.res;
   h->m = cfg.m; h->m0 = cfg.m0; h->ef_construction = cfg.ef_construction; h->dim = d;
   h->ml = cfg.ml; h->max_layers = cfg.max_layers;
+  h->device = device;
   ISL_TRY(isl::attach_upper_layers(h.get(), offs, adjs));
   c.hand_rows_to(c.res);
   c.release();
+  out = std::move(h);
+  return ISL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+isl_status isl_hnsw_random_levels(uint64_t seed, uint64_t n, double ml, uint64_t max_layers, uint64_t* out) {
+  return random_levels_at(seed, 0, n, ml, max_layers, out);
+}
+
+isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options* opts_in, const float* vectors,
+                          uint64_t n, uint64_t d, const uint64_t* levels_in, uint64_t level_seed, int32_t mem,
+                          int32_t device, isl_hnsw** out) {
+  using isl::fail;
+  if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  isl_build_options opts;
+  isl_build_options_default(&opts);
+  if (opts_in) {
+    ISL_TRY(isl_build::check_build_options(opts_in, true));
+    opts = *opts_in;
+  }
+  isl_hnsw_config cfg;
+  if (cfg_in) cfg = *cfg_in;
+  else isl_hnsw_config_default(&cfg);
+  ISL_TRY(isl::hnsw_config_validate(cfg.m, cfg.m0, cfg.ef_construction, cfg.metric));
+  if (n == 0) {  // HnswGraph::new: no nodes, no entry point, no dimension
+    ISL_TRY(isl_hnsw_from_layers(cfg.m, cfg.m0, cfg.ef_construction, (int32_t)cfg.metric, 0, 0, 0, nullptr, nullptr,
+                                 nullptr, 0, 0, 0, nullptr, device, out));
+    (*out)->ml = cfg.ml;
+    (*out)->max_layers = cfg.max_layers;
+    return ISL_OK;
+  }
+  if (d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
+  std::vector<uint64_t> levels;
+  uint64_t top = 0;
+  ISL_TRY(all_levels(nullptr, cfg, n, levels_in, level_seed, levels, top));
+  std::unique_ptr<isl_hnsw> h;
+  ISL_TRY(grow(cfg, opts, nullptr, vectors, n, d, levels, top, mem, device, h));  // insert into nothing
   *out = h.release();
+  return ISL_OK;
+}
+
+isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const float* vectors, uint64_t n_new,
+                           uint64_t d, const uint64_t* levels_in, uint64_t level_seed, int32_t mem,
+                           uint64_t* first_id) {
+  using isl::fail;
+  if (!h || !h->core || (!vectors && n_new)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  isl_build_options opts;
+  isl_build_options_default(&opts);
+  if (opts_in) {
+    ISL_TRY(isl_build::check_build_options(opts_in, true));
+    opts = *opts_in;
+  }
+  const isl_index* core = h->core;
+  const uint64_t n0 = core->num_nodes;
+  if (n_new == 0) {
+    if (first_id) *first_id = n0;
+    return ISL_OK;
+  }
+  if (n0 && d != h->dim) return isl::fail_dim(h->dim, d);  // hnsw.rs:216-222
+  if (d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
+  isl_hnsw_config cfg;
+  cfg.m = h->m; cfg.m0 = h->m0; cfg.ef_construction = h->ef_construction;
+  cfg.ml = h->ml; cfg.metric = core->cfg.metric; cfg.max_layers = h->max_layers;
+  std::vector<uint64_t> levels;
+  uint64_t top = 0;
+  ISL_TRY(all_levels(n0 ? core : nullptr, cfg, n0 + n_new, levels_in, level_seed, levels, top));
+  if (n0) {
+    if (core->recompute || core->d_emb16 || !core->d_emb || !core->d_norm2 || core->nvec != n0 || core->emb_d != d ||
+        core->device < 0)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert needs the graph's float32 rows resident on the device");
+    if (!core->has_entry) return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the graph has nodes and no entry point");
+    // the link kernel takes "has the layer" from the levels: a handle made without them (all 0) or with levels
+    // that do not reach its top layer would quietly grow into another graph
+    if (core->levels.size() != n0 || core->entry_point >= n0 || core->levels[core->entry_point] != core->max_level ||
+        *std::max_element(core->levels.begin(), core->levels.end()) != core->max_level)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the nodes' levels do not match the graph's layers (max_level "
+                  "%llu; the entry point's level must equal it and no level may exceed it) -- was the handle made "
+                  "without levels?", (unsigned long long)core->max_level);
+    if (core->max_degree > h->m0)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: a layer-0 list of %u ids is longer than m0 = %llu",
+                  core->max_degree, (unsigned long long)h->m0);
+    if (core->host_csr_valid && core->node_offsets.size() == n0 + 1 && core->node_offsets[n0] != core->nnz)
+      return fail(ISL_ERR_UNSUPPORTED,
+                  "isl_hnsw_insert: the device copy of layer 0 is not the lists verbatim (ids repeated inside a list "
+                  "were removed at upload)");
+  }
+  {  // the &mut self of the reference: not beside a search on the same handle
+    std::lock_guard<std::mutex> lock(core->mu);
+    if (isl::any_lane_busy(core))
+      return fail(ISL_ERR_SEARCH, "Search error: the graph cannot grow while searches are in flight");
+  }
+  std::unique_ptr<isl_hnsw> grown;
+  ISL_TRY(grow(cfg, opts, n0 ? h : nullptr, vectors, n_new, d, levels, top, mem, n0 ? core->device : h->device,
+               grown));
+  // the swap: the grown graph was built beside the old one, which nothing has touched so far
+  std::lock_guard<std::mutex> host_lock(h->host_mu);
+  isl_index* old = h->core;
+  {
+    std::lock_guard<std::mutex> lock(old->mu);
+    if (isl::any_lane_busy(old)) {
+      isl_index_free(grown->core);
+      return fail(ISL_ERR_SEARCH, "Search error: the graph cannot grow while searches are in flight");
+    }
+  }
+  h->core = grown->core;
+  h->layer_off.swap(grown->layer_off);
+  h->layer_adj.swap(grown->layer_adj);
+  h->dim = d;
+  h->device = h->core->device;
+  h->host_valid = false;
+  h->h_off.clear();
+  h->h_adj.clear();
+  isl_index_free(old);  // with its lanes and padded adjacency; the new core sets its own up at the first search
+  if (first_id) *first_id = n0;
   return ISL_OK;
 }
 
