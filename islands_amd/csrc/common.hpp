@@ -101,7 +101,7 @@ struct SearchWorkspace {
   DeviceBuffer<uint64_t> d_prof;    // ISL_DEBUG phase timers of the call in flight
   DeviceBuffer<uint64_t> d_tline;   // ISL_TIMELINE: [nq][2] start / end ticks of every query of the call in flight
   DeviceBuffer<uint32_t> q_entry;   // HnswGraph: [2][nq] layer-0 entry and descent evaluations per query
-  // recompute provider: the union of the calls this lane answers as one (search.hip, recompute_coalesced)
+  // recompute provider: the union of the calls this lane answers as one (search_recompute.hip, recompute_coalesced)
   DeviceBuffer<float> co_q;
   DeviceBuffer<uint64_t> co_ids;
   DeviceBuffer<float> co_dist;
@@ -248,7 +248,7 @@ struct isl_index {
   mutable std::mutex mu;  // lane claims, the exact pool, index mutation -- never held across a search
   mutable std::mutex recompute_mu;  // searches over the recompute provider share its row table
   // asynchronous calls over the recompute provider that wait for their turn: the one that gets it answers every
-  // compatible call waiting at that moment together with its own (search.hip, recompute_coalesced)
+  // compatible call waiting at that moment together with its own (search_recompute.hip, recompute_coalesced)
   struct RecJoin {
     std::mutex mu;        // guards `waiting`
     std::mutex leader;    // held by the call that is running the rounds

@@ -1,5 +1,5 @@
 // Internal view of the recompute encoder shared by encoder.hip (kernels, C ABI), api_index.hip
-// (isl_set_recompute_provider) and search.hip (the rounds that re-encode the nodes a search misses).
+// (isl_set_recompute_provider) and search_recompute.hip (the rounds that re-encode the nodes a search misses).
 #pragma once
 
 #include "common.hpp"

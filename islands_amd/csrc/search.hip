@@ -23,6 +23,9 @@
 //     HBM scratch, results in LDS) for those queries, for ef > 512, for adjacency rows longer
 //     than 64 and for NaN / -0.0 distances.
 #include "search_geometry.hpp"
+#include "search_internal.hpp"
+
+using namespace isl_lane;
 
 namespace {
 
@@ -70,7 +73,6 @@ __global__ void seed_redo_kernel(const uint32_t* __restrict__ list, uint32_t n, 
 }
 
 constexpr uint32_t kExactSlots = 32;
-constexpr uint32_t kTlPrefetchDefault = 0;  // (set from the measurement: DESIGN.md section 3.4)
 constexpr uint32_t kOvfBits = 15;
 
 // Every allocation of the search path is a reserve() that counts into the lane's alloc_events: a
@@ -105,7 +107,9 @@ hipStream_t pool_stream(int32_t device, uint32_t lane, bool* created) {
   return st;
 }
 
-isl_status ensure_lane_stream(const isl_index* idx, isl::SearchWorkspace& ws) {
+}  // namespace
+
+isl_status isl_lane::ensure_lane_stream(const isl_index* idx, isl::SearchWorkspace& ws) {
   if (ws.stream) return ISL_OK;
   bool created = false;
   hipStream_t st = pool_stream(idx->device, (uint32_t)(&ws - idx->ws), &created);
@@ -123,6 +127,12 @@ isl_status ensure_lane_stream(const isl_index* idx, isl::SearchWorkspace& ws) {
   ws.stream = st;
   return ISL_OK;
 }
+
+void isl_lane::copy_words(const uint32_t* src, uint32_t* dst, uint64_t n, uint32_t grid, uint32_t block, hipStream_t st) {
+  hipLaunchKernelGGL(copy_u32_kernel, dim3(grid), dim3(block), 0, st, src, dst, n);
+}
+
+namespace {
 
 isl_status prepare_workspace(const isl_index* idx, isl::SearchWorkspace& ws, uint32_t nq, uint32_t slots,
                              uint32_t plog_cap) {
@@ -172,9 +182,11 @@ isl_status prepare_host_staging(isl::SearchWorkspace& ws, uint64_t nq, uint64_t 
   return ws.h_count.reserve(slots, ev);
 }
 
+}  // namespace
+
 // The shared scratch pool of the heap-exact kernel (under idx->mu).  Its sizes follow the index
 // (node / row count, longest row); the setters that change those drop the pool.
-isl_status ensure_pool(const isl_index* idx, isl::SearchWorkspace& ws) {
+isl_status isl_lane::ensure_pool(const isl_index* idx, isl::SearchWorkspace& ws) {
   isl::ExactPool& pl = idx->pool;
   if (pl.slots) return ISL_OK;
   uint64_t max_id = std::max(idx->num_nodes, idx->nvec);
@@ -200,6 +212,8 @@ isl_status ensure_pool(const isl_index* idx, isl::SearchWorkspace& ws) {
   return st;
 }
 
+namespace {
+
 // CSR -> W (64 or 128) ids per node (EMPTY-padded) + degree; one wave per row
 __global__ void pad_rows_kernel(const uint64_t* __restrict__ off, const uint32_t* __restrict__ adj, uint64_t n,
                                 uint32_t W, uint32_t* __restrict__ ell, uint32_t* __restrict__ deg) {
@@ -211,13 +225,6 @@ __global__ void pad_rows_kernel(const uint64_t* __restrict__ off, const uint32_t
   for (uint32_t i = lane; i < W; i += 64) ell[row * W + i] = i < d ? adj[o0 + i] : EMPTY;
   if (lane == 0) deg[row] = d;
 }
-
-// Stream a call runs on.  OWN: the lane's non-blocking stream (host-pointer entry point).
-// USER: the caller's stream (NULL = legacy default stream, ordered after the caller's earlier
-// work on it, e.g. torch kernels that produced the queries).  OWN_AFTER_USER: the lane's stream,
-// made to wait for everything already enqueued on the caller's stream -- lets several searches
-// overlap (asynchronous entry point).
-enum class StreamMode { OWN, USER, OWN_AFTER_USER };
 
 // status / counters / work-queue heads of the call -> the lane's pinned mirrors, and for a
 // host-buffer call its answers too; one kernel behind the search kernels.
@@ -244,39 +251,8 @@ isl_status publish(isl::SearchWorkspace& ws, uint64_t nq, uint64_t k, hipStream_
   return ISL_OK;
 }
 
-// One search as its entry point received it; every pointer is a device pointer.
-struct SearchCall {
-  const float* queries = nullptr;
-  uint64_t nq = 0, d = 0, k = 0, ef = 0;
-  uint64_t* ids = nullptr;
-  float* dist = nullptr;
-  uint32_t* count = nullptr;
-  hipStream_t user_stream = nullptr;
-  StreamMode mode = StreamMode::OWN;
-  bool two_level = false;  // the two-level search with a PQ filter, re-ranking `ratio` of the approximate queue
-  float ratio = 0.0f;
-};
-hipStream_t call_stream(const isl::SearchWorkspace& ws, const SearchCall& c) {
-  return c.mode == StreamMode::USER ? c.user_stream : ws.stream;
-}
-
-// What search_sync asks of one enqueue beyond the call itself; the default is an ordinary launch
-// over all queries (asynchronous entry points, warm launches).
-struct RoundPlan {
-  // a round of the recompute provider: the RESUME kernel over `active` queries, listed in ws.qlist
-  // unless it is the first round (`listed`); `exact` queries of ws.h_xlist go straight to the
-  // heap-exact kernel's queue
-  uint32_t active = 0;
-  uint32_t exact = 0;
-  bool exact_parks = false;   // this call's queries park in the heap-exact kernel (bounded row cache)
-  bool listed = false;
-  uint32_t prefetch = 0;      // two-level search: ids a parked query names beyond its misses (0 = none)
-  // two-level search: `retry` queries (listed in ws.qlist) re-run alone with a queue window grown
-  // by `window_scale`; the PQ distance tables of the call's first launch stay
-  uint32_t retry = 0;
-  uint32_t window_scale = 1;
-  bool tables_built = false;
-};
+// (SearchCall, the call as its entry point received it, and RoundPlan, what a round asks of one enqueue:
+// search_internal.hpp)
 
 // the one switch over the fast kernel's S: each case is an object of its own (search_fast.hip)
 void launch_fast(const isl_launch::FastKernel& k, uint32_t grid, size_t lds, hipStream_t st, const SearchParams& p) {
@@ -535,12 +511,22 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   return ISL_OK;
 }
 
+// counters of the most recent call this thread completed, per index (isl_search_last_stats)
+struct LastStats { const isl_index* idx = nullptr; isl_search_stats st{}; };
+thread_local LastStats tl_last_stats;
+void note_last_stats(const isl_index* idx, const isl_search_stats& st) {
+  tl_last_stats.idx = idx;
+  tl_last_stats.st = st;
+}
+
+}  // namespace
+
 // A failure part-way through an enqueue (a launch error, publish, a lane buffer that could not grow)
 // may leave kernels of this call on the stream: they are drained before the error goes back, because
 // the caller releases the lane next and the lane's next owner rewrites its pinned buffers / may
 // reallocate what those kernels still read.
-isl_status search_enqueue(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c,
-                          const RoundPlan& plan = RoundPlan{}, bool warm = false) {
+isl_status isl_lane::search_enqueue(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c,
+                                      const RoundPlan& plan, bool warm) {
   const isl_status st = search_enqueue_impl(idx, ws, c, plan, warm);
   if (st != ISL_OK) {
     const isl::ErrorRecord keep = isl::last_error();
@@ -554,22 +540,12 @@ isl_status search_enqueue(const isl_index* idx, isl::SearchWorkspace& ws, const 
   return st;
 }
 
-// counters of the most recent call this thread completed, per index (isl_search_last_stats)
-struct LastStats { const isl_index* idx = nullptr; isl_search_stats st{}; };
-thread_local LastStats tl_last_stats;
-void note_last_stats(const isl_index* idx, const isl_search_stats& st) {
-  tl_last_stats.idx = idx;
-  tl_last_stats.st = st;
-}
-
 // Waits for the call in flight on `ws`, leaves its counters in ws.stats and turns per-query
 // failures into the CoreError the reference's sequential map would have returned.
-isl_status search_statuses(isl::SearchWorkspace& ws, uint64_t nq, bool* window_short);
-
 // defer_statuses: the per-query statuses are not final yet (a batch the recompute provider works
 // through in rounds, some of its queries not even started): the caller runs search_statuses itself.
-isl_status search_finish(const isl_index* idx, isl::SearchWorkspace& ws, uint32_t* misses = nullptr,
-                         bool* window_short = nullptr, bool defer_statuses = false) {
+isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& ws, uint32_t* misses,
+                                     bool defer_statuses) {
   if (!ws.enqueued) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "no search in flight for this token");
   ws.enqueued = false;
   const uint64_t nq = ws.nq_inflight;
@@ -652,11 +628,11 @@ isl_status search_finish(const isl_index* idx, isl::SearchWorkspace& ws, uint32_
     if (head[13]) return ISL_OK;  // a round of the recompute provider: statuses are not final yet
   }
   if (defer_statuses) return ISL_OK;
-  return search_statuses(ws, nq, window_short);
+  return search_statuses(ws, nq);
 }
 
 // per-query failures -> the CoreError the reference's sequential map would have returned
-isl_status search_statuses(isl::SearchWorkspace& ws, uint64_t nq, bool* window_short) {
+isl_status isl_lane::search_statuses(isl::SearchWorkspace& ws, uint64_t nq) {
   const uint32_t* status = ws.h_status;
   for (uint64_t i = 0; i < nq; i++) {  // first failing query wins, like the sequential map
     if (status[i] == QS_OK) continue;
@@ -664,11 +640,6 @@ isl_status search_statuses(isl::SearchWorkspace& ws, uint64_t nq, bool* window_s
       uint64_t node = 0;
       ISL_HIP(hipMemcpy(&node, ws.payload + i, 8, hipMemcpyDeviceToHost));
       return isl::fail_node(node);
-    }
-    if (status[i] == QS_SCRATCH && window_short) {  // two-level search: 7 = the queue window was too small
-      uint64_t why = 0;
-      ISL_HIP(hipMemcpy(&why, ws.payload + i, 8, hipMemcpyDeviceToHost));
-      *window_short = why == 7;
     }
     if (status[i] == QS_SCRATCH)
       return isl::fail(ISL_ERR_SEARCH, "Search error: device scratch exhausted for query %llu (candidate heap, "
@@ -680,502 +651,40 @@ isl_status search_statuses(isl::SearchWorkspace& ws, uint64_t nq, bool* window_s
   return ISL_OK;
 }
 
-// ---- recompute provider (EmbeddingProvider backed by the encoder, leann.rs:82-99) ----
-// lists each missed id once: the first reporter of an id claims its slot-map entry
-__global__ void dedupe_misses_kernel(const uint32_t* __restrict__ miss, uint32_t n,
-                                     uint32_t* __restrict__ slot_of, uint32_t* __restrict__ uniq,
-                                     uint32_t* __restrict__ uniq_count) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const uint32_t id = miss[i];
-  if (atomicCAS(&slot_of[id], kNoSlot, kSlotClaim) == kNoSlot) uniq[atomicAdd(uniq_count, 1u)] = id;
-}
+namespace {
 
-// Hands the round's unique misses their slab slots (one wave): once the slab is full a clock hand walks it and
-// skips the rows some query asked for in this round (stamp == round) -- those belong to hops that
-// are waiting for their last rows, evicting them would make the hop wait for THEM next round.  The
-// node that held a slot before loses its row.  Ids left over when a full turn finds no more free
-// slots are un-claimed and reported again next round.
-__global__ __launch_bounds__(64) void assign_slots_kernel(const uint32_t* __restrict__ uniq,
-                                                          const uint32_t* __restrict__ n_ptr,
-                                                          uint32_t round_no, uint32_t slab_rows,
-                                                          uint32_t* __restrict__ head_word,
-                                                          uint32_t* __restrict__ slot_of, uint32_t* __restrict__ owner,
-                                                          uint32_t* __restrict__ stamp, uint32_t* __restrict__ uslots,
-                                                          uint32_t* __restrict__ taken, uint32_t quantum,
-                                                          uint32_t chunk) {
-  const uint32_t lane = threadIdx.x;
-  // How many of the round's misses are encoded now: the encoder's GEMMs run whole waves of tiles over the
-  // chip's CUs, and a batch that ends a little past a full wave pays for a whole one more (860 nodes x 64
-  // tokens: 645 tiles of the hidden x hidden GEMMs = 2.52 waves on 256 CUs, 84 % of them filled).  So a
-  // round takes whole encoder passes of `chunk` nodes plus a multiple of `quantum` nodes (the largest batch
-  // whose narrowest GEMM still fits ONE wave of tiles), plus the rest when that rest nearly fills a wave
-  // anyway; what is left over is un-claimed below and reported again next round, when it is batched with
-  // that round's misses.  quantum == 0: everything (a provider whose shapes were not analysed).
-  const uint32_t n_all = *n_ptr;
-  uint32_t n = n_all;
-  if (quantum && n >= quantum) {
-    const uint32_t whole = chunk ? (n / chunk) * chunk : 0u, rem = n - whole;
-    const uint32_t r = rem % quantum;
-    n = whole + (rem - r) + (r * 10u >= quantum * 9u ? r : 0u);
-  }
-  // never-used slots first (head_word[1] counts them): nothing is evicted before the slab is full
-  uint32_t fill = head_word[1], done = 0;
-  {
-    const uint32_t t = n < slab_rows - fill ? n : slab_rows - fill;
-    for (uint32_t i = lane; i < t; i += 64) {
-      const uint32_t id = uniq[i], s = fill + i;
-      owner[s] = id;
-      slot_of[id] = s;
-      stamp[s] = round_no;
-      uslots[i] = s;
-    }
-    done = t;
-    fill += t;
-  }
-  uint32_t pos = *head_word % slab_rows, walked = 0;
-  while (done < n && walked < slab_rows) {
-    const uint32_t step = slab_rows - walked < 64u ? slab_rows - walked : 64u;
-    const uint32_t s = (pos + lane) % slab_rows;
-    const bool free_ = lane < step && stamp[s] != round_no;
-    const uint64_t fm = ballot(free_);
-    const uint32_t i = done + (uint32_t)__popcll(fm & ((1ull << lane) - 1ull));
-    if (free_ && i < n) {
-      const uint32_t id = uniq[i];
-      const uint32_t old = owner[s];
-      if (old != kNoSlot) slot_of[old] = kNoSlot;  // (never one of this round's ids: those were absent)
-      owner[s] = id;
-      slot_of[id] = s;
-      stamp[s] = round_no;
-      uslots[i] = s;
-    }
-    done += (uint32_t)__popcll(fm);
-    pos = (pos + step) % slab_rows;
-    walked += step;
-  }
-  if (done > n) done = n;
-  for (uint32_t i = done + lane; i < n_all; i += 64) slot_of[uniq[i]] = kNoSlot;  // (the quantum's left-overs too)
-  if (lane == 0) { head_word[0] = pos; head_word[1] = fill; *taken = done; }
-}
-
-// norm2[id] = sum_j row[id][j]^2 in the reference's order for the freshly encoded rows
-__global__ __launch_bounds__(64) void row_norm2_list_kernel(const float* __restrict__ emb, uint64_t stride,
-                                                            uint32_t d, const uint32_t* __restrict__ ids,
-                                                            uint32_t n, float* __restrict__ norm2) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  float* tile = reinterpret_cast<float*>(smem);
-  const uint32_t lane = threadIdx.x;
-  for (uint32_t base = blockIdx.x * 64; base < n; base += gridDim.x * 64) {
-    const uint32_t R = n - base < 64 ? n - base : 64;
-    const uint32_t uid = lane < R ? ids[base + lane] : 0u;
-    const float v = wave_distances<METRIC_SUMSQ_RAW>(emb, stride, d, uid, R, tile, tile, 0.f);
-    if (lane < R) norm2[uid] = v;
-  }
-}
-
-// query lists of a lane (rounds of the recompute provider, retries of the two-level search)
-isl_status ensure_qlist(isl::SearchWorkspace& ws, uint64_t nq) {
-  uint64_t* const ev = &ws.alloc_events;
-  const uint64_t c = nq < 1024 ? 1024 : nq;
-  ISL_TRY(ws.qflag.reserve(c, ev));
-  ISL_TRY(ws.qlist.reserve(c, ev));
-  ISL_TRY(ws.xslot.reserve(c, ev));
-  ISL_TRY(ws.h_qlist.reserve(c, ev));
-  return ws.h_xlist.reserve(c, ev);
-}
-
-// Two-level search: the queries of the finished launch whose approximate-queue window was too small
-// (QS_SCRATCH with payload 7) -> ws.h_qlist[0, *count).
-isl_status tl_collect_short(isl::SearchWorkspace& ws, uint64_t nq, uint32_t* count) {
-  *count = 0;
-  bool any = false;
-  for (uint64_t i = 0; i < nq && !any; ++i) any = ws.h_status[i] == QS_SCRATCH;
-  if (!any) return ISL_OK;
-  ISL_TRY(ensure_qlist(ws, nq));
-  std::vector<uint64_t> pay(nq);
-  ISL_HIP(hipMemcpy(pay.data(), ws.payload, nq * 8, hipMemcpyDeviceToHost));
-  uint32_t n = 0;
-  for (uint64_t i = 0; i < nq; ++i)
-    if (ws.h_status[i] == QS_SCRATCH && pay[i] == 7) ws.h_qlist[n++] = (uint32_t)i;
-  *count = n;
-  return ISL_OK;
-}
-
-isl_status prepare_recompute(isl::SearchWorkspace& ws, uint64_t nq, uint64_t state_words_per_query) {
-  const uint64_t cap = std::min<uint64_t>(nq * 128 + 64, 0xFFFFFFF0ull);  // a hop keeps up to 128 rows
-  const uint64_t pcap = nq * 8 + 64;  // + the ids parked two-level queries expect to promote next (behind miss[cap])
-  if (ws.miss_cap < cap || ws.pref_cap < pcap) {
-    // the prefetch ids sit behind miss[miss_cap]: a new split means new arrays
-    ws.miss.reset(); ws.uniq.reset(); ws.uslots.reset(); ws.uniq_count.reset();
-    ws.miss_cap = 0;
-    ws.pref_cap = 0;
-    uint64_t* const ev = &ws.alloc_events;
-    ISL_TRY(ws.miss.reserve(cap + pcap, ev));
-    ISL_TRY(ws.uniq.reserve(cap + pcap, ev));
-    ISL_TRY(ws.uslots.reserve(cap + pcap, ev));
-    ISL_TRY(ws.uniq_count.reserve(1, ev));
-    ws.miss_cap = cap;
-    ws.pref_cap = pcap;
-  }
-  ISL_TRY(ensure_qlist(ws, nq));
-  return ws.qstate.reserve(std::max<uint64_t>(nq, 1) * state_words_per_query, &ws.alloc_events);
-}
-
-// One synchronous search on a claimed lane.  With the in-memory provider: enqueue + finish.  With
-// the recompute provider: rounds of (search; every query that needs an absent row reports it and
-// stops) -> (encode the reported nodes once each) until a round completes without a miss; that
-// last round is an ordinary search over materialised rows, so ids, distances, counters and error
-// behaviour are those of the in-memory provider holding the same embeddings.
-isl_status search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c) {
-  const uint64_t nq = c.nq;
+// The in-memory provider: enqueue + finish.  Two-level search: a query whose approximate queue outgrew the
+// LDS window is never answered differently: the queries it happened to are run again, alone, with a window
+// four times the size (plan.retry of them, plan.window_scale).
+isl_status search_resident(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c) {
   const bool tl = c.two_level;
-  // two-level search: a query whose approximate queue outgrew the LDS window is never answered
-  // differently: the queries it happened to are run again, alone, with a window four times the size
-  // (plan.retry of them, plan.window_scale)
   RoundPlan plan;
-  if (!idx->recompute) {
-    double ms_total = 0.0;
-    for (;;) {
-      ISL_TRY(search_enqueue(idx, ws, c, plan));
-      plan.tables_built = tl;
-      ISL_TRY(search_finish(idx, ws, nullptr, nullptr, tl));
-      if (!tl) return ISL_OK;  // (statuses evaluated by search_finish)
-      ms_total += ws.stats.kernel_ms;
-      uint32_t nshort = 0;
-      ISL_TRY(tl_collect_short(ws, nq, &nshort));
-      if (nshort && plan.window_scale < 64) {
-        plan.window_scale *= 4;
-        plan.retry = nshort;
-        hipStream_t st = call_stream(ws, c);
-        hipLaunchKernelGGL(copy_u32_kernel, dim3(16), dim3(256), 0, st, ws.h_qlist, ws.qlist, (uint64_t)nshort);
-        ISL_HIP(hipGetLastError());
-        continue;
-      }
-      ws.stats.kernel_ms = ms_total;
-      return search_statuses(ws, nq, nullptr);
-    }
-  }
-  // the rounds rewrite the provider's row cache: one recompute search at a time
-  std::lock_guard<std::mutex> rlock(idx->recompute_mu);
-  CallGeometry cg0;
-  {
-    const TwoLevelCall tl0{c.ratio};
-    ISL_TRY(call_geometry(idx, c.d, c.k, c.ef, tl ? &tl0 : nullptr, cg0));
-  }
-  // searches that park and resume: the wave-per-query traversal and the two-level search (the
-  // heap-exact kernel alone -- ef > 512, rows past 128 ids -- re-runs a blocked query from its start)
-  // searches park and resume: the wave-per-query traversal, the two-level search, and -- since round 3 --
-  // the heap-exact kernel (ef > 512, rows past 128 ids, tie hand-overs), whose parked queries keep their
-  // slot of the scratch pool across the rounds
-  // -- when the row cache is bounded.  With a row for every node nothing is ever evicted, a blocked query
-  // of that kernel simply starts over next round (all of them advance in parallel, where parked ones
-  // would advance 32 at a time: the pool's slots).
-  const bool exact_only = !tl && !cg0.use_fast;
-  const bool x_park = !tl && idx->slab_rows < idx->nvec;
-  const bool resumable = tl || cg0.use_fast || x_park;
-  ISL_TRY(prepare_recompute(ws, nq, tl || cg0.use_fast ? cg0.state_words : 1));  // (the heap-exact kernel parks in the pool)
-  ISL_TRY(ensure_lane_stream(idx, ws));
-  hipStream_t st = call_stream(ws, c);
-  if (!idx->keep_rows) {  // every call starts from an empty cache: each node is encoded once per call
-    ISL_HIP(hipMemsetAsync(idx->d_slot_of, 0xFF, (idx->nvec + 1) * 4, st));
-    ISL_HIP(hipMemsetAsync(idx->d_owner, 0xFF, idx->slab_rows * 4, st));
-    ISL_HIP(hipMemsetAsync(idx->d_stamp, 0, idx->slab_rows * 4, st));
-    ISL_HIP(hipMemsetAsync(idx->d_slab_head, 0, 8, st));
-  }
-  ISL_HIP(hipMemsetAsync(ws.qflag, 0, nq * 4, st));
-  ISL_HIP(hipMemsetAsync(ws.xslot, 0, nq * 4, st));
-  if (!tl) {
-    // no query is parked in the heap-exact kernel's pool yet (recompute calls run one at a time per index)
-    if (!idx->pool.slots) {
-      std::lock_guard<std::mutex> lock(idx->mu);
-      ISL_TRY(ensure_pool(idx, ws));
-    }
-    ISL_HIP(hipMemsetAsync(idx->pool.locks, 0, (size_t)idx->pool.slots * 4, st));
-  }
-  uint64_t encoded = 0, rounds = 0;
-  double kernel_ms = 0.0;
-  // Queries in flight at a time: each may hold one hop (<= 128 rows) waiting for its last rows, and
-  // those rows are exempt from eviction -- half the slab stays free for the rows being encoded, so
-  // every round serves every miss and every query in flight advances by a hop per round.  (2^20
-  // rows: 4096 queries; a smaller cache works through the batch a few queries at a time.)
-  // (A slab with a row for every node never evicts: no limit.)
-  // (a hop parked in the heap-exact kernel may hold a whole adjacency row of any length)
-  const uint64_t hop_rows = 2 * std::max<uint64_t>(128, tl ? 128 : idx->max_degree);
-  const uint32_t max_active = idx->slab_rows < idx->nvec
-                                  ? (uint32_t)std::max<uint64_t>(1, idx->slab_rows / hop_rows) : (uint32_t)nq;
-  uint32_t active = (uint32_t)std::min<uint64_t>(nq, max_active);
-  uint32_t next_fresh = active;  // queries [next_fresh, nq) have not been started
-  uint32_t nxl = 0;              // queries this round hands straight to the heap-exact kernel
-  bool listed = active < nq;
-  if (!resumable) {
-    active = 0;  // an ordinary launch over all queries every round (round fields stay 0)
-    listed = false;
-  } else if (exact_only) {  // no traversal kernel in front: the round's queries are the heap-exact kernel's queue
-    for (uint32_t i = 0; i < active; ++i) ws.h_xlist[i] = i;
-    nxl = active;
-    active = 0;
-    listed = true;
-  } else if (listed) {
-    for (uint32_t i = 0; i < active; ++i) ws.h_qlist[i] = i;
-    hipLaunchKernelGGL(copy_u32_kernel, dim3(16), dim3(256), 0, st, ws.h_qlist, ws.qlist, (uint64_t)active);
-  }
-  struct RoundReset {  // no slot of the heap-exact kernel's pool stays with a query of this call whatever happens below
-    const isl_index* idx;
-    hipStream_t st;
-    ~RoundReset() {
-      if (idx->pool.slots && idx->pool.locks) {
-        (void)hipMemsetAsync(idx->pool.locks, 0, (size_t)idx->pool.slots * 4, st);
-        (void)hipStreamSynchronize(st);
-      }
-    }
-  } reset{idx, st};
-  uint32_t* h_taken = ws.h_head + 15;  // (word 15 of the pinned ticket mirror is otherwise unused)
-  // encoder batches in whole waves of GEMM tiles (assign_slots_kernel; ISL_RECOMPUTE_QUANTUM=0: every miss at once)
-  uint32_t enc_quantum = 0, enc_chunk = 0;
-  isl::encoder_batch_quantum(idx->enc, idx->tok_L, &enc_quantum, &enc_chunk);
-  if (const char* qe = getenv("ISL_RECOMPUTE_QUANTUM")) enc_quantum = (uint32_t)std::max(0, atoi(qe));  // (read per call: A/B in one process)
-  // Every query in flight advances by at least one hop per round, and a query makes at most a few
-  // times ef hops with new rows: the cap scales with the number of groups the batch is worked
-  // through in, so a 256-row cache (one query at a time) is not cut short and a bug still ends.
-  const uint64_t max_rounds = 64 + ((nq + max_active - 1) / max_active) * ((uint64_t)64 * cg0.ef + 4096);
-  uint32_t stalled = 0;
-  // Two-level search: a parked query also names the nodes it expects to promote next (tl_prefetch of them), which
-  // are encoded in the same round -- fewer, fuller rounds.  Only with a slab that has room to spare (the names are
-  // guesses: under a small cache they would push out rows that hops are waiting for).  ISL_TL_PREFETCH=n overrides
-  // (0 = off; read per call).
-  uint32_t prefetch = (tl && idx->slab_rows >= (uint64_t)1024 * std::max<uint32_t>(1u, max_active)) ? kTlPrefetchDefault : 0u;
-  if (const char* pe = getenv("ISL_TL_PREFETCH")) prefetch = tl ? (uint32_t)std::min(8, std::max(0, atoi(pe))) : 0u;
-  std::vector<uint32_t> again;  // two-level search: queries to start over with a larger queue window
+  double ms_total = 0.0;
   for (;;) {
-    plan.active = active;
-    plan.exact = nxl;
-    plan.exact_parks = x_park;
-    plan.listed = listed;
-    plan.prefetch = prefetch;
-    idx->round_no += 1;
     ISL_TRY(search_enqueue(idx, ws, c, plan));
     plan.tables_built = tl;
-    uint32_t misses = 0;
-    ISL_TRY(search_finish(idx, ws, &misses, nullptr, resumable));
-    const uint32_t guesses = prefetch ? std::min<uint32_t>(ws.h_head[14], (uint32_t)ws.pref_cap) : 0u;
-    kernel_ms += ws.stats.kernel_ms;
-    rounds += 1;
-    if (resumable) {  // next round: the queries that are waiting for rows, topped up with fresh ones
-      uint32_t na = 0;
-      nxl = 0;
-      // queries parked in the heap-exact kernel go straight back to its queue (in front: they hold slots);
-      // the others that wait for rows go through the traversal kernel again -- or, when there is none in
-      // front (ef > 512, long rows), to that queue as well
-      for (uint64_t i = 0; i < next_fresh; ++i)
-        if (ws.h_status[i] == QS_BLOCKED_X) ws.h_xlist[nxl++] = (uint32_t)i;
-      for (uint64_t i = 0; i < next_fresh; ++i)
-        if (ws.h_status[i] == QS_BLOCKED) {
-          if (exact_only) ws.h_xlist[nxl++] = (uint32_t)i;
-          else ws.h_qlist[na++] = (uint32_t)i;
-        }
-      while (na + nxl < max_active && !again.empty()) { ws.h_qlist[na++] = again.back(); again.pop_back(); }
-      while (na + nxl < max_active && next_fresh < nq) {
-        if (exact_only) ws.h_xlist[nxl++] = next_fresh++;
-        else ws.h_qlist[na++] = next_fresh++;
-      }
-      if (!na && tl) {
-        // every query has run to its end; those whose queue window was too small start over -- alone,
-        // nothing is parked now -- with a window four times the size (and a state block to match)
-        uint32_t nshort = 0;
-        ISL_TRY(tl_collect_short(ws, nq, &nshort));
-        if (nshort && plan.window_scale < 64) {
-          plan.window_scale *= 4;
-          const TwoLevelCall tl1{c.ratio, plan.window_scale};
-          CallGeometry cg1;
-          ISL_TRY(call_geometry(idx, c.d, c.k, c.ef, &tl1, cg1));
-          ISL_TRY(ws.qstate.reserve(std::max<uint64_t>(nq, 1) * cg1.state_words, &ws.alloc_events));
-          again.assign(ws.h_qlist.get(), ws.h_qlist + nshort);
-          while (na < max_active && !again.empty()) { ws.h_qlist[na++] = again.back(); again.pop_back(); }
-        }
-      }
-      active = na;
-      listed = true;
-      if (!active && !nxl) {  // now the statuses are final
-        ISL_TRY(search_statuses(ws, nq, nullptr));
-        break;
-      }
-      if (na) hipLaunchKernelGGL(copy_u32_kernel, dim3(16), dim3(256), 0, st, ws.h_qlist, ws.qlist, (uint64_t)na);
-    } else if (!misses) {
-      break;
-    }
-    if (rounds > max_rounds)
-      return isl::fail(ISL_ERR_SEARCH, "Search error: %llu recompute rounds without completing the batch (row cache "
-                       "%llu rows, %u queries in flight at a time)", (unsigned long long)rounds,
-                       (unsigned long long)idx->slab_rows, max_active);
-    if (!misses) continue;  // only fresh queries to start
-    if (misses > ws.miss_cap) misses = (uint32_t)ws.miss_cap;
-    ISL_HIP(hipMemsetAsync(ws.uniq_count, 0, 4, st));
-    hipLaunchKernelGGL(dedupe_misses_kernel, dim3((misses + 255) / 256), dim3(256), 0, st, ws.miss, misses,
-                       idx->d_slot_of, ws.uniq, ws.uniq_count);
-    // the guesses go behind the misses in the unique list: what a full slab or the quantum leaves out is theirs first
-    if (guesses)
-      hipLaunchKernelGGL(dedupe_misses_kernel, dim3((guesses + 255) / 256), dim3(256), 0, st, ws.miss + ws.miss_cap, guesses,
-                         idx->d_slot_of, ws.uniq, ws.uniq_count);
-    // slots for the new rows (clock hand over the slab; rows asked for in this round stay)
-    hipLaunchKernelGGL(assign_slots_kernel, dim3(1), dim3(64), 0, st, ws.uniq, ws.uniq_count, idx->round_no,
-                       (uint32_t)idx->slab_rows, idx->d_slab_head, idx->d_slot_of, idx->d_owner, idx->d_stamp,
-                       ws.uslots, ws.ticket + 15, enc_quantum, enc_chunk);
+    ISL_TRY(search_finish(idx, ws, nullptr, tl));
+    if (!tl) return ISL_OK;  // (statuses evaluated by search_finish)
+    ms_total += ws.stats.kernel_ms;
+    uint32_t nshort = 0;
+    ISL_TRY(tl_retry_short(ws, c.nq, plan.window_scale, &nshort));
+    if (!nshort) break;
+    plan.retry = nshort;
+    copy_words(ws.h_qlist, ws.qlist, nshort, 16, 256, call_stream(ws, c));
     ISL_HIP(hipGetLastError());
-    hipLaunchKernelGGL(copy_u32_kernel, dim3(1), dim3(64), 0, st, ws.ticket + 15, h_taken, (uint64_t)1);
-    ISL_HIP(hipStreamSynchronize(st));
-    const uint32_t take = *h_taken;
-    // no row could be placed although rows are missing: every slot is held by a hop of this round.  A
-    // resumable batch cannot get here (half the slab stays free by construction); a batch that re-runs
-    // its blocked queries from their start needs their whole traversal resident and never will be.
-    if (take == 0 && ++stalled >= (resumable ? 3u : 1u))
-      return isl::fail(ISL_ERR_SEARCH, "Search error: the recompute provider's row cache (%llu rows) is too small "
-                       "for this batch (no missing row could be placed)", (unsigned long long)idx->slab_rows);
-    if (take) stalled = 0;
-    ISL_TRY(isl::encoder_embed_nodes(idx->enc, idx->d_tokens, idx->d_lens, idx->tok_L, ws.uniq, take,
-                                     idx->enc_normalize, idx->d_emb, idx->emb_stride, st, ws.uslots));
-    const size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
-    if (take)
-      hipLaunchKernelGGL(row_norm2_list_kernel, dim3(std::min<uint32_t>((take + 63) / 64, 4096)), dim3(64), lds, st,
-                         idx->d_emb, idx->emb_stride, (uint32_t)idx->emb_d, ws.uslots, take, idx->d_norm2);
-    ISL_HIP(hipGetLastError());
-    encoded += take;
   }
-  ws.stats.encoded_nodes = encoded;
-  ws.stats.recompute_rounds = rounds;
-  ws.stats.kernel_ms = kernel_ms;
-  ws.stats.allocations = ws.alloc_events - ws.alloc_mark;
-  return ISL_OK;
+  ws.stats.kernel_ms = ms_total;
+  return search_statuses(ws, c.nq);
 }
 
-// ---- concurrent asynchronous calls over the recompute provider, answered together ----
-// Calls over the recompute provider run one at a time per index (the rounds rewrite the provider's row cache).
-// A caller that keeps several batches in flight therefore used to get them answered one after the other, each
-// with its own small encoder passes -- where ONE call over all their queries encodes a node once for all of
-// them and hands the encoder fuller passes (8 x 1024 queries at 10M nodes: 89.0 against 74.9 queries/s,
-// DESIGN.md section 3.4).  So the asynchronous device-buffer calls queue here: the call whose turn it is takes
-// every compatible call (same d, k, ef, search kind, re-rank ratio) that is waiting at that moment, runs the
-// rounds ONCE over the union of their queries on its own lane, and scatters the answers; the others wake up
-// answered.  Every query's answer is what its own call would have computed (a query's traversal does not
-// depend on what else is in the batch).  If the union fails -- one query's NodeNotFound fails the call it
-// belongs to, not its neighbours' -- every member is run by itself and gets its own status.
-struct RecCall {
-  SearchCall call;  // (on the member's own lane's stream: StreamMode::OWN)
-  isl::SearchWorkspace* ws;
-  bool done = false;
-  isl_status status = ISL_OK;
-  isl::ErrorRecord err;
-};
+}  // namespace
 
-isl_status recompute_coalesced(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c) {
-  static const bool off = getenv("ISL_NO_RECOMPUTE_COALESCE") != nullptr;  // A/B switch for measurements
-  if (off) return search_sync(idx, ws, c);
-  const uint64_t d = c.d, k = c.k;
-  RecCall me{c, &ws};
-  auto& J = idx->rec_join;
-  {
-    std::lock_guard<std::mutex> l(J.mu);
-    J.waiting.push_back(&me);
-  }
-  std::unique_lock<std::mutex> lead(J.leader);
-  if (me.done) {  // answered by the call that had the turn before
-    if (me.status != ISL_OK) isl::last_error() = me.err;
-    return me.status;
-  }
-  constexpr uint64_t kMaxUnion = 1u << 17;  // queries one set of rounds works through
-  std::vector<RecCall*> group{&me};
-  uint64_t total = c.nq;
-  {
-    std::lock_guard<std::mutex> l(J.mu);
-    std::vector<void*> rest;
-    for (void* v : J.waiting) {
-      RecCall* m = static_cast<RecCall*>(v);
-      if (m == &me) continue;
-      const SearchCall& o = m->call;
-      const bool same = o.d == d && o.k == k && o.ef == c.ef && o.two_level == c.two_level && (!c.two_level || o.ratio == c.ratio);
-      if (same && total + o.nq <= kMaxUnion) { group.push_back(m); total += o.nq; }
-      else rest.push_back(v);
-    }
-    J.waiting.swap(rest);
-  }
-  if (group.size() == 1) return search_sync(idx, ws, c);
-
-  auto alone = [&](RecCall* m) {  // the member's own call, on the member's own lane
-    m->status = search_sync(idx, *m->ws, m->call);
-    if (m->status != ISL_OK) m->err = isl::last_error();
-  };
-  auto fall_back = [&]() -> isl_status {  // every member by itself: its own answers, its own error
-    for (RecCall* m : group)
-      if (m != &me) { alone(m); m->done = true; }
-    return search_sync(idx, ws, c);
-  };
-  uint64_t* const ev = &ws.alloc_events;
-  if (ws.co_q.reserve(total * d, ev) != ISL_OK || ws.co_ids.reserve(total * std::max<uint64_t>(k, 1), ev) != ISL_OK ||
-      ws.co_dist.reserve(total * std::max<uint64_t>(k, 1), ev) != ISL_OK || ws.co_cnt.reserve(total, ev) != ISL_OK ||
-      ensure_lane_stream(idx, ws) != ISL_OK)
-    return fall_back();
-  hipStream_t st = ws.stream;
-  uint64_t o = 0;
-  bool copied = true;
-  for (RecCall* m : group) {  // a member's queries are there once its caller's stream has reached the call (ev_in)
-    if (m != &me) copied = copied && hipStreamWaitEvent(st, m->ws->ev_in, 0) == hipSuccess;
-    copied = copied && hipMemcpyAsync(ws.co_q + o * d, m->call.queries, m->call.nq * d * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
-    o += m->call.nq;
-  }
-  if (!copied) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); return fall_back(); }
-  // (a host-buffer call's lane publishes its answers into pinned mirrors sized for THAT call: not for the union)
-  const bool publishes = ws.publish_results;
-  ws.publish_results = false;
-  SearchCall all_calls = c;  // the union: every member's queries, answered into the lane's own buffers
-  all_calls.queries = ws.co_q;
-  all_calls.nq = total;
-  all_calls.ids = ws.co_ids;
-  all_calls.dist = ws.co_dist;
-  all_calls.count = ws.co_cnt;
-  const isl_status rc = search_sync(idx, ws, all_calls);
-  ws.publish_results = publishes;
-  if (rc != ISL_OK) return fall_back();
-  const isl_search_stats all = ws.stats;
-  o = 0;
-  bool scattered = true;
-  for (RecCall* m : group) {
-    const uint64_t mq = m->call.nq;
-    if (k) {
-      scattered = scattered && hipMemcpyAsync(m->call.ids, ws.co_ids + o * k, mq * k * 8, hipMemcpyDeviceToDevice, st) == hipSuccess;
-      scattered = scattered && hipMemcpyAsync(m->call.dist, ws.co_dist + o * k, mq * k * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
-    }
-    scattered = scattered && hipMemcpyAsync(m->call.count, ws.co_cnt + o, mq * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
-    if (m->ws->publish_results) {  // a host-buffer call (isl_search_batch_async): its wait copies out of the lane's pinned mirrors
-      if (k) {
-        scattered = scattered && hipMemcpyAsync(m->ws->h_ids, ws.co_ids + o * k, mq * k * 8, hipMemcpyDeviceToHost, st) == hipSuccess;
-        scattered = scattered && hipMemcpyAsync(m->ws->h_dist, ws.co_dist + o * k, mq * k * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-      }
-      scattered = scattered && hipMemcpyAsync(m->ws->h_count, ws.co_cnt + o, mq * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
-      m->ws->nq_inflight = mq;
-      m->ws->k_inflight = k;
-    }
-    o += mq;
-  }
-  scattered = scattered && hipStreamSynchronize(st) == hipSuccess;
-  if (!scattered) { (void)hipGetLastError(); return fall_back(); }
-  // each member's counters are its own queries' (the lane's pinned mirror holds the union's, query by query);
-  // rounds, encoded nodes and kernel time are the union's
-  o = 0;
-  for (RecCall* m : group) {
-    isl_search_stats ms = all;
-    ms.queries = m->call.nq;
-    ms.expansions = ms.edges = ms.evals = ms.pushes = 0;
-    for (uint64_t i = o; i < o + m->call.nq; ++i) {
-      ms.expansions += ws.h_ctr[i * 4 + 0];
-      ms.edges += ws.h_ctr[i * 4 + 1];
-      ms.evals += ws.h_ctr[i * 4 + 2];
-      ms.pushes += ws.h_ctr[i * 4 + 3];
-    }
-    m->ws->stats = ms;
-    o += m->call.nq;
-    if (m != &me) { m->status = ISL_OK; m->done = true; }
-  }
-  return ISL_OK;
+// One synchronous search on a claimed lane: by the index's provider.
+isl_status isl_lane::search_sync(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c) {
+  return idx->recompute ? recompute_rounds(idx, ws, c) : search_resident(idx, ws, c);
 }
+
+namespace {
 
 // Checks shared by the entry points; *done = 1 when the call is already answered.
 isl_status precheck(const isl_index* idx, uint64_t nq, uint64_t d, uint64_t k, uint32_t* out_count,

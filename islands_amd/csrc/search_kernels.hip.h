@@ -1,11 +1,12 @@
 // The search kernels of libislands_amd.so (one 64-lane wavefront per query) -- included by the
 // translation units that instantiate them: search_fast{1,2,4,8}.hip (the fast kernel per result-set
-// size), search_aux.hip (heap-exact kernel, two-level search, HnswGraph descent) and search.hip
-// (host side).  Everything lives in an anonymous namespace: each unit emits the instantiations
+// size), search_aux.hip (heap-exact kernel, two-level search, HnswGraph descent), search.hip and
+// search_recompute.hip (host side).  Everything lives in an anonymous namespace: each unit emits the instantiations
 // it launches and nothing else.
 #pragma once
 #include "device_common.hip.h"
 #include "encoder.hpp"
+#include "query_status.hpp"
 
 #include <algorithm>
 #include <type_traits>
@@ -18,16 +19,7 @@ constexpr uint32_t EMPTY = 0xFFFFFFFFu;
 constexpr uint32_t FLAG_EXP = 0x80000000u;
 constexpr uint32_t ID_MASK = 0x7FFFFFFFu;
 
-// per-query status words written by the kernels
-enum : uint32_t {
-  QS_OK = 0,
-  QS_NODE_NOT_FOUND = 5,
-  QS_REDO = 0x100,     // fast kernel gave up -> exact kernel
-  QS_SCRATCH = 0x101,  // exact kernel ran out of candidate scratch
-  QS_REPLAY = 0x102,   // result-heap order needed: replay kernel re-orders from the push log
-  QS_BLOCKED = 0x103,  // recompute provider: a needed row is not materialised yet (ids reported)
-  QS_BLOCKED_X = 0x104 // ... and the query is parked in the heap-exact kernel (it keeps its pool slot)
-};
+// (the per-query status words QS_* the kernels write: query_status.hpp)
 
 struct SearchParams {
   const uint64_t* off;

@@ -17,15 +17,21 @@ LLVM = "/opt/rocm/lib/llvm/bin/"
 
 def code_hashes(code_object):
     """symbol -> sha256 of its instructions (`llvm-objdump -d --no-show-raw-insn`, split at the
-    `<symbol>:` lines, the trailing `// address` comments stripped)"""
+    `<symbol>:` lines, the trailing `// address` comments stripped; a `...` of zeros that ends a symbol is left
+    out: it is the alignment padding up to the next symbol and depends on what follows the kernel in the object)"""
     dis = subprocess.run([LLVM + "llvm-objdump", "-d", "--no-show-raw-insn", code_object], capture_output=True,
                          text=True, check=True).stdout
-    out, cur = {}, None
+    out, cur, pad = {}, None, False
     for line in dis.splitlines():
         m = re.match(r"^[0-9a-f]+ <(\S+)>:", line)
         if m:
-            cur = out.setdefault(m.group(1), hashlib.sha256())
+            cur, pad = out.setdefault(m.group(1), hashlib.sha256()), False  # (a `...` held back was padding)
+        elif cur is not None and line.strip() == "...":
+            pad = True
         elif cur is not None and line.strip():
+            if pad:  # zeros inside the symbol's body are code like any other
+                cur.update(b"...\n")
+                pad = False
             cur.update(re.sub(r"\s*//.*$", "", line).strip().encode() + b"\n")
     return {k: v.hexdigest()[:16] for k, v in out.items()}
 
