@@ -157,6 +157,17 @@ void isl_build_options_default(isl_build_options* o); /* REFERENCE, 1.0, 1, batc
 isl_status isl_index_build_ex(const isl_leann_config* cfg, const isl_build_options* opts,
                               const float* vectors, uint64_t n, uint64_t d, const uint64_t* levels,
                               int32_t mem, int32_t device, isl_index** out);
+/* isl_index_build_ex over rows of either stored type.  dtype ISL_DTYPE_F32: rows = n x d float, the call IS
+ * isl_index_build_ex.  dtype ISL_DTYPE_BF16: rows = n x d bf16 bit patterns (u16); the provider's vectors are
+ * their exact f32 images, the construction is LeannIndex::build over those images (either selection rule,
+ * any batch), and the finished index keeps the rows as bf16 -- as if isl_set_embeddings(..., ISL_DTYPE_BF16)
+ * had been called on it.  Host or device rows (mem).  Checked in this order before any device call: NULL
+ * out, or NULL rows with n > 0 -> ISL_ERR_INVALID_ARGUMENT; opts as in isl_index_build_ex; an unknown dtype ->
+ * ISL_ERR_INVALID_ARGUMENT; isl_leann_config_validate; n == 0 -> an empty index; d == 0 ->
+ * ISL_ERR_EMPTY_COLLECTION; m0 > 128, ef_construction > 512 or too many nodes -> ISL_ERR_UNSUPPORTED. */
+isl_status isl_index_build_rows(const isl_leann_config* cfg, const isl_build_options* opts, const void* rows,
+                                int32_t dtype, uint64_t n, uint64_t d, const uint64_t* levels, int32_t mem,
+                                int32_t device, isl_index** out);
 /* select() of ISL_SELECT_DIVERSE for nb base nodes of an index whose f32 rows are on the device
  * (bf16 rows or a recompute provider -> ISL_ERR_UNSUPPORTED): cand_ids is [nb][pitch] in any order
  * (the call computes d(base, c) and stable-sorts), cand_cnt[i] <= min(pitch, 512), cap <= 128;
@@ -223,7 +234,8 @@ isl_status isl_index_upload(isl_index* idx, int32_t device);
  * dtype ISL_DTYPE_BF16: `rows` holds bf16 bit patterns (u16) and is stored as such -- half the
  * HBM bytes per visited node; the provider's vectors are their exact f32 images and the
  * arithmetic stays the reference's f32 chain, so results equal the reference's on those f32
- * rows.  (The HnswGraph facade, the builder and the distance / PQ entry points take f32.) */
+ * rows.  (The LeannIndex builder takes either type through isl_index_build_rows; the HnswGraph facade and its
+ * builder, isl_select_neighbors and the distance / PQ entry points take f32.) */
 isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
                               int32_t dtype, int32_t mem);
 

@@ -147,6 +147,16 @@ class LeannIndex {
     check(isl_index_build_ex(&cfg, &opts, vectors.data(), n, d, levels, ISL_MEM_HOST, device, &idx.h_));
     return idx;
   }
+  // The same from bf16 rows (isl_index_build_rows): `rows_bits` is n rows of d bf16 bit patterns; the graph is
+  // the one build() makes from their exact f32 images, and the index keeps the rows as bf16.
+  static LeannIndex build_bf16(const std::vector<uint16_t>& rows_bits, uint64_t n, uint64_t d, const LeannConfig& cfg,
+                               const isl_build_options& opts = build_options(), const uint64_t* levels = nullptr,
+                               int32_t device = 0) {
+    LeannIndex idx(nullptr);
+    check(isl_index_build_rows(&cfg, &opts, rows_bits.data(), ISL_DTYPE_BF16, n, d, levels, ISL_MEM_HOST, device,
+                               &idx.h_));
+    return idx;
+  }
   // select() of the diverse rule for one base node over candidates in any order (isl_select_neighbors)
   std::vector<uint64_t> select_neighbors(uint64_t base, const std::vector<uint64_t>& candidates, uint64_t cap,
                                          const isl_build_options& opts = build_options()) const {

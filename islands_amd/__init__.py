@@ -372,6 +372,27 @@ class LeannIndex:
                                              C.byref(h)))
         return cls(_handle=h)
 
+    @classmethod
+    def build_bf16(cls, rows_bits=None, config: LeannConfig | None = None, levels=None, batch: int = 1,
+                   device: int = 0, select=None, alpha: float = 1.0, keep_pruned: bool = True,
+                   device_ptr: int | None = None, n: int | None = None, d: int | None = None) -> "LeannIndex":
+        """build() from bf16 rows (isl_index_build_rows): `rows_bits` is [n, d] uint16 bit patterns, or
+        (device_ptr, n, d) names rows resident on `device`.  The graph is the one build() makes from their
+        exact f32 images; the index keeps the rows as bf16, as after set_embeddings_bf16."""
+        c = (config or LeannConfig())._to_c()
+        lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint64)
+        o = cls._build_options(select, alpha, keep_pruned, batch)
+        h = C.c_void_p()
+        if device_ptr is not None:
+            rows, mem = C.c_void_p(device_ptr), MEM_DEVICE
+        else:
+            r = np.ascontiguousarray(rows_bits, dtype=np.uint16)
+            n, d = r.shape if r.ndim == 2 else (0, 0)
+            rows, mem = (_ptr(r) if n else None), MEM_HOST
+        _check(_ffi.lib().isl_index_build_rows(C.byref(c), C.byref(o), rows, 1, n, d,
+                                               None if lv is None else _ptr(lv), mem, device, C.byref(h)))
+        return cls(_handle=h)
+
     def select_neighbors(self, base_ids, candidates, cap: int, alpha: float = 1.0,
                          keep_pruned: bool = True, counts=None):
         """isl_select_neighbors: the diverse rule's select() for every base node over its row of

@@ -167,6 +167,8 @@ SIGNATURES = {
     "isl_build_options_default": (None, [P(BuildOptionsC)]),
     "isl_index_build_ex": (i32, [P(LeannConfigC), P(BuildOptionsC), C.c_void_p, u64, u64, C.c_void_p, i32, i32,
                                  P(C.c_void_p)]),
+    "isl_index_build_rows": (i32, [P(LeannConfigC), P(BuildOptionsC), C.c_void_p, i32, u64, u64, C.c_void_p, i32, i32,
+                                   P(C.c_void_p)]),
     "isl_select_neighbors": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, C.c_void_p, u64, C.c_void_p,
                                    u64, C.c_void_p, C.c_void_p]),
     "isl_index_metadata_new": (None, [u64, u64, C.c_int64, P(IndexMetadataC)]),

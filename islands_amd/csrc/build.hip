@@ -14,6 +14,11 @@
 // row and the re-selection of a row that outgrew m0 -- for the occlusion rule defined in
 // include/islands_amd.h; everything else (order, construction search, locks, step ramp) is shared.
 //
+// isl_index_build_rows is the same construction over rows of either stored type.  bf16 rows (ISL_DTYPE_BF16)
+// stay bf16 in the construction graph and in the finished index; the selection and link kernels take the row
+// type as a template parameter and measure bf16 rows with the tile-free routine of device_common.hip.h over
+// the exact f32 images, so the graph is the one built from the widened rows.
+//
 // The HnswGraph builder (hnsw_build.hip) runs the same selection kernels and link_kernel's HNSW mode
 // over one fixed-width table per layer.  Both go through one host path, isl_build::Scaffold
 // (build_internal.hpp, defined below the kernels): the construction graph and everything allocated for
@@ -34,14 +39,19 @@ using isl_build::BuildParams;
 
 // ---------------------------------------------------------------- ISL_SELECT_DIVERSE
 // What a selection reads besides its lists: the rows and the rule's two parameters.
-struct SelCtx {
-  const float* emb;
+// ROWT = float, or uint16_t for bf16 bit patterns (stride in elements of it; norm2 is of the widened values).
+template <typename ROWT>
+struct SelCtxT {
+  const ROWT* emb;
   const float* norm2;
   uint64_t stride;
   uint32_t d;
   float alpha;
   uint32_t keep_pruned;
 };
+using SelCtx = SelCtxT<float>;
+template <typename ROWT>
+constexpr bool kBf16 = sizeof(ROWT) == 2;
 
 // LDS lists of one selection over up to `nmax` candidates, laid out behind the query.
 struct SelState {
@@ -52,8 +62,10 @@ struct SelState {
   uint32_t* out;   // [M] the row: kept, then the fillers
 };
 using isl_plan::query_floats;  // (constexpr: the figure the host reserves is the one the kernels lay out by)
+using isl_plan::query_floats_bf16;
+template <typename ROWT = float>
 __device__ __forceinline__ SelState sel_state(float* qs, uint32_t d, uint32_t nmax) {
-  uint32_t* w = reinterpret_cast<uint32_t*>(qs + query_floats(d));
+  uint32_t* w = reinterpret_cast<uint32_t*>(qs + (kBf16<ROWT> ? query_floats_bf16(d) : query_floats(d)));
   SelState s;
   s.cid = w;
   s.cd = reinterpret_cast<float*>(w + nmax);
@@ -73,6 +85,24 @@ __device__ __forceinline__ float load_row_query(const SelCtx& c, uint32_t id, fl
   __syncthreads();
   return (METRIC == ISL_METRIC_COSINE || METRIC == METRIC_COSINE_PRE) ? c.norm2[id] : 0.0f;
 }
+// The same for a bf16 row: widened (exactly) into the f32 query area, 8 elements per lane and turn.  A row
+// starts 16-byte aligned and is padded with zeros to 8 elements; the area holds d rounded up to 32.
+template <int METRIC>
+__device__ __forceinline__ float load_row_query(const SelCtxT<uint16_t>& c, uint32_t id, float* qs) {
+  const uint16_t* q = c.emb + (uint64_t)id * c.stride;
+  const uint32_t d8 = (c.d + 7u) & ~7u;
+  for (uint32_t j = threadIdx.x * 8u; j < d8; j += 512u) {
+    const v4u w = *reinterpret_cast<const v4u*>(q + j);
+    *reinterpret_cast<float4*>(qs + j) =
+        make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
+                    __uint_as_float(w.y & 0xFFFF0000u));
+    *reinterpret_cast<float4*>(qs + j + 4u) =
+        make_float4(__uint_as_float(w.z << 16), __uint_as_float(w.z & 0xFFFF0000u), __uint_as_float(w.w << 16),
+                    __uint_as_float(w.w & 0xFFFF0000u));
+  }
+  __syncthreads();
+  return (METRIC == ISL_METRIC_COSINE || METRIC == METRIC_COSINE_PRE) ? c.norm2[id] : 0.0f;
+}
 
 // select(b, C, M) of include/islands_amd.h for one wave, turned inside out: a candidate is kept
 // iff no EARLIER KEPT one occludes it, so the head of the undecided list is always kept, its row
@@ -81,8 +111,8 @@ __device__ __forceinline__ float load_row_query(const SelCtx& c, uint32_t id, fl
 // over a shrinking list; a round costs what a hop of the search costs per 16 rows.  d(s, c) is
 // calculate(vec[s], vec[c]) through the same chain as every other distance of the library.
 // In: s.cid / s.cd [n] (written by the caller, not yet synchronised).  Out: s.out, count returned.
-template <int METRIC>
-__device__ __forceinline__ uint32_t diverse_select(const SelCtx& c, uint32_t n, uint32_t M,
+template <int METRIC, typename ROWT = float>
+__device__ __forceinline__ uint32_t diverse_select(const SelCtxT<ROWT>& c, uint32_t n, uint32_t M,
                                                    const SelState& s, float* qs, float* tile) {
   const uint32_t lane = threadIdx.x;
   const uint64_t below = (1ull << lane) - 1ull;
@@ -105,7 +135,11 @@ __device__ __forceinline__ uint32_t diverse_select(const SelCtx& c, uint32_t n, 
       const uint32_t pos = valid ? s.lst[base + lane] : 0u;
       const uint32_t rid = valid ? s.cid[pos] : aid;
       const float aux = (METRIC == METRIC_COSINE_PRE && valid) ? c.norm2[rid] : 0.0f;
-      const float ds = wave_distances<METRIC>(c.emb, c.stride, c.d, rid, cnt, qs, tile, q_norm, aux);
+      float ds;
+      // bf16 rows: the tile-free routine (quad-owned rows, 16-byte loads of 8 elements, guarded tail) -- the
+      // same contract, lane j < cnt gets row rid(j), and no tile
+      if constexpr (kBf16<ROWT>) ds = direct_distances<METRIC, uint16_t>(c.emb, c.stride, c.d, rid, cnt, qs, q_norm, aux);
+      else ds = wave_distances<METRIC>(c.emb, c.stride, c.d, rid, cnt, qs, tile, q_norm, aux);
       // occluded: alpha * d(s, c) <= d(b, c), separate roundings; false for a NaN on either side
       const bool stays = valid && !(c.alpha * ds <= s.cd[pos]);
       const uint64_t m = ballot(stays);
@@ -198,19 +232,21 @@ __global__ __launch_bounds__(64) void select_kernel(BuildParams p) {
   if (lane == 0) p.sel_cnt[b] = nsel;
 }
 
-__device__ __forceinline__ SelCtx sel_ctx(const BuildParams& p) {
-  return SelCtx{p.emb, p.norm2, p.stride, p.d, p.alpha, p.keep_pruned};
+template <typename ROWT = float>
+__device__ __forceinline__ SelCtxT<ROWT> sel_ctx(const BuildParams& p) {
+  if constexpr (kBf16<ROWT>) return SelCtxT<ROWT>{p.emb16, p.norm2, p.stride, p.d, p.alpha, p.keep_pruned};
+  else return SelCtxT<ROWT>{p.emb, p.norm2, p.stride, p.d, p.alpha, p.keep_pruned};
 }
 
 // ISL_SELECT_DIVERSE for one new node per wave: select(node, search result, m0), with the search's
-// distances as d(node, c).
-template <int METRIC_API>
+// distances as d(node, c).  Over bf16 rows (ROWT = uint16_t) there is no tile: the query leads the LDS.
+template <int METRIC_API, typename ROWT = float>
 __global__ __launch_bounds__(64) void select_diverse_kernel(BuildParams p) {
   constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
   extern __shared__ __align__(16) unsigned char smem[];
   float* tile = reinterpret_cast<float*>(smem);
-  float* qs = tile + TILE_ROWS * TILE_LD;
-  const SelState s = sel_state(qs, p.d, p.ef);
+  float* qs = tile + (kBf16<ROWT> ? 0 : TILE_ROWS * TILE_LD);
+  const SelState s = sel_state<ROWT>(qs, p.d, p.ef);
   const uint32_t lane = threadIdx.x, b = blockIdx.x;
   const uint32_t n = p.cand_cnt[b] < p.ef ? p.cand_cnt[b] : p.ef;
   const uint64_t* cid = p.cand_ids + (uint64_t)b * p.ef;
@@ -219,7 +255,7 @@ __global__ __launch_bounds__(64) void select_diverse_kernel(BuildParams p) {
     s.cid[i] = (uint32_t)cid[i];
     s.cd[i] = cdist[i];
   }
-  const uint32_t nsel = diverse_select<METRIC>(sel_ctx(p), n, p.m0, s, qs, tile);
+  const uint32_t nsel = diverse_select<METRIC>(sel_ctx<ROWT>(p), n, p.m0, s, qs, tile);
   uint32_t* out = p.sel + (uint64_t)b * p.m0;
   for (uint32_t i = lane; i < nsel; i += 64) out[i] = s.out[i];
   if (lane == 0) p.sel_cnt[b] = nsel;
@@ -282,12 +318,14 @@ __global__ __launch_bounds__(64) void select_neighbors_kernel(SelectNeighborsPar
 // selected neighbour takes the back link only if it has the layer, the new id is appended without a
 // `contains` test, and the reference rule's re-sort (prune_connections, :405-446) leaves the new id out --
 // it looks every id up in the node map, which the node being inserted has not entered yet.
-template <int METRIC_API, bool DIVERSE = false, bool HNSW = false>
+// ROWT = uint16_t: LeannIndex::build over bf16 rows (no tile; norm_a of a row is its norm2, the bits the
+// d-step sum over the widened values gives).
+template <int METRIC_API, bool DIVERSE = false, bool HNSW = false, typename ROWT = float>
 __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
   constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
   extern __shared__ __align__(16) unsigned char smem[];
   float* tile = reinterpret_cast<float*>(smem);
-  float* qs = tile + TILE_ROWS * TILE_LD;
+  float* qs = tile + (kBf16<ROWT> ? 0 : TILE_ROWS * TILE_LD);
   const uint32_t lane = threadIdx.x, b = blockIdx.x;
   const uint32_t node = HNSW ? p.node_ids[b] : (uint32_t)(p.id0 + b);
   const uint32_t nsel = p.sel_cnt[b];
@@ -317,7 +355,9 @@ __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
         // prune_neighbors_temp: distances from nid to every neighbour, stable sort, keep m0
         __threadfence_block();
         __syncthreads();
-        const float q_norm = load_query<METRIC>(p.emb + (uint64_t)nid * p.stride, p.d, qs);
+        float q_norm;
+        if constexpr (kBf16<ROWT>) q_norm = load_row_query<METRIC>(sel_ctx<ROWT>(p), nid, qs);
+        else q_norm = load_query<METRIC>(p.emb + (uint64_t)nid * p.stride, p.d, qs);
         // the row holds dg = m0 + 1 <= 129 ids: up to three slices of 64, one id per lane each
         constexpr int CH = 3;
         uint32_t rid[CH];
@@ -330,7 +370,10 @@ __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
           dist[c] = 0.0f;
           if (cnt) {
             const float aux = (METRIC == METRIC_COSINE_PRE && lane < cnt) ? p.norm2[rid[c]] : 0.0f;
-            dist[c] = wave_distances<METRIC>(p.emb, p.stride, p.d, rid[c], cnt, qs, tile, q_norm, aux);
+            if constexpr (kBf16<ROWT>)
+              dist[c] = direct_distances<METRIC, uint16_t>(p.emb16, p.stride, p.d, rid[c], cnt, qs, q_norm, aux);
+            else
+              dist[c] = wave_distances<METRIC>(p.emb, p.stride, p.d, rid[c], cnt, qs, tile, q_norm, aux);
           }
         }
         // stable sort by distance (`<` only, leann.rs:650): rank of every entry among all dg.
@@ -357,11 +400,11 @@ __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
         }
         __syncthreads();
         if constexpr (DIVERSE) {
-          const SelState s = sel_state(qs, p.d, p.W);
+          const SelState s = sel_state<ROWT>(qs, p.d, p.W);
 #pragma unroll
           for (int c = 0; c < CH; ++c)
             if (64u * c + lane < dg) { s.cid[rank[c]] = rid[c]; s.cd[rank[c]] = dist[c]; }
-          const uint32_t nk = diverse_select<METRIC>(sel_ctx(p), dg, p.m0, s, qs, tile);
+          const uint32_t nk = diverse_select<METRIC>(sel_ctx<ROWT>(p), dg, p.m0, s, qs, tile);
           for (uint32_t i = lane; i < nk; i += 64) row[i] = s.out[i];
           dg = nk;
         } else {
@@ -420,26 +463,43 @@ __global__ void gather_rows_kernel(const float* __restrict__ emb, uint64_t strid
   if (i >= (uint64_t)B * d) return;
   out[i] = emb[(id0 + i / d) * stride + i % d];
 }
+// ... from bf16 rows: the queries of a step are the widened rows
+__global__ void gather_rows_bf16_kernel(const uint16_t* __restrict__ emb, uint64_t stride, uint32_t d,
+                                        uint64_t id0, uint32_t B, float* __restrict__ out) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint64_t)B * d) return;
+  out[i] = __uint_as_float((uint32_t)emb[(id0 + i / d) * stride + i % d] << 16);
+}
 
 constexpr size_t kTileBytes = (size_t)TILE_ROWS * TILE_LD * 4;
-size_t sel_lds(uint64_t d, uint32_t nmax, uint32_t M) { return isl_plan::select_lds(kTileBytes, (uint32_t)d, nmax, M); }
+// (bf16 rows: no tile)
+size_t sel_lds(bool bf16, uint64_t d, uint32_t nmax, uint32_t M) {
+  return bf16 ? isl_plan::select_lds_bf16((uint32_t)d, nmax, M) : isl_plan::select_lds(kTileBytes, (uint32_t)d, nmax, M);
+}
 
-// one wave per node of the step, the kernel instantiated for the index's metric
-template <bool DIVERSE, bool HNSW>
+// one wave per node of the step, the kernel instantiated for the index's metric and row type
+template <bool DIVERSE, bool HNSW, typename ROWT = float>
 void launch_link_as(uint32_t metric, uint32_t grid, size_t lds, const BuildParams& p) {
   isl_build::by_metric(metric, [&](auto mc) {
-    hipLaunchKernelGGL((link_kernel<decltype(mc)::value, DIVERSE, HNSW>), dim3(grid), dim3(64), lds, 0, p);
+    hipLaunchKernelGGL((link_kernel<decltype(mc)::value, DIVERSE, HNSW, ROWT>), dim3(grid), dim3(64), lds, 0, p);
   });
 }
 void launch_link(uint32_t metric, bool diverse, bool hnsw, uint32_t grid, size_t lds, const BuildParams& p) {
-  if (!diverse && !hnsw) launch_link_as<false, false>(metric, grid, lds, p);
+  if (p.emb16) {  // LeannIndex::build alone takes bf16 rows (Scaffold::open)
+    if (diverse) launch_link_as<true, false, uint16_t>(metric, grid, lds, p);
+    else launch_link_as<false, false, uint16_t>(metric, grid, lds, p);
+  }
+  else if (!diverse && !hnsw) launch_link_as<false, false>(metric, grid, lds, p);
   else if (!hnsw) launch_link_as<true, false>(metric, grid, lds, p);
   else if (!diverse) launch_link_as<false, true>(metric, grid, lds, p);
   else launch_link_as<true, true>(metric, grid, lds, p);
 }
 void launch_select_diverse(uint32_t metric, uint32_t grid, size_t lds, const BuildParams& p) {
   isl_build::by_metric(metric, [&](auto mc) {
-    hipLaunchKernelGGL(select_diverse_kernel<decltype(mc)::value>, dim3(grid), dim3(64), lds, 0, p);
+    if (p.emb16)
+      hipLaunchKernelGGL((select_diverse_kernel<decltype(mc)::value, uint16_t>), dim3(grid), dim3(64), lds, 0, p);
+    else
+      hipLaunchKernelGGL(select_diverse_kernel<decltype(mc)::value>, dim3(grid), dim3(64), lds, 0, p);
   });
 }
 
@@ -460,6 +520,11 @@ isl_status check_build_options(const isl_build_options* o, bool need_rule) {
 }
 
 size_t link_lds(uint64_t d) { return isl_plan::link_lds(kTileBytes, (uint32_t)d); }
+
+isl_status check_row_dtype(int32_t dtype) {
+  if (dtype != ISL_DTYPE_F32 && dtype != ISL_DTYPE_BF16) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "unknown row dtype");
+  return ISL_OK;
+}
 
 Scaffold::~Scaffold() {
   const isl::ErrorRecord first = isl::last_error();
@@ -485,9 +550,11 @@ isl_status Scaffold::alloc_bytes(void** out, uint64_t bytes, bool zero, bool kep
   return ISL_OK;
 }
 
-isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw_, const float* vectors,
-                          uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef,
-                          const isl_index* old) {
+isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw_, const void* vectors,
+                          int32_t dtype, uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0,
+                          uint32_t ef, const isl_index* old) {
+  if (dtype != ISL_DTYPE_F32 && (hnsw_ || old))
+    return isl::fail(ISL_ERR_UNSUPPORTED, "the HnswGraph builder keeps f32 vectors");
   ISL_TRY(isl_index_new(&cfg, &g));
   g->cfg.prune_ratio = 0.0f;  // construction searches do not prune (leann.rs:692-749)
   g->is_hnsw = hnsw_;         // HnswGraph heap order: distance alone
@@ -497,8 +564,8 @@ isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& 
   g->has_dimension = true;
   g->dimension = d;
   g->max_degree = m0;  // the widest row a construction search can meet: a row is back at <= m0 ids before the next search
-  if (old) ISL_TRY(isl::set_grown_embeddings(g, old, vectors, n - old->nvec, d, mem));
-  else ISL_TRY(isl_set_embeddings(g, vectors, n, d, ISL_DTYPE_F32, mem));
+  if (old) ISL_TRY(isl::set_grown_embeddings(g, old, static_cast<const float*>(vectors), n - old->nvec, d, mem));
+  else ISL_TRY(isl_set_embeddings(g, vectors, n, d, dtype, mem));
   hnsw = hnsw_;
   diverse = opts.select_rule == ISL_SELECT_DIVERSE;
   ISL_TRY(alloc(&p.lock, n, true));
@@ -508,7 +575,7 @@ isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& 
   ISL_TRY(alloc(&cand_cnt, B));
   ISL_TRY(alloc(&p.sel, B * m0));
   ISL_TRY(alloc(&p.sel_cnt, B));
-  p.emb = g->d_emb; p.norm2 = g->d_norm2; p.stride = g->emb_stride; p.d = (uint32_t)d;
+  p.emb = g->d_emb; p.emb16 = g->d_emb16; p.norm2 = g->d_norm2; p.stride = g->emb_stride; p.d = (uint32_t)d;
   p.ef = ef;
   p.cand_ids = cand_ids; p.cand_dist = cand_dist; p.cand_cnt = cand_cnt;
   if (!hnsw) { p.hub_percentile = cfg.hub_percentile; p.high_degree = cfg.high_degree_pruning; }
@@ -528,13 +595,14 @@ isl_status Scaffold::insert(const Table& t, uint32_t cnt, bool locking, uint64_t
   p.B = cnt;
   p.locking = locking;
   const uint32_t metric = g->cfg.metric;
+  const bool bf16 = p.emb16 != nullptr;
   if (diverse) {
-    launch_select_diverse(metric, cnt, sel_lds(d, p.ef, t.M), p);
-    launch_link(metric, true, hnsw, cnt, sel_lds(d, t.M + 1, t.M), p);
+    launch_select_diverse(metric, cnt, sel_lds(bf16, d, p.ef, t.M), p);
+    launch_link(metric, true, hnsw, cnt, sel_lds(bf16, d, t.M + 1, t.M), p);
   } else {
     // the reference rule's selection does not measure: take(M), or the hub rule of LeannIndex::build
     hipLaunchKernelGGL(select_kernel, dim3(cnt), dim3(64), (size_t)p.ef * 12, 0, p);
-    launch_link(metric, false, hnsw, cnt, link_lds(d), p);
+    launch_link(metric, false, hnsw, cnt, bf16 ? isl_plan::link_lds_bf16((uint32_t)d) : link_lds(d), p);
   }
   if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "builder launch failed");
   return ISL_OK;
@@ -567,7 +635,7 @@ isl_status Scaffold::table_to_csr(const Table& t, uint64_t n, bool kept, uint64_
 }
 
 void Scaffold::hand_rows_to(isl_index* r) {
-  r->d_emb = std::move(g->d_emb); r->d_norm2 = std::move(g->d_norm2);
+  r->d_emb = std::move(g->d_emb); r->d_emb16 = std::move(g->d_emb16); r->d_norm2 = std::move(g->d_norm2);
   r->nvec = g->nvec; r->emb_d = g->emb_d; r->emb_stride = g->emb_stride;
 }
 
@@ -602,9 +670,15 @@ extern "C" isl_status isl_index_build(const isl_leann_config* cfg, const float* 
   return isl_index_build_ex(cfg, &o, vectors, n, d, levels, mem, device, out);
 }
 
-extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg_in, const isl_build_options* opts_in,
+extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg, const isl_build_options* opts,
                                          const float* vectors, uint64_t n, uint64_t d, const uint64_t* levels,
                                          int32_t mem, int32_t device, isl_index** out) {
+  return isl_index_build_rows(cfg, opts, vectors, ISL_DTYPE_F32, n, d, levels, mem, device, out);
+}
+
+extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const isl_build_options* opts_in,
+                                           const void* vectors, int32_t dtype, uint64_t n, uint64_t d,
+                                           const uint64_t* levels, int32_t mem, int32_t device, isl_index** out) {
   using isl::fail;
   if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
@@ -613,6 +687,7 @@ extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg_in, const i
     ISL_TRY(isl_build::check_build_options(opts_in, true));
     opts = *opts_in;
   }
+  ISL_TRY(isl_build::check_row_dtype(dtype));
   isl_leann_config cfg;
   if (cfg_in) cfg = *cfg_in;
   else isl_leann_config_paper_default(&cfg);
@@ -631,7 +706,7 @@ extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg_in, const i
   const uint32_t m0 = (uint32_t)cfg.m0, ef = (uint32_t)cfg.ef_construction;
 
   Scaffold c;
-  ISL_TRY(c.open(cfg, opts, false, vectors, n, d, mem, device, isl_plan::largest_step(steps), m0, ef));
+  ISL_TRY(c.open(cfg, opts, false, vectors, dtype, n, d, mem, device, isl_plan::largest_step(steps), m0, ef));
   Table t{nullptr, nullptr, m0};
   ISL_TRY(c.alloc(&t.ell, n * (m0 + 1)));
   ISL_TRY(c.alloc(&t.deg, n, true));
@@ -648,8 +723,13 @@ extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg_in, const i
   for (const isl_plan::Step& s : steps) {
     g->has_entry = true;
     g->entry_point = entry;  // :669: entry_point.unwrap_or(0) as of the start of the step
-    hipLaunchKernelGGL(gather_rows_kernel, dim3((uint32_t)((s.count * d + 255) / 256)), dim3(256), 0, 0,
-                       g->d_emb, g->emb_stride, (uint32_t)d, s.first, s.count, c.qbuf);
+    const dim3 ggrid((uint32_t)((s.count * d + 255) / 256));
+    if (g->d_emb16)  // the step's queries are the widened rows
+      hipLaunchKernelGGL(gather_rows_bf16_kernel, ggrid, dim3(256), 0, 0, g->d_emb16.get(), g->emb_stride, (uint32_t)d,
+                         s.first, s.count, c.qbuf);
+    else
+      hipLaunchKernelGGL(gather_rows_kernel, ggrid, dim3(256), 0, 0, g->d_emb.get(), g->emb_stride, (uint32_t)d,
+                         s.first, s.count, c.qbuf);
     if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "gather launch failed");
     ISL_TRY(c.insert(t, s.count, s.count > 1, s.first));
     if (hipDeviceSynchronize() != hipSuccess) return fail(ISL_ERR_DEVICE, "builder kernels failed");
@@ -721,7 +801,7 @@ extern "C" isl_status isl_select_neighbors(const isl_index* idx, const isl_build
   p.pitch = nmax; p.cap = (uint32_t)cap; p.nmax = nmax;
   isl_build::by_metric(idx->cfg.metric, [&](auto mc) {
     hipLaunchKernelGGL(select_neighbors_kernel<decltype(mc)::value>, dim3((uint32_t)nb), dim3(64),
-                       sel_lds(idx->emb_d, nmax, (uint32_t)cap), 0, p);
+                       sel_lds(false, idx->emb_d, nmax, (uint32_t)cap), 0, p);
   });
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return fail(ISL_ERR_DEVICE, "select_neighbors kernel failed");

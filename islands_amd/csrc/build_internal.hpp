@@ -37,12 +37,17 @@ struct BuildParams {
   const uint32_t* node_levels;  // [n] HnswNode::level
   uint32_t layer;
   uint32_t* cur_of;             // [n] `current` of every node being inserted: selected[0] after a layer
+  // LeannIndex::build over bf16 rows (isl_index_build_rows): the table the kernels' bf16 instantiations read
+  // instead of emb (NULL otherwise); stride is then in bf16 elements, norm2 is of the widened values
+  const uint16_t* emb16;
 };
 
 // struct_size, rule and alpha of caller-supplied options, before any device call
 isl_status check_build_options(const isl_build_options* o, bool need_rule);
 // bytes of LDS of the reference-rule link kernel and of the insertion descent (tile + query)
 size_t link_lds(uint64_t d);
+// ISL_DTYPE_F32 / ISL_DTYPE_BF16, before any device call
+isl_status check_row_dtype(int32_t dtype);
 
 // f(std::integral_constant<int, METRIC>{}) for the metric of a call: the one place a kernel template's
 // metric argument is chosen at run time
@@ -93,11 +98,13 @@ struct Scaffold {
   isl_status alloc_bytes(void** out, uint64_t bytes, bool zero, bool kept);
   // The construction graph over `vectors` and the buffers of steps of up to B nodes, rows of up to m0 ids.
   // cfg: metric (and, for LeannIndex::build, the hub rule); opts: the selection rule.
+  // dtype: what `vectors` holds and the construction graph stores (isl_set_embeddings); bf16 rows are for
+  // LeannIndex::build alone (not with hnsw, not with `old`).
   // With `old` (a finished graph that grows, isl_hnsw_insert) the rows come from two sources: the first
   // old->nvec of the n are old's rows and norms, copied on the device; `vectors` holds the n - old->nvec new ones.
-  isl_status open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw, const float* vectors,
-                  uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0, uint32_t ef,
-                  const isl_index* old = nullptr);
+  isl_status open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw, const void* vectors,
+                  int32_t dtype, uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0,
+                  uint32_t ef, const isl_index* old = nullptr);
   // Inserts `cnt` nodes on table `t`, their rows being in qbuf: construction search over the table, selection
   // (truncation / hub rule, or select()), links both ways.  The nodes are id0 .. id0 + cnt - 1, or node_ids[]
   // on `layer` of an HnswGraph.  Returns once the kernels are launched.
@@ -111,7 +118,7 @@ struct Scaffold {
                           uint32_t* d_flag);
   // fixed-width table -> CSR arrays on the device (one wave per row)
   isl_status table_to_csr(const Table& t, uint64_t n, bool kept, uint64_t** off, uint32_t** adj);
-  // the finished index takes over the rows (and their norms) of the construction graph
+  // the finished index takes over the rows (f32 or bf16, and their norms) of the construction graph
   void hand_rows_to(isl_index* r);
   // success: the finished graph leaves with what was kept for it
   isl_index* release();

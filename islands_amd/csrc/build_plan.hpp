@@ -88,5 +88,14 @@ constexpr size_t link_lds(size_t tile_bytes, uint32_t d) { return tile_bytes + (
 constexpr size_t select_lds(size_t tile_bytes, uint32_t d, uint32_t nmax, uint32_t M) {
   return link_lds(tile_bytes, d) + (size_t)nmax * 16 + (size_t)M * 4;
 }
+// bf16 rows: the kernels measure with the tile-free routine (direct_distances over 16-byte loads of 8
+// elements), so there is no tile -- the LDS is the query, widened to f32, plus the lists.  That routine
+// walks the query in steps of 32 elements and fetches the operand of a step whole, the last one included:
+// d rounded up to whole steps, plus the same 16 of slack.
+constexpr uint32_t query_floats_bf16(uint32_t d) { return (d + 31u) / 32u * 32u + 16u; }
+constexpr size_t link_lds_bf16(uint32_t d) { return (size_t)query_floats_bf16(d) * 4; }
+constexpr size_t select_lds_bf16(uint32_t d, uint32_t nmax, uint32_t M) {
+  return link_lds_bf16(d) + (size_t)nmax * 16 + (size_t)M * 4;
+}
 
 }  // namespace isl_plan

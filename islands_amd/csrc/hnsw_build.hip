@@ -197,7 +197,7 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
   lcfg.metric = cfg.metric;
   lcfg.prune_ratio = 0.0f;
   isl_build::Scaffold c;
-  ISL_TRY(c.open(lcfg, opts, true, vectors, n, d, mem, device, B, m0, ef, old));
+  ISL_TRY(c.open(lcfg, opts, true, vectors, ISL_DTYPE_F32, n, d, mem, device, B, m0, ef, old));
   isl_index* g = c.g;
 
   // one table per layer, and what the descent and the per-layer gathers read

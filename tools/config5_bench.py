@@ -3,13 +3,14 @@ stress (benches/vector_ops.rs batch_calculate as ONE query x row GEMM on the bf1
 PQ distance tables + codes (benches/pq_compression.rs shapes: build_distance_tables,
 table_distance), the two-level re-rank search over them and the plain traversal over the bf16 rows.
 
-    python tools/config5_bench.py [--nodes 10000000] [--dim 4096] [--nq 4096]
+    python tools/config5_bench.py [--nodes 10000000] [--dim 4096] [--nq 4096] [--graph harness|product]
 
 One JSON line with both rooflines: `mfma` for the distance GEMM (flops / kernel time against the
 2.5 PFLOP/s dense bf16 peak), `hbm` for the traversal (SURVEY 8d bytes with s = 2 / wall time
 against 8 TB/s).  Rows are generated and kept in bf16 only (82 GB at 10M x 4096; never a 164 GB
 float32 copy): the harness of tools/synth.py builds the graph on the bf16 rows, ground truth is
-the exact top-k under the library's own bf16 distance GEMM."""
+the exact top-k under the library's own bf16 distance GEMM.  --graph product takes the index from the
+library's own builder instead (LeannIndex.build_bf16 on the resident bf16 rows, the diverse rule)."""
 import argparse
 import ctypes as C
 import gc
@@ -54,6 +55,9 @@ def main():
     ap.add_argument("--tl-ratios", default="0.3,0.5,0.7,0.85,1.0")
     ap.add_argument("--tl-efs", default="128,256")
     ap.add_argument("--skip-two-level", action="store_true")
+    ap.add_argument("--graph", choices=["harness", "product"], default="harness",
+                    help="harness: synth.build_graph; product: the library's builder over the bf16 rows (diverse rule)")
+    ap.add_argument("--build-batch", type=int, default=4096, help="--graph product: nodes inserted per step")
     ap.add_argument("--graph-only", action="store_true", help="stop after the graph (harness check)")
     a = ap.parse_args()
     N, d, nq, k, ef = a.nodes, a.dim, a.nq, a.k, a.ef
@@ -127,15 +131,29 @@ def main():
     # (every harness GEMM on float32 operands and every per-chunk tensor within 1 GiB: round 2 lost a box
     # to a GPU memory access fault inside this builder on bf16 operands at d = 4096 -- tools/synth.py,
     # _CHUNK_BYTES, has what is known about it)
-    off, nb, entry = synth.build_graph(x16, m0=60, precise=True)
-    torch.cuda.synchronize()
-    gst = synth.graph_stats(off)
-    log(f"graph in {time.time() - t0:.1f}s: {gst}")
-    if a.graph_only:
-        return
-    idx = ia.LeannIndex.from_device_csr(off.data_ptr(), nb.data_ptr(), N, entry, d, ia.LeannConfig.paper_default(), device=0)
-    del off, nb
-    idx.set_embeddings_bf16(None, device_ptr=x16.view(torch.int16).data_ptr(), n=N, d=d)
+    if a.graph == "product":
+        # isl_index_build_rows: the graph is built over the bf16 rows and the index keeps its own copy of them
+        idx = ia.LeannIndex.build_bf16(config=ia.LeannConfig.paper_default(), batch=a.build_batch, select="diverse",
+                                       device_ptr=x16.view(torch.int16).data_ptr(), n=N, d=d)
+        sample = np.random.default_rng(0).integers(1, N, size=min(N - 1, 20000))
+        degs = np.array([len(idx.get_neighbors(int(i))) for i in sample])
+        gst = {"builder": "LeannIndex.build_bf16, diverse rule", "nodes_per_step": a.build_batch,
+               "build_s": round(time.time() - t0, 1), "mean_degree_of_sample": round(float(degs.mean()), 2),
+               "min_degree_of_sample": int(degs.min())}
+        log(f"graph: {gst}")
+        if a.graph_only:
+            return
+    else:
+        off, nb, entry = synth.build_graph(x16, m0=60, precise=True)
+        torch.cuda.synchronize()
+        gst = synth.graph_stats(off)
+        gst["build_s"] = round(time.time() - t0, 1)
+        log(f"graph in {time.time() - t0:.1f}s: {gst}")
+        if a.graph_only:
+            return
+        idx = ia.LeannIndex.from_device_csr(off.data_ptr(), nb.data_ptr(), N, entry, d, ia.LeannConfig.paper_default(), device=0)
+        del off, nb
+        idx.set_embeddings_bf16(None, device_ptr=x16.view(torch.int16).data_ptr(), n=N, d=d)
     torch.cuda.synchronize()
     log("index resident (its own copy of the bf16 rows)")
 
@@ -237,6 +255,7 @@ def main():
 
     print(json.dumps({
         "metric": "BASELINE config 5: 10M x 4096 bf16, query batch 4096 (distance GEMM + PQ re-rank + traversal)",
+        "graph_source": a.graph,
         "value": round(a.steps * nq / dt, 1), "unit": "queries/s", "recall_at_10": round(rec, 4),
         "config": {"workload": f"{N} x {d} bf16 rows resident in HBM, query batch {nq}, k={k}, ef={ef}, cosine, "
                                f"{depth} batches in flight", "graph": gst, "distinct_batches": nb_batches,
