@@ -246,7 +246,8 @@ typedef struct isl_search_stats {
   uint64_t queries;
   uint64_t expansions;     /* H: candidates expanded */
   uint64_t edges;          /* E: neighbour ids read */
-  uint64_t evals;          /* V: embeddings fetched / distances evaluated */
+  uint64_t evals;          /* V: embeddings fetched / distances evaluated (an index with entry seeds: the
+                              pick's evaluations against its L2-resident seed table are not counted) */
   uint64_t pushes;         /* heap insertions */
   uint64_t exact_path;     /* queries answered by the heap-exact kernel */
   uint64_t replayed;       /* queries whose tied prefix was re-ordered by the replay kernel */
@@ -335,6 +336,48 @@ isl_status isl_search(const isl_index* idx, const float* query, uint64_t d, uint
  * points and isl_search_wait alike); zeros when there is none.  Calls made by other threads never
  * show up here -- use isl_search_wait_stats for a per-call record. */
 isl_status isl_search_last_stats(const isl_index* idx, isl_search_stats* out);
+
+/* ---- entry seeds (extension; the reference enters every search at entry_point, leann.rs:911) ----
+ * A LeannIndex may carry an entry-seed table: E node ids plus a contiguous device copy of their rows.
+ * While the table is non-empty every plain search of the index -- isl_search, isl_search_batch, _async,
+ * _device, _device_async and each shard of a sharded submit -- starts query q at
+ *   pick(q) = the seed at the smallest position p minimising Distance::calculate(metric, q, x[seeds[p]])
+ * in the search's total order of distances (-0 == +0, NaN last), and is otherwise the reference's search:
+ * ids, distances, count and the H / E / V / push counters are those of the reference search of the same
+ * graph with entry_point = pick(q).  The pick's own E evaluations are NOT in V: the table stays resident
+ * in L2 and adds no HBM row traffic, which is what V stands for in the roofline formula; V counts the
+ * entry node once, as always.  Two-level searches and searches over the recompute provider IGNORE the
+ * table and keep entry_point.  With no table (the default) nothing changes: no launch, buffer or counter.
+ * The table is dropped by whatever replaces the rows it copied (isl_set_embeddings,
+ * isl_set_recompute_provider, a fresh isl_index_upload) and is not part of isl_index_to_bytes /
+ * isl_index_save, which are the reference's format: keep the ids from isl_index_entry_seeds and set them
+ * again after a load.  Setting or selecting while searches are in flight -> ISL_ERR_SEARCH, as
+ * isl_index_prepare.  An isl_index_prepare made after the seeds are set covers the pick's buffers
+ * (isl_search_stats::allocations stays 0).  ISL_ENTRY_SEEDS=N in the environment makes isl_index_build,
+ * isl_index_build_ex and isl_index_build_rows select N seeds for the index they return (unset or 0: none;
+ * not a decimal count -> ISL_ERR_INVALID_ARGUMENT; above the cap -> ISL_ERR_UNSUPPORTED).
+ * Common errors: a NULL index -> ISL_ERR_INVALID_ARGUMENT; count > ISL_MAX_ENTRY_SEEDS -> ISL_ERR_UNSUPPORTED;
+ * the index of an HnswGraph -> ISL_ERR_UNSUPPORTED; an empty index -> ISL_ERR_EMPTY_COLLECTION; no rows
+ * resident on the device (none attached, or the recompute provider) -> ISL_ERR_UNSUPPORTED. */
+#define ISL_MAX_ENTRY_SEEDS 65536ull
+/* Greedy k-centre selection of min(count, len) seeds, installed as the index's table (count == 0 clears it):
+ *   seeds[0] = entry_point;  mind[r] = D(x[seeds[0]], x[r]) for every row r;
+ *   repeat: j = the row not yet chosen with the largest mind[j] (ties: the smaller id); seeds += j;
+ *           mind[r] = min(mind[r], D(x[j], x[r]))
+ * with D(a, b) = Distance::calculate(metric, a, b) (the seed is a), bf16 rows as their f32 images, min / largest
+ * in the total order above.  One pass over the rows per seed, no host round trip between passes.
+ * out_ids (may be NULL) receives the ids in selection order, *out_count (may be NULL) their number. */
+isl_status isl_index_select_entry_seeds(isl_index* idx, uint64_t count, uint64_t* out_ids, uint64_t* out_count);
+/* Installs the caller's seeds (count == 0 clears the table).  Repeated ids are accepted (the pick's tie rule
+ * makes them harmless); an id >= len (or without a row) -> ISL_ERR_NODE_NOT_FOUND with the id. */
+isl_status isl_index_set_entry_seeds(isl_index* idx, const uint64_t* ids, uint64_t count);
+/* *count = seeds in the table; the first min(cap, *count) ids go to `out` (NULL with cap == 0). */
+isl_status isl_index_entry_seeds(const isl_index* idx, uint64_t* out, uint64_t cap, uint64_t* count);
+/* out_ids[q] = seeds[pick(q)] for nq queries of d floats (d != the rows' -> ISL_ERR_DIMENSION_MISMATCH; no table
+ * -> ISL_ERR_INVALID_ARGUMENT).  mem applies to queries and out_ids alike; runs on `stream` and is synchronised
+ * before returning.  Must not run concurrently with the two setters above. */
+isl_status isl_index_pick_entries(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d,
+                                  uint64_t* out_ids, int32_t mem, void* stream);
 
 /* ---- distance.rs ---- */
 /* Distance::calculate, distance.rs:38-52. */

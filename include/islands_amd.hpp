@@ -205,6 +205,28 @@ class LeannIndex {
     check(isl_set_recompute_provider(h_, enc, tokens.data(), nullptr, n, L, normalize ? 1 : 0,
                                      keep_rows ? 1 : 0, ISL_MEM_HOST));
   }
+  // entry seeds (no reference counterpart): plain searches start at the seed nearest to the query
+  std::vector<uint64_t> select_entry_seeds(uint64_t count) {
+    std::vector<uint64_t> ids(count < len() ? count : len());
+    uint64_t n = 0;
+    check(isl_index_select_entry_seeds(h_, count, ids.data(), &n));
+    ids.resize(n);
+    return ids;
+  }
+  void set_entry_seeds(const std::vector<uint64_t>& ids) { check(isl_index_set_entry_seeds(h_, ids.data(), ids.size())); }
+  std::vector<uint64_t> entry_seeds() const {
+    uint64_t n = 0;
+    check(isl_index_entry_seeds(h_, nullptr, 0, &n));
+    std::vector<uint64_t> ids(n);
+    check(isl_index_entry_seeds(h_, ids.data(), n, &n));
+    return ids;
+  }
+  // queries: nq rows of dimension() floats, row-major
+  std::vector<uint64_t> pick_entries(const std::vector<float>& queries, uint64_t nq) const {
+    std::vector<uint64_t> ids(nq);
+    check(isl_index_pick_entries(h_, queries.data(), nq, nq ? queries.size() / nq : 0, ids.data(), ISL_MEM_HOST, nullptr));
+    return ids;
+  }
   // no reference counterpart: sets up every search lane ahead of time (isl_index_prepare)
   void prepare(uint64_t max_nq, uint64_t max_ef, uint64_t max_k = 10, int32_t lanes = 8) {
     check(isl_index_prepare(h_, max_nq, max_ef, max_k, lanes));

@@ -414,6 +414,45 @@ class LeannIndex:
                                                _ptr(cnt), cap, _ptr(out), _ptr(ocnt)))
         return out[:, :cap], ocnt
 
+    # ---- extension: entry seeds, a nearest-seed start for every query of a plain search ----
+    def select_entry_seeds(self, count: int) -> np.ndarray:
+        """isl_index_select_entry_seeds: greedy k-centre selection of min(count, len) seeds from the entry
+        point, installed as the index's entry-seed table.  Returns the ids in selection order."""
+        out = np.zeros(max(min(int(count), len(self)), 1), dtype=np.uint64)
+        n = C.c_uint64()
+        _check(_ffi.lib().isl_index_select_entry_seeds(self._h, count, _ptr(out), C.byref(n)))
+        return out[:n.value]
+
+    def set_entry_seeds(self, ids) -> "LeannIndex":
+        """isl_index_set_entry_seeds: the caller's seeds (an empty list clears the table).  The table is not
+        serialised: keep entry_seeds() and set them again after a load."""
+        a = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        _check(_ffi.lib().isl_index_set_entry_seeds(self._h, _ptr(a) if a.size else None, a.size))
+        return self
+
+    def entry_seeds(self) -> np.ndarray:
+        n = C.c_uint64()
+        _check(_ffi.lib().isl_index_entry_seeds(self._h, None, 0, C.byref(n)))
+        out = np.zeros(max(n.value, 1), dtype=np.uint64)
+        _check(_ffi.lib().isl_index_entry_seeds(self._h, _ptr(out), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def pick_entries(self, queries=None, d_queries_ptr: int | None = None, nq: int | None = None,
+                     d: int | None = None, d_out_ptr: int | None = None, stream: int = 0):
+        """isl_index_pick_entries: the seed every query of a plain search would start at.  Either a host
+        matrix (returns ids [nq] u64), or (d_queries_ptr, nq, d, d_out_ptr) for buffers on the index's device."""
+        if d_queries_ptr is not None:
+            _check(_ffi.lib().isl_index_pick_entries(self._h, C.c_void_p(d_queries_ptr), nq, d,
+                                                     C.c_void_p(d_out_ptr), MEM_DEVICE, C.c_void_p(stream)))
+            return None
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        out = np.zeros(max(q.shape[0], 1), dtype=np.uint64)
+        _check(_ffi.lib().isl_index_pick_entries(self._h, _ptr(q), q.shape[0], q.shape[1], _ptr(out), MEM_HOST,
+                                                 None))
+        return out[:q.shape[0]]
+
     @classmethod
     def from_device_csr(cls, d_offsets_ptr: int, d_neighbors_ptr: int, num_nodes: int,
                         entry_point: int | None, dimension: int | None,

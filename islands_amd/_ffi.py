@@ -171,6 +171,10 @@ SIGNATURES = {
                                    P(C.c_void_p)]),
     "isl_select_neighbors": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, C.c_void_p, u64, C.c_void_p,
                                    u64, C.c_void_p, C.c_void_p]),
+    "isl_index_select_entry_seeds": (i32, [C.c_void_p, u64, C.c_void_p, P(u64)]),
+    "isl_index_set_entry_seeds": (i32, [C.c_void_p, C.c_void_p, u64]),
+    "isl_index_entry_seeds": (i32, [C.c_void_p, C.c_void_p, u64, P(u64)]),
+    "isl_index_pick_entries": (i32, [C.c_void_p, C.c_void_p, u64, u64, C.c_void_p, i32, C.c_void_p]),
     "isl_index_metadata_new": (None, [u64, u64, C.c_int64, P(IndexMetadataC)]),
     "isl_storage_write_metadata": (i32, [P(IndexMetadataC), P(C.c_void_p), P(C.c_size_t)]),
     "isl_storage_read_metadata": (i32, [C.c_void_p, C.c_size_t, P(IndexMetadataC), P(C.c_size_t)]),

@@ -559,6 +559,7 @@ isl_status isl_index_upload(isl_index* idx, int32_t device) {
     return fail(ISL_ERR_UNSUPPORTED, "index already resident on device %d", idx->device);
   if (idx->d_off) return ISL_OK;  // already uploaded
   if (!idx->host_csr_valid) return fail(ISL_ERR_INVALID_ARGUMENT, "no host CSR to upload");
+  drop_entry_seeds(idx);  // a table belongs to the rows of one residency
   if (idx->num_nodes >= kMaxDeviceId)
     return fail(ISL_ERR_UNSUPPORTED, "num_nodes %llu exceeds the device id range",
                 (unsigned long long)idx->num_nodes);
@@ -711,6 +712,7 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
   std::lock_guard<std::mutex> lock(idx->mu);
   if (any_lane_busy(idx))  // their kernels read the tables freed below
     return fail(ISL_ERR_SEARCH, "Search error: the embedding provider cannot be swapped while searches are in flight");
+  drop_entry_seeds(idx);  // copies of rows that are about to go
   idx->d_emb.reset();
   idx->d_emb16.reset();
   free_exact_pool(idx->pool);  // sized by the row count: rebuilt by the next prepare / search
@@ -817,6 +819,7 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
   std::lock_guard<std::mutex> lock(idx->mu);
   if (any_lane_busy(idx))
     return fail(ISL_ERR_SEARCH, "Search error: the embedding provider cannot be swapped while searches are in flight");
+  drop_entry_seeds(idx);  // the seeds' rows were the old provider's
   const uint64_t d = enc->cfg.hidden, stride = (d + 3) / 4 * 4;
   // (d_emb16 too: bf16 rows of an earlier in-memory provider would otherwise stay the table the
   // searches read)

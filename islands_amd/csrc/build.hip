@@ -744,7 +744,16 @@ extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const
   c.res->max_level = max_level;
   if (levels) c.res->levels.assign(levels, levels + n);
   c.hand_rows_to(c.res);
-  *out = c.release();
+  isl_index* built = c.release();
+  // ISL_ENTRY_SEEDS=N: the finished index leaves with N entry seeds selected (as isl_index_select_entry_seeds)
+  const isl_status seeded = isl::env_entry_seeds(built);
+  if (seeded != ISL_OK) {
+    const isl::ErrorRecord keep = isl::last_error();
+    isl_index_free(built);
+    isl::last_error() = keep;
+    return seeded;
+  }
+  *out = built;
   return ISL_OK;
 }
 

@@ -100,7 +100,8 @@ struct SearchWorkspace {
   PinnedBuffer<uint32_t> h_head;
   DeviceBuffer<uint64_t> d_prof;    // ISL_DEBUG phase timers of the call in flight
   DeviceBuffer<uint64_t> d_tline;   // ISL_TIMELINE: [nq][2] start / end ticks of every query of the call in flight
-  DeviceBuffer<uint32_t> q_entry;   // HnswGraph: [2][nq] layer-0 entry and descent evaluations per query
+  DeviceBuffer<uint32_t> q_entry;   // HnswGraph: [2][nq] layer-0 entry and descent evaluations per query; an index
+                                    // with entry seeds: [4][nq], the pick's packed 64-bit minima behind those two
   // recompute provider: the union of the calls this lane answers as one (search_recompute.hip, recompute_coalesced)
   DeviceBuffer<float> co_q;
   DeviceBuffer<uint64_t> co_ids;
@@ -199,6 +200,16 @@ struct isl_index {
   isl::DeviceBuffer<float> d_norm2;  // [nvec] sum of squares of every row, reference summation order
   uint64_t nvec = 0, emb_d = 0, emb_stride = 0;
 
+  // entry seeds (entry_seeds.hip): seed_count node ids and a contiguous copy of their rows, of the type and at
+  // the stride of the provider's table, with their norms; seed_count == 0 = no table (the default).  Dropped by
+  // whatever replaces the rows they were copied from.
+  std::vector<uint64_t> seed_ids;
+  uint64_t seed_count = 0;
+  isl::DeviceBuffer<uint32_t> d_seed_ids;      // [seed_count]
+  isl::DeviceBuffer<float> d_seed_rows;        // [seed_count][emb_stride] (f32 rows)
+  isl::DeviceBuffer<uint16_t> d_seed_rows16;   // ... or bf16 rows
+  isl::DeviceBuffer<float> d_seed_norm2;       // [seed_count]
+
   // graph under construction (build.hip): fixed-width adjacency rows, searched in place
   uint32_t* d_ell = nullptr;      // [num_nodes][ell_w]: the builder's rows (borrowed) or ell_copy
   uint32_t* d_ell_deg = nullptr;  // [num_nodes]
@@ -294,6 +305,16 @@ isl_status set_grown_embeddings(isl_index* idx, const isl_index* old, const floa
 // build_distance_tables (pq.rs:307-338) for nq device-resident queries into d_tables [nq][m][K]
 isl_status pq_launch_tables(const isl_pq* pq, const float* d_queries, uint64_t nq, float* d_tables,
                             hipStream_t st);
+// entry_seeds.hip -- forgets the entry-seed table (under idx->mu, no search in flight)
+void drop_entry_seeds(isl_index* idx);
+// ... the nearest seed of nq device-resident queries, enqueued on `st`: node ids into q_entry [nq] (with
+// q_evals [nq] = 1 and status [nq] = QS_OK, what the traversal reads beside a given entry) and / or as u64 into
+// d_out_ids; `packed` [nq] is scratch.  Nothing is launched for an index without seeds or for nq == 0.
+isl_status launch_entry_pick(const isl_index* idx, const float* d_queries, uint64_t nq, uint32_t* q_entry,
+                             uint32_t* q_evals, unsigned long long* packed, uint32_t* status, uint64_t* d_out_ids,
+                             hipStream_t st);
+// ... ISL_ENTRY_SEEDS=N after a successful build: selects N seeds for `idx` (unset or 0: nothing)
+isl_status env_entry_seeds(isl_index* idx);
 void free_workspace(SearchWorkspace& ws);
 void free_exact_pool(ExactPool& pool);
 // true while a search is in flight on any lane (call under idx->mu): provider / PQ setters and

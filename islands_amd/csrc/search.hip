@@ -397,6 +397,17 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     p.max_level = 0u;
     ISL_HIP(hipMemsetAsync(ws.status, 0, nq * 4, st));  // QS_OK: the fast kernel reads it where q_entry is set
   }
+  // entry seeds: a plain search over resident rows starts every query at the seed nearest to it (the pick is
+  // launched below, ahead of the traversal); two-level searches and the recompute provider keep entry_point
+  const bool seeded = idx->seed_count != 0 && !tl && !idx->recompute && !idx->is_hnsw && !idx->build_q_entry &&
+                      !warm && !resume && nq != 0;
+  if (seeded) {
+    ISL_TRY(ws.q_entry.reserve(nq * 4, &ws.alloc_events));
+    p.q_entry = ws.q_entry;
+    p.q_evals = ws.q_entry + nq;
+    p.entry_given = 1u;
+    p.max_level = 0u;
+  }
   if (tl) {
     const isl_pq* pq = idx->pq;
     const uint64_t want = std::max<uint64_t>(nq, 1) * pq->m * pq->K;
@@ -454,6 +465,11 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     const uint32_t dgrid = (uint32_t)std::min<uint64_t>(nq_grid, 8192);
     isl_launch::launch_descent(metric, dgrid, cg.descent_lds, st, &p);
     ISL_HIP(hipGetLastError());
+  }
+  if (seeded) {
+    // q_entry[q] = the nearest seed, q_evals[q] = 1, status[q] = QS_OK (the fast kernel reads it where q_entry is set)
+    ISL_TRY(isl::launch_entry_pick(idx, c.queries, nq, ws.q_entry, ws.q_entry + nq,
+                                   reinterpret_cast<unsigned long long*>(ws.q_entry + 2 * nq), ws.status, nullptr, st));
   }
   if (tl) {
   } else if (use_fast) {
@@ -1009,6 +1025,7 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
     ISL_TRY(prepare_host_staging(ws, max_nq, d, std::max<uint64_t>(max_k, 1)));
     if (idx->recompute) ISL_TRY(prepare_recompute(ws, max_nq, cg_max.state_words));
     if (idx->is_hnsw) ISL_TRY(ws.q_entry.reserve(max_nq * 2, &ws.alloc_events));
+    else if (idx->seed_count) ISL_TRY(ws.q_entry.reserve(max_nq * 4, &ws.alloc_events));  // entry, evals, packed minima
     if (idx->pq && idx->d_codes && !idx->is_hnsw && d == idx->pq->dimension)
       ISL_TRY(ws.tl_tables.reserve(max_nq * idx->pq->m * idx->pq->K, &ws.alloc_events));
     memset(ws.h_q, 0, max_nq * d * 4);
