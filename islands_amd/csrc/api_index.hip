@@ -559,7 +559,7 @@ isl_status isl_index_upload(isl_index* idx, int32_t device) {
     return fail(ISL_ERR_UNSUPPORTED, "index already resident on device %d", idx->device);
   if (idx->d_off) return ISL_OK;  // already uploaded
   if (!idx->host_csr_valid) return fail(ISL_ERR_INVALID_ARGUMENT, "no host CSR to upload");
-  drop_entry_seeds(idx);  // a table belongs to the rows of one residency
+  idx->seeds = {};  // a table belongs to the rows of one residency
   if (idx->num_nodes >= kMaxDeviceId)
     return fail(ISL_ERR_UNSUPPORTED, "num_nodes %llu exceeds the device id range",
                 (unsigned long long)idx->num_nodes);
@@ -676,27 +676,54 @@ isl_status isl_index_from_device_csr(const isl_leann_config* cfg, int32_t device
   return ISL_OK;
 }
 
-// Rows [first, nvec) of the f32 provider's table (allocated for nvec rows of emb_d floats at emb_stride, plus
-// the slack) from `rows` (host or device, `mem`), the padding and the slack zeroed, and their norms.
-static isl_status upload_f32_rows(isl_index* idx, uint64_t first, const float* rows, int32_t mem) {
-  const uint64_t n = idx->nvec, cnt = n - first, d = idx->emb_d, stride = idx->emb_stride;
-  float* at = idx->d_emb + first * stride;
-  if (stride != d) ISL_HIP(hipMemset(at, 0, (size_t)(cnt * stride + 256) * sizeof(float)));
-  else ISL_HIP(hipMemset(idx->d_emb + n * stride, 0, 256 * sizeof(float)));
-  hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  if (stride == d) ISL_HIP(hipMemcpy(at, rows, (size_t)cnt * d * 4, kind));
-  else ISL_HIP(hipMemcpy2D(at, stride * 4, rows, d * 4, d * 4, cnt, kind));
-  // norm_b of cosine_distance (distance.rs:79) depends on the row alone: computed once, in the
-  // reference's left-to-right order, and reused by every search
+}  // extern "C"
+
+// norm_b of cosine_distance (distance.rs:79) depends on the row alone: computed once, in the reference's
+// left-to-right order, and reused by every search
+static void launch_row_norm2(const float* rows, uint64_t cnt, uint64_t d, uint64_t stride, float* norm2) {
   using namespace isl_dev;
-  size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
-  uint32_t grid = (uint32_t)std::min<uint64_t>((cnt + 63) / 64, 8192);
-  hipLaunchKernelGGL(row_norm2_kernel, dim3(grid), dim3(64), lds, 0, at, cnt, (uint32_t)d, stride,
-                     idx->d_norm2 + first);
+  const size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((cnt + 63) / 64, 8192);
+  hipLaunchKernelGGL(row_norm2_kernel, dim3(grid), dim3(64), lds, 0, rows, cnt, (uint32_t)d, stride, norm2);
+}
+
+isl_status isl::RowTable::fill(uint64_t first, uint64_t count, const void* src, int32_t mem) {
+  const uint64_t es = isl_rows::elem_size(dtype_), d = d_, stride = stride_;
+  unsigned char* at = block_ + first * stride * es;
+  const uint64_t slack = first + count == n_ ? isl_rows::slack(dtype_) : 0;
+  if (stride != d) ISL_HIP(hipMemset(at, 0, (size_t)((count * stride + slack) * es)));
+  else if (slack) ISL_HIP(hipMemset(at + count * stride * es, 0, (size_t)(slack * es)));
+  const hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (stride == d) ISL_HIP(hipMemcpy(at, src, (size_t)(count * d * es), kind));
+  else ISL_HIP(hipMemcpy2D(at, stride * es, src, d * es, d * es, count, kind));
+  if (!is_bf16()) {
+    launch_row_norm2(f32() + first * stride, count, d, stride, norm2_ + first);
+  } else {
+    // bf16 rows are bit patterns and the provider's vectors their exact f32 images: widen a chunk of rows to
+    // f32 and reuse the f32 kernel
+    const uint64_t stride32 = isl_rows::stride(ISL_DTYPE_F32, d), chunk = isl_rows::norm_chunk_rows(count, d);
+    DeviceBuffer<float> tmp;
+    ISL_TRY(tmp.reserve(isl_rows::norm_chunk_floats(chunk, d)));
+    ISL_HIP(hipMemset(tmp, 0, (size_t)isl_rows::norm_chunk_floats(chunk, d) * 4));
+    for (uint64_t o = 0; o < count; o += chunk) {
+      const uint64_t c = std::min(chunk, count - o);
+      hipLaunchKernelGGL(widen_bf16_kernel, dim3((uint32_t)((c * d + 255) / 256)), dim3(256), 0, 0,
+                         bf16() + (first + o) * stride, stride, (uint32_t)d, c, tmp.get(), stride32);
+      launch_row_norm2(tmp, c, d, stride32, norm2_ + first + o);
+    }
+  }
   ISL_HIP(hipGetLastError());
-  ISL_HIP(hipDeviceSynchronize());
+  ISL_HIP(hipDeviceSynchronize());  // (also: tmp goes when this returns)
   return ISL_OK;
 }
+
+isl_status isl::RowTable::zero() {
+  ISL_HIP(hipMemset(block_, 0, (size_t)(isl_rows::alloc_elems(dtype_, n_, d_) * isl_rows::elem_size(dtype_))));
+  ISL_HIP(hipMemset(norm2_, 0, (size_t)n_ * 4));
+  return ISL_OK;
+}
+
+extern "C" {
 
 // InMemoryEmbeddingProvider::new, leann.rs:111-120
 isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
@@ -712,77 +739,34 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
   std::lock_guard<std::mutex> lock(idx->mu);
   if (any_lane_busy(idx))  // their kernels read the tables freed below
     return fail(ISL_ERR_SEARCH, "Search error: the embedding provider cannot be swapped while searches are in flight");
-  drop_entry_seeds(idx);  // copies of rows that are about to go
-  idx->d_emb.reset();
-  idx->d_emb16.reset();
+  if (dtype == ISL_DTYPE_BF16 && idx->is_hnsw) return fail(ISL_ERR_UNSUPPORTED, "the HnswGraph facade keeps f32 vectors");
+  // every check is above: from here on the old provider goes
+  idx->seeds = {};  // copies of rows that are about to go
   free_exact_pool(idx->pool);  // sized by the row count: rebuilt by the next prepare / search
   idx->recompute = false;  // back to the in-memory provider
-  if (dtype == ISL_DTYPE_BF16) {
-    // rows are bf16 bit patterns; the provider's vectors are their exact f32 images.  Rows start
-    // 16-byte aligned (stride = d rounded up to 8 elements), 1 KiB of slack like the f32 table.
-    if (idx->is_hnsw) return fail(ISL_ERR_UNSUPPORTED, "the HnswGraph facade keeps f32 vectors");
-    const uint64_t stride16 = (d + 7) / 8 * 8;
-    const size_t bytes16 = (size_t)(n * stride16 + 512) * 2;
-    ISL_TRY(idx->d_emb16.reserve(n * stride16 + 512));
-    ISL_HIP(hipMemset(idx->d_emb16, 0, bytes16));
-    hipMemcpyKind kind16 = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    ISL_HIP(hipMemcpy2D(idx->d_emb16, stride16 * 2, rows, d * 2, d * 2, n, kind16));
-    idx->nvec = n;
-    idx->emb_d = d;
-    idx->emb_stride = stride16;
-    idx->d_norm2.reset();
-    ISL_TRY(idx->d_norm2.reserve(n));
-    // norm_b in the reference's order: widen a chunk of rows to f32 and reuse the f32 kernel
-    using namespace isl_dev;
-    const uint64_t stride32 = (d + 3) / 4 * 4;
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(n, (256ull << 20) / (stride32 * 4)));
-    DeviceBuffer<float> tmp;
-    ISL_TRY(tmp.reserve(chunk * stride32 + 256));
-    ISL_HIP(hipMemset(tmp, 0, (size_t)(chunk * stride32 + 256) * 4));
-    const size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
-    for (uint64_t o = 0; o < n; o += chunk) {
-      const uint64_t c = std::min(chunk, n - o);
-      hipLaunchKernelGGL(widen_bf16_kernel, dim3((uint32_t)((c * d + 255) / 256)), dim3(256), 0, 0,
-                         idx->d_emb16 + o * stride16, stride16, (uint32_t)d, c, tmp.get(), stride32);
-      hipLaunchKernelGGL(row_norm2_kernel, dim3((uint32_t)std::min<uint64_t>((c + 63) / 64, 8192)), dim3(64), lds,
-                         0, tmp.get(), c, (uint32_t)d, stride32, idx->d_norm2 + o);
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) return fail(ISL_ERR_DEVICE, "bf16 row upload failed: %s", hipGetErrorString(e));
-    return ISL_OK;
-  }
-  uint64_t stride = (d + 3) / 4 * 4;  // rows start 16-byte aligned
-  ISL_TRY(idx->d_emb.reserve(n * stride + 256));  // slack for whole-slab reads
-  idx->d_norm2.reset();
-  ISL_TRY(idx->d_norm2.reserve(n));
+  ISL_TRY(idx->rows.allocate(dtype, n, d));
   idx->nvec = n;
-  idx->emb_d = d;
-  idx->emb_stride = stride;
-  return upload_f32_rows(idx, 0, static_cast<const float*>(rows), mem);
+  return idx->rows.fill(0, n, rows, mem);
 }
 
-// (re)allocates the recompute provider's row cache: slab, per-slot norms, slot map, owners
-static isl_status alloc_recompute_cache(isl_index* idx, uint64_t rows) {
+// (re)allocates the recompute provider's row cache: slot map, owners and, last, the slab of `rows` rows of d
+// floats with its per-slot norms -- idx->rows holds slots only once everything beside them is there
+static isl_status alloc_recompute_cache(isl_index* idx, uint64_t rows, uint64_t d) {
   // the old cache goes before the new one is allocated: the slab may be most of the card
-  idx->d_emb.reset(); idx->d_norm2.reset(); idx->d_slot_of.reset();
+  idx->rows.reset(); idx->d_slot_of.reset();
   idx->d_owner.reset(); idx->d_stamp.reset(); idx->d_slab_head.reset();
-  idx->slab_rows = 0;
-  const uint64_t stride = idx->emb_stride, n = idx->nvec;
   // a block of `count` elements, every byte `fill`
   auto fresh = [](auto& buf, uint64_t count, int fill) -> isl_status {
     ISL_TRY(buf.reserve(count));
     ISL_HIP(hipMemset(buf, fill, count * sizeof(*buf.get())));
     return ISL_OK;
   };
-  ISL_TRY(fresh(idx->d_emb, rows * stride + 256, 0));
-  ISL_TRY(fresh(idx->d_norm2, rows, 0));
-  ISL_TRY(fresh(idx->d_slot_of, n + 1, 0xFF));
+  ISL_TRY(fresh(idx->d_slot_of, idx->nvec + 1, 0xFF));
   ISL_TRY(fresh(idx->d_owner, rows, 0xFF));
   ISL_TRY(fresh(idx->d_stamp, rows, 0));
   ISL_TRY(fresh(idx->d_slab_head, 2, 0));  // [0] clock hand, [1] slots used so far
-  idx->slab_rows = rows;
-  return ISL_OK;
+  ISL_TRY(idx->rows.allocate(ISL_DTYPE_F32, rows, d));
+  return idx->rows.zero();
 }
 
 isl_status isl_index_set_recompute_cache_rows(isl_index* idx, uint64_t rows) {
@@ -794,12 +778,12 @@ isl_status isl_index_set_recompute_cache_rows(isl_index* idx, uint64_t rows) {
     return fail(ISL_ERR_SEARCH, "Search error: the row cache cannot be resized while searches are in flight");
   // a hop of one query needs up to 128 rows at once (plus the entry point): that is the floor
   rows = std::min<uint64_t>(idx->nvec, std::max<uint64_t>(rows, 256));
-  return alloc_recompute_cache(idx, rows);
+  return alloc_recompute_cache(idx, rows, idx->enc->cfg.hidden);
 }
 
 uint64_t isl_index_recompute_cache_bytes(const isl_index* idx) {
   if (!idx || !idx->recompute) return 0;
-  return (idx->slab_rows * idx->emb_stride + 256) * 4 + idx->slab_rows * 12 + (idx->nvec + 1) * 4;
+  return isl_rows::recompute_cache_bytes(idx->rows.n(), idx->rows.d(), idx->nvec);
 }
 
 // EmbeddingProvider backed by the encoder (recompute mode), see islands_amd.h.
@@ -819,23 +803,18 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
   std::lock_guard<std::mutex> lock(idx->mu);
   if (any_lane_busy(idx))
     return fail(ISL_ERR_SEARCH, "Search error: the embedding provider cannot be swapped while searches are in flight");
-  drop_entry_seeds(idx);  // the seeds' rows were the old provider's
-  const uint64_t d = enc->cfg.hidden, stride = (d + 3) / 4 * 4;
-  // (d_emb16 too: bf16 rows of an earlier in-memory provider would otherwise stay the table the
-  // searches read)
-  idx->d_emb16.reset();
+  idx->seeds = {};  // the seeds' rows were the old provider's
+  const uint64_t d = enc->cfg.hidden;
   idx->d_tokens.reset();
   idx->d_lens.reset();
   free_exact_pool(idx->pool);
   idx->recompute = false;
   // Recompute mode does not store embeddings (leann.rs:366-371): what is resident is the token
-  // table plus a BOUNDED row cache -- a slab of slab_rows rows, 4 bytes of slot map per node.  The
+  // table plus a BOUNDED row cache -- a slab of rows.n() rows, 4 bytes of slot map per node.  The
   // default slab (2^20 rows, or every node of a smaller index) holds what a batch of a thousand
   // queries visits; isl_index_set_recompute_cache_rows changes it.
   idx->nvec = n;
-  idx->emb_d = d;
-  idx->emb_stride = stride;
-  ISL_TRY(alloc_recompute_cache(idx, std::min<uint64_t>(n, 1ull << 20)));
+  ISL_TRY(alloc_recompute_cache(idx, std::min<uint64_t>(n, 1ull << 20), d));
   hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   ISL_TRY(idx->d_tokens.reserve(n * L));
   ISL_HIP(hipMemcpy(idx->d_tokens, tokens, (size_t)n * L * 2, kind));
@@ -845,9 +824,6 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
   }
   idx->enc = enc;
   idx->tok_L = (uint32_t)L;
-  idx->nvec = n;
-  idx->emb_d = d;
-  idx->emb_stride = stride;
   idx->enc_normalize = normalize;
   idx->keep_rows = keep_rows != 0;
   idx->recompute = true;
@@ -859,23 +835,20 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
 }  // extern "C"
 
 // The f32 provider of a graph that grows (Scaffold::open over rows from two sources): one table of
-// old->nvec + n_new rows, the first of them copied on the device from `old` together with their norms (a
-// row's norm is a function of the row alone: the copied value is the bits a recomputation would give), the
-// rest taken from `rows` as isl_set_embeddings takes them (upload_f32_rows).  `idx` is a fresh construction graph.
+// old's rows + n_new, the first of them copied on the device from `old` together with their norms (a row's
+// norm is a function of the row alone: the copied value is the bits a recomputation would give), the rest
+// taken from `rows` as isl_set_embeddings takes them (RowTable::fill).  `idx` is a fresh construction graph.
 isl_status isl::set_grown_embeddings(isl_index* idx, const isl_index* old, const float* rows, uint64_t n_new,
                                      uint64_t d, int32_t mem) {
-  const uint64_t n0 = old->nvec, n = n0 + n_new;
-  const uint64_t stride = (d + 3) / 4 * 4;
-  if (!old->d_emb || !old->d_norm2 || old->emb_d != d || old->emb_stride != stride)
+  const RowTable& o = old->rows;
+  const uint64_t n0 = o.n(), n = n0 + n_new;
+  if (!o.f32() || !o.norm2() || o.d() != d)
     return fail(ISL_ERR_UNSUPPORTED, "the graph's rows are not resident f32 rows of this dimension");
   ISL_TRY(use_device(idx->device));
   std::lock_guard<std::mutex> lock(idx->mu);
-  ISL_TRY(idx->d_emb.reserve(n * stride + 256));
-  ISL_TRY(idx->d_norm2.reserve(n));
-  ISL_HIP(hipMemcpy(idx->d_emb, old->d_emb, (size_t)n0 * stride * 4, hipMemcpyDeviceToDevice));
-  ISL_HIP(hipMemcpy(idx->d_norm2, old->d_norm2, (size_t)n0 * 4, hipMemcpyDeviceToDevice));
+  ISL_TRY(idx->rows.allocate(ISL_DTYPE_F32, n, d));
+  ISL_HIP(hipMemcpy(idx->rows.f32(), o.f32(), (size_t)n0 * o.stride() * 4, hipMemcpyDeviceToDevice));
+  ISL_HIP(hipMemcpy(idx->rows.norm2(), o.norm2(), (size_t)n0 * 4, hipMemcpyDeviceToDevice));
   idx->nvec = n;
-  idx->emb_d = d;
-  idx->emb_stride = stride;
-  return upload_f32_rows(idx, n0, rows, mem);
+  return idx->rows.fill(n0, n_new, rows, mem);
 }

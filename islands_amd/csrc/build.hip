@@ -480,7 +480,7 @@ size_t sel_lds(bool bf16, uint64_t d, uint32_t nmax, uint32_t M) {
 // one wave per node of the step, the kernel instantiated for the index's metric and row type
 template <bool DIVERSE, bool HNSW, typename ROWT = float>
 void launch_link_as(uint32_t metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  isl_build::by_metric(metric, [&](auto mc) {
+  isl::by_metric(metric, [&](auto mc) {
     hipLaunchKernelGGL((link_kernel<decltype(mc)::value, DIVERSE, HNSW, ROWT>), dim3(grid), dim3(64), lds, 0, p);
   });
 }
@@ -495,7 +495,7 @@ void launch_link(uint32_t metric, bool diverse, bool hnsw, uint32_t grid, size_t
   else launch_link_as<true, true>(metric, grid, lds, p);
 }
 void launch_select_diverse(uint32_t metric, uint32_t grid, size_t lds, const BuildParams& p) {
-  isl_build::by_metric(metric, [&](auto mc) {
+  isl::by_metric(metric, [&](auto mc) {
     if (p.emb16)
       hipLaunchKernelGGL((select_diverse_kernel<decltype(mc)::value, uint16_t>), dim3(grid), dim3(64), lds, 0, p);
     else
@@ -528,10 +528,10 @@ isl_status check_row_dtype(int32_t dtype) {
 
 Scaffold::~Scaffold() {
   const isl::ErrorRecord first = isl::last_error();
-  for (void* q : tmp) (void)hipFree(q);
-  for (void* q : keep) (void)hipFree(q);
+  keep.clear();
   isl_index_free(res);
-  if (g) {  // the tables and per-query arrays it searched were borrowed from tmp
+  if (g) {  // the tables and per-query arrays it searched were borrowed from tmp, which goes after this body:
+            // isl_index_free never sees them
     g->d_ell = nullptr; g->d_ell_deg = nullptr;
     g->build_q_entry = nullptr; g->build_q_evals = nullptr;
     isl_index_free(g);
@@ -542,9 +542,9 @@ Scaffold::~Scaffold() {
 isl_status Scaffold::alloc_bytes(void** out, uint64_t bytes, bool zero, bool kept) {
   bytes = bytes ? bytes : 4;
   void* q = nullptr;
-  if (hipMalloc(&q, bytes) != hipSuccess)
-    return isl::fail(ISL_ERR_DEVICE, "hipMalloc of %llu bytes failed for the builder", (unsigned long long)bytes);
-  (kept ? keep : tmp).push_back(q);
+  if (!kept) q = tmp.alloc<unsigned char>(bytes);
+  else if (keep.emplace_back().reserve(bytes) == ISL_OK) q = keep.back().get();
+  if (!q) return isl::fail(ISL_ERR_DEVICE, "hipMalloc of %llu bytes failed for the builder", (unsigned long long)bytes);
   if (zero && hipMemset(q, 0, bytes) != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "hipMemset failed");
   *out = q;
   return ISL_OK;
@@ -575,7 +575,8 @@ isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& 
   ISL_TRY(alloc(&cand_cnt, B));
   ISL_TRY(alloc(&p.sel, B * m0));
   ISL_TRY(alloc(&p.sel_cnt, B));
-  p.emb = g->d_emb; p.emb16 = g->d_emb16; p.norm2 = g->d_norm2; p.stride = g->emb_stride; p.d = (uint32_t)d;
+  p.emb = g->rows.f32(); p.emb16 = g->rows.bf16(); p.norm2 = g->rows.norm2(); p.stride = g->rows.stride();
+  p.d = (uint32_t)d;
   p.ef = ef;
   p.cand_ids = cand_ids; p.cand_dist = cand_dist; p.cand_cnt = cand_cnt;
   if (!hnsw) { p.hub_percentile = cfg.hub_percentile; p.high_degree = cfg.high_degree_pruning; }
@@ -634,14 +635,11 @@ isl_status Scaffold::table_to_csr(const Table& t, uint64_t n, bool kept, uint64_
   return ISL_OK;
 }
 
-void Scaffold::hand_rows_to(isl_index* r) {
-  r->d_emb = std::move(g->d_emb); r->d_emb16 = std::move(g->d_emb16); r->d_norm2 = std::move(g->d_norm2);
-  r->nvec = g->nvec; r->emb_d = g->emb_d; r->emb_stride = g->emb_stride;
-}
-
 isl_index* Scaffold::release() {
   isl_index* r = res;
-  for (void* q : keep) r->hnsw_owned.emplace_back().adopt(static_cast<unsigned char*>(q), 0);
+  r->rows = std::move(g->rows);
+  r->nvec = g->nvec;
+  for (auto& b : keep) r->hnsw_owned.push_back(std::move(b));
   keep.clear();
   res = nullptr;
   return r;
@@ -724,11 +722,11 @@ extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const
     g->has_entry = true;
     g->entry_point = entry;  // :669: entry_point.unwrap_or(0) as of the start of the step
     const dim3 ggrid((uint32_t)((s.count * d + 255) / 256));
-    if (g->d_emb16)  // the step's queries are the widened rows
-      hipLaunchKernelGGL(gather_rows_bf16_kernel, ggrid, dim3(256), 0, 0, g->d_emb16.get(), g->emb_stride, (uint32_t)d,
+    if (g->rows.is_bf16())  // the step's queries are the widened rows
+      hipLaunchKernelGGL(gather_rows_bf16_kernel, ggrid, dim3(256), 0, 0, g->rows.bf16(), g->rows.stride(), (uint32_t)d,
                          s.first, s.count, c.qbuf);
     else
-      hipLaunchKernelGGL(gather_rows_kernel, ggrid, dim3(256), 0, 0, g->d_emb.get(), g->emb_stride, (uint32_t)d,
+      hipLaunchKernelGGL(gather_rows_kernel, ggrid, dim3(256), 0, 0, g->rows.f32(), g->rows.stride(), (uint32_t)d,
                          s.first, s.count, c.qbuf);
     if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "gather launch failed");
     ISL_TRY(c.insert(t, s.count, s.count > 1, s.first));
@@ -743,7 +741,6 @@ extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const
   ISL_TRY(isl_index_from_device_csr(&cfg, device, n, d_off, d_adj, 1, entry, 1, d, &c.res));
   c.res->max_level = max_level;
   if (levels) c.res->levels.assign(levels, levels + n);
-  c.hand_rows_to(c.res);
   isl_index* built = c.release();
   // ISL_ENTRY_SEEDS=N: the finished index leaves with N entry seeds selected (as isl_index_select_entry_seeds)
   const isl_status seeded = isl::env_entry_seeds(built);
@@ -773,7 +770,7 @@ extern "C" isl_status isl_select_neighbors(const isl_index* idx, const isl_build
   if (cap == 0 || cap > isl_plan::kMaxM0) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: 1 <= cap <= 128");
   if (nb == 0) return ISL_OK;
   if (nb > 0x7FFFFFFFull) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: too many base nodes");
-  if (idx->recompute || idx->d_emb16 || !idx->d_emb || idx->device < 0)
+  if (idx->recompute || !idx->rows.f32() || idx->device < 0)
     return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors needs float32 rows resident on the device");
   uint32_t nmax = 1;
   for (uint64_t i = 0; i < nb; ++i) {
@@ -805,12 +802,13 @@ extern "C" isl_status isl_select_neighbors(const isl_index* idx, const isl_build
       hipMemcpy(d_cand, hcand.data(), (size_t)nb * nmax * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(d_cnt, cand_cnt, nb * 4, hipMemcpyHostToDevice) != hipSuccess)
     return fail(ISL_ERR_DEVICE, "cannot stage the candidates");
-  p.c = SelCtx{idx->d_emb, idx->d_norm2, idx->emb_stride, (uint32_t)idx->emb_d, opts.alpha, opts.keep_pruned ? 1u : 0u};
+  const isl::RowTable& rows = idx->rows;
+  p.c = SelCtx{rows.f32(), rows.norm2(), rows.stride(), (uint32_t)rows.d(), opts.alpha, opts.keep_pruned ? 1u : 0u};
   p.base_ids = d_base; p.cand = d_cand; p.cand_cnt = d_cnt;
   p.pitch = nmax; p.cap = (uint32_t)cap; p.nmax = nmax;
-  isl_build::by_metric(idx->cfg.metric, [&](auto mc) {
+  isl::by_metric(idx->cfg.metric, [&](auto mc) {
     hipLaunchKernelGGL(select_neighbors_kernel<decltype(mc)::value>, dim3((uint32_t)nb), dim3(64),
-                       sel_lds(false, idx->emb_d, nmax, (uint32_t)cap), 0, p);
+                       sel_lds(false, rows.d(), nmax, (uint32_t)cap), 0, p);
   });
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return fail(ISL_ERR_DEVICE, "select_neighbors kernel failed");

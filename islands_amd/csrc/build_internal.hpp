@@ -6,8 +6,6 @@
 #include "build_plan.hpp"
 #include "common.hpp"
 
-#include <type_traits>
-
 namespace isl_build {
 
 struct BuildParams {
@@ -49,18 +47,6 @@ size_t link_lds(uint64_t d);
 // ISL_DTYPE_F32 / ISL_DTYPE_BF16, before any device call
 isl_status check_row_dtype(int32_t dtype);
 
-// f(std::integral_constant<int, METRIC>{}) for the metric of a call: the one place a kernel template's
-// metric argument is chosen at run time
-template <class F>
-void by_metric(uint32_t metric, F&& f) {
-  switch (metric) {
-    case ISL_METRIC_COSINE: f(std::integral_constant<int, ISL_METRIC_COSINE>{}); break;
-    case ISL_METRIC_EUCLIDEAN: f(std::integral_constant<int, ISL_METRIC_EUCLIDEAN>{}); break;
-    case ISL_METRIC_DOT: f(std::integral_constant<int, ISL_METRIC_DOT>{}); break;
-    default: f(std::integral_constant<int, ISL_METRIC_MANHATTAN>{}); break;
-  }
-}
-
 // One table the nodes of a step are inserted on: the whole graph of LeannIndex::build, or one layer of an
 // HnswGraph under construction.
 struct Table {
@@ -76,8 +62,8 @@ struct Table {
 struct Scaffold {
   isl_index* g = nullptr;
   isl_index* res = nullptr;   // the finished index, once there is one
-  std::vector<void*> tmp;     // freed on every way out
-  std::vector<void*> keep;    // res->hnsw_owned after release(), freed before it
+  isl::TempScope tmp;         // freed on every way out
+  std::vector<isl::DeviceBuffer<unsigned char>> keep;  // res->hnsw_owned after release(), freed before it
   float* qbuf = nullptr;      // [B][d] queries of a step: the rows of its nodes
   uint64_t* cand_ids = nullptr;  // [B][ef] what the construction search found (p.cand_*)
   float* cand_dist = nullptr;
@@ -118,9 +104,7 @@ struct Scaffold {
                           uint32_t* d_flag);
   // fixed-width table -> CSR arrays on the device (one wave per row)
   isl_status table_to_csr(const Table& t, uint64_t n, bool kept, uint64_t** off, uint32_t** adj);
-  // the finished index takes over the rows (f32 or bf16, and their norms) of the construction graph
-  void hand_rows_to(isl_index* r);
-  // success: the finished graph leaves with what was kept for it
+  // success: the finished graph leaves with the construction graph's rows and what was kept for it
   isl_index* release();
 };
 

@@ -13,10 +13,12 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/islands_amd.h"
 #include "device_buffer.hpp"
+#include "row_table.hpp"
 
 namespace isl {
 
@@ -43,6 +45,18 @@ isl_status fail_node(uint64_t node);
     isl_status _s = (expr);      \
     if (_s != ISL_OK) return _s; \
   } while (0)
+
+// f(std::integral_constant<int, METRIC>{}) for the metric of a call: the one place a kernel template's
+// metric argument is chosen at run time
+template <class F>
+void by_metric(uint32_t metric, F&& f) {
+  switch (metric) {
+    case ISL_METRIC_COSINE: f(std::integral_constant<int, ISL_METRIC_COSINE>{}); break;
+    case ISL_METRIC_EUCLIDEAN: f(std::integral_constant<int, ISL_METRIC_EUCLIDEAN>{}); break;
+    case ISL_METRIC_DOT: f(std::integral_constant<int, ISL_METRIC_DOT>{}); break;
+    default: f(std::integral_constant<int, ISL_METRIC_MANHATTAN>{}); break;
+  }
+}
 
 // Selects `device` after checking that it exists and is a gfx950 part.
 isl_status use_device(int32_t device);
@@ -194,21 +208,14 @@ struct isl_index {
   // (ef << 32 | evaluations; 0 = none yet): the size of the visited table of later calls WITH THAT ef follows it
   // (search.hip, fast_geometry)
   mutable std::atomic<uint64_t> evals_hint{0};
-  // in-memory provider (leann.rs:104-159): nvec rows, `stride` floats apart
-  isl::DeviceBuffer<float> d_emb;
-  isl::DeviceBuffer<uint16_t> d_emb16;  // bf16 rows (ISL_DTYPE_BF16) instead of d_emb
-  isl::DeviceBuffer<float> d_norm2;  // [nvec] sum of squares of every row, reference summation order
-  uint64_t nvec = 0, emb_d = 0, emb_stride = 0;
+  // The embedding provider's rows.  In-memory provider (leann.rs:104-159): `rows` holds all nvec of them, f32 or
+  // bf16.  Recompute provider: nvec is still the provider's length (the node count), while `rows` is the bounded
+  // f32 slab indexed by SLOT -- rows.n() slots, the slab_rows of recompute_plan.hpp.
+  isl::RowTable rows;
+  uint64_t nvec = 0;
 
-  // entry seeds (entry_seeds.hip): seed_count node ids and a contiguous copy of their rows, of the type and at
-  // the stride of the provider's table, with their norms; seed_count == 0 = no table (the default).  Dropped by
-  // whatever replaces the rows they were copied from.
-  std::vector<uint64_t> seed_ids;
-  uint64_t seed_count = 0;
-  isl::DeviceBuffer<uint32_t> d_seed_ids;      // [seed_count]
-  isl::DeviceBuffer<float> d_seed_rows;        // [seed_count][emb_stride] (f32 rows)
-  isl::DeviceBuffer<uint16_t> d_seed_rows16;   // ... or bf16 rows
-  isl::DeviceBuffer<float> d_seed_norm2;       // [seed_count]
+  // entry seeds (entry_seeds.hip); empty by default
+  isl::EntrySeeds seeds;
 
   // graph under construction (build.hip): fixed-width adjacency rows, searched in place
   uint32_t* d_ell = nullptr;      // [num_nodes][ell_w]: the builder's rows (borrowed) or ell_copy
@@ -230,14 +237,13 @@ struct isl_index {
   isl::DeviceBuffer<uint16_t> d_tokens; // [nvec][tok_L]
   isl::DeviceBuffer<uint16_t> d_lens;   // [nvec] or NULL
   uint32_t tok_L = 0;
-  // the rows live in a bounded slab (d_emb / d_norm2 indexed by SLOT): slot_of[id] = the node's
+  // the rows live in a bounded slab (`rows`, indexed by SLOT): slot_of[id] = the node's
   // slot or 0xFFFFFFFF, owner[slot] = the node in it; slots are handed out round-robin, so the
   // oldest rows make room once the slab is full
   isl::DeviceBuffer<uint32_t> d_slot_of;    // [nvec]
-  isl::DeviceBuffer<uint32_t> d_owner;      // [slab_rows]
-  isl::DeviceBuffer<uint32_t> d_stamp;      // [slab_rows] round in which a row was last asked for
+  isl::DeviceBuffer<uint32_t> d_owner;      // [rows.n()]
+  isl::DeviceBuffer<uint32_t> d_stamp;      // [rows.n()] round in which a row was last asked for
   isl::DeviceBuffer<uint32_t> d_slab_head;  // [1] where the clock hand of the slot allocator stands
-  uint64_t slab_rows = 0;
   mutable uint32_t round_no = 1;       // rounds of recompute searches so far (under recompute_mu)
   bool recompute = false, keep_rows = false;
   int32_t enc_normalize = 1;
@@ -305,9 +311,7 @@ isl_status set_grown_embeddings(isl_index* idx, const isl_index* old, const floa
 // build_distance_tables (pq.rs:307-338) for nq device-resident queries into d_tables [nq][m][K]
 isl_status pq_launch_tables(const isl_pq* pq, const float* d_queries, uint64_t nq, float* d_tables,
                             hipStream_t st);
-// entry_seeds.hip -- forgets the entry-seed table (under idx->mu, no search in flight)
-void drop_entry_seeds(isl_index* idx);
-// ... the nearest seed of nq device-resident queries, enqueued on `st`: node ids into q_entry [nq] (with
+// entry_seeds.hip -- the nearest seed of nq device-resident queries, enqueued on `st`: node ids into q_entry [nq] (with
 // q_evals [nq] = 1 and status [nq] = QS_OK, what the traversal reads beside a given entry) and / or as u64 into
 // d_out_ids; `packed` [nq] is scratch.  Nothing is launched for an index without seeds or for nq == 0.
 isl_status launch_entry_pick(const isl_index* idx, const float* d_queries, uint64_t nq, uint32_t* q_entry,

@@ -224,20 +224,13 @@ __global__ __launch_bounds__(256) void seed_pick_finish_kernel(const unsigned lo
   if (out_ids) out_ids[q] = id;
 }
 
-// f(metric constant, row type tag) for the index's metric and row type; cosine takes the precomputed norms
+// f(metric constant, row type tag) for the index's metric and the type of `rows`; cosine takes the precomputed norms
 template <typename F>
-bool by_metric_rows(int32_t metric, bool bf16, F&& f) {
-  auto rows = [&](auto mc) {
-    if (bf16) f(mc, uint16_t{});
-    else f(mc, float{});
-  };
-  switch (metric) {
-    case ISL_METRIC_COSINE: rows(std::integral_constant<int, METRIC_COSINE_PRE>{}); return true;
-    case ISL_METRIC_EUCLIDEAN: rows(std::integral_constant<int, ISL_METRIC_EUCLIDEAN>{}); return true;
-    case ISL_METRIC_DOT: rows(std::integral_constant<int, ISL_METRIC_DOT>{}); return true;
-    case ISL_METRIC_MANHATTAN: rows(std::integral_constant<int, ISL_METRIC_MANHATTAN>{}); return true;
-    default: return false;
-  }
+void by_metric_rows(uint32_t metric, const isl::RowTable& rows, F&& f) {
+  isl::by_metric(metric, [&](auto mc) {
+    constexpr int m = decltype(mc)::value == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : decltype(mc)::value;
+    rows.with_row_type([&](auto row) { f(std::integral_constant<int, m>{}, row); });
+  });
 }
 
 constexpr uint32_t kMaxSelectDim = 32768;  // the seed's row waits in LDS as f32: 128 KiB of the CU's 160
@@ -246,35 +239,32 @@ constexpr uint32_t kMaxSelectDim = 32768;  // the seed's row waits in LDS as f32
 isl_status check_seedable(const isl_index* idx, const char* who) {
   if (idx->is_hnsw) return fail(ISL_ERR_UNSUPPORTED, "%s: entry seeds belong to a LeannIndex, not to the HnswGraph facade", who);
   if (idx->num_nodes == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "%s: the index is empty", who);
-  if (idx->recompute || (!idx->d_emb && !idx->d_emb16) || idx->device < 0)
+  if (idx->recompute || !idx->rows.resident() || idx->device < 0)
     return fail(ISL_ERR_UNSUPPORTED, "%s needs rows resident on the device", who);
   return ISL_OK;
 }
 
-// ids -> the table (under idx->mu, no search in flight, ids checked)
+// ids -> the table (under idx->mu, no search in flight, ids checked): a table is either whole or absent
 isl_status install_seeds(isl_index* idx, const std::vector<uint64_t>& ids) {
-  isl::drop_entry_seeds(idx);
+  idx->seeds = {};
   const uint64_t E = ids.size();
   if (!E) return ISL_OK;
   std::vector<uint32_t> h32(E);
   for (uint64_t i = 0; i < E; ++i) h32[i] = (uint32_t)ids[i];
-  const uint64_t stride = idx->emb_stride;
-  ISL_TRY(idx->d_seed_ids.reserve(E));
-  ISL_TRY(idx->d_seed_norm2.reserve(E));
-  ISL_HIP(hipMemcpy(idx->d_seed_ids, h32.data(), E * 4, hipMemcpyHostToDevice));
-  if (idx->d_emb16) {
-    ISL_TRY(idx->d_seed_rows16.reserve(E * stride));
-    hipLaunchKernelGGL(gather_seed_rows_kernel<uint16_t>, dim3((uint32_t)E), dim3(256), 0, 0, idx->d_emb16.get(), stride,
-                       idx->d_norm2.get(), idx->d_seed_ids.get(), idx->d_seed_rows16.get(), idx->d_seed_norm2.get());
-  } else {
-    ISL_TRY(idx->d_seed_rows.reserve(E * stride));
-    hipLaunchKernelGGL(gather_seed_rows_kernel<float>, dim3((uint32_t)E), dim3(256), 0, 0, idx->d_emb.get(), stride,
-                       idx->d_norm2.get(), idx->d_seed_ids.get(), idx->d_seed_rows.get(), idx->d_seed_norm2.get());
-  }
+  const isl::RowTable& from = idx->rows;
+  isl::EntrySeeds s;
+  ISL_TRY(s.d_ids.reserve(E));
+  ISL_TRY(s.rows.allocate(from.dtype(), E, from.d()));
+  ISL_HIP(hipMemcpy(s.d_ids, h32.data(), E * 4, hipMemcpyHostToDevice));
+  from.with_row_type([&](auto row) {
+    using T = decltype(row);
+    hipLaunchKernelGGL(gather_seed_rows_kernel<T>, dim3((uint32_t)E), dim3(256), 0, 0, from.as<const T>(), from.stride(),
+                       from.norm2(), s.d_ids.get(), s.rows.as<T>(), s.rows.norm2());
+  });
   ISL_HIP(hipGetLastError());
   ISL_HIP(hipDeviceSynchronize());
-  idx->seed_ids = ids;
-  idx->seed_count = E;  // last: a table is either whole or absent
+  s.ids = ids;
+  idx->seeds = std::move(s);
   return ISL_OK;
 }
 
@@ -287,7 +277,7 @@ isl_status select_seeds(isl_index* idx, uint64_t count, std::vector<uint64_t>& i
   if (!E) return ISL_OK;
   const uint64_t entry = idx->has_entry ? idx->entry_point : 0;
   if (entry >= n) return isl::fail_node(entry);
-  if (idx->emb_d > kMaxSelectDim)
+  if (idx->rows.d() > kMaxSelectDim)
     return fail(ISL_ERR_UNSUPPORTED, "entry-seed selection takes rows of up to %u elements", kMaxSelectDim);
   isl::DeviceBuffer<uint32_t> mind;
   isl::DeviceBuffer<unsigned long long> best;
@@ -297,17 +287,16 @@ isl_status select_seeds(isl_index* idx, uint64_t count, std::vector<uint64_t>& i
   ISL_HIP(hipMemset(best, 0, E * 8));
   ISL_HIP(hipMemcpy(best, &first, 8, hipMemcpyHostToDevice));
   SelectParams p{};
-  const bool bf16 = (bool)idx->d_emb16;
-  p.emb = bf16 ? (const void*)idx->d_emb16.get() : (const void*)idx->d_emb.get();
-  p.norm2 = idx->d_norm2;
-  p.stride = idx->emb_stride;
+  p.emb = idx->rows.data();
+  p.norm2 = idx->rows.norm2();
+  p.stride = idx->rows.stride();
   p.n = n;
-  p.d = (uint32_t)idx->emb_d;
+  p.d = (uint32_t)idx->rows.d();
   p.mind = mind;
   p.best = best;
   const size_t lds = (size_t)((p.d + 31u) & ~31u) * 4;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 63) / 64, 8192);
-  const bool known = by_metric_rows((int32_t)idx->cfg.metric, bf16, [&](auto mc, auto row) {
+  by_metric_rows(idx->cfg.metric, idx->rows, [&](auto mc, auto row) {
     auto k = seed_select_pass_kernel<decltype(mc)::value, decltype(row)>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     for (uint64_t pass = 0; pass + 1 < E; ++pass) {
@@ -315,7 +304,6 @@ isl_status select_seeds(isl_index* idx, uint64_t count, std::vector<uint64_t>& i
       hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, 0, p);
     }
   });
-  if (!known) return fail(ISL_ERR_INVALID_ARGUMENT, "unknown metric %d", (int)idx->cfg.metric);
   ISL_HIP(hipGetLastError());
   ISL_HIP(hipDeviceSynchronize());
   std::vector<unsigned long long> h(E);
@@ -332,40 +320,30 @@ isl_status select_seeds(isl_index* idx, uint64_t count, std::vector<uint64_t>& i
 
 namespace isl {
 
-void drop_entry_seeds(isl_index* idx) {
-  idx->seed_count = 0;
-  idx->seed_ids.clear();
-  idx->d_seed_ids.reset();
-  idx->d_seed_rows.reset();
-  idx->d_seed_rows16.reset();
-  idx->d_seed_norm2.reset();
-}
-
 isl_status launch_entry_pick(const isl_index* idx, const float* d_queries, uint64_t nq, uint32_t* q_entry,
                              uint32_t* q_evals, unsigned long long* packed, uint32_t* status, uint64_t* d_out_ids,
                              hipStream_t st) {
-  if (!nq || !idx->seed_count) return ISL_OK;
+  const isl::RowTable& rows = idx->seeds.rows;
+  if (!nq || !rows.n()) return ISL_OK;
   PickParams p{};
-  const bool bf16 = (bool)idx->d_seed_rows16;
   p.queries = d_queries;
-  p.rows = bf16 ? (const void*)idx->d_seed_rows16.get() : (const void*)idx->d_seed_rows.get();
-  p.norm2 = idx->d_seed_norm2;
-  p.stride = idx->emb_stride;
+  p.rows = rows.data();
+  p.norm2 = rows.norm2();
+  p.stride = rows.stride();
   p.nq = (uint32_t)nq;
-  p.d = (uint32_t)idx->emb_d;
-  p.seeds = (uint32_t)idx->seed_count;
+  p.d = (uint32_t)rows.d();
+  p.seeds = (uint32_t)rows.n();
   p.packed = packed;
-  const isl_seeds::PickGrid g = isl_seeds::pick_grid(nq, idx->seed_count, (uint32_t)device_cu_count(idx->device));
+  const isl_seeds::PickGrid g = isl_seeds::pick_grid(nq, rows.n(), (uint32_t)device_cu_count(idx->device));
   p.tiles_per_split = g.tiles_per_split;
   ISL_HIP(hipMemsetAsync(packed, 0xFF, nq * 8, st));
-  const bool known = by_metric_rows((int32_t)idx->cfg.metric, bf16, [&](auto mc, auto row) {
+  by_metric_rows(idx->cfg.metric, rows, [&](auto mc, auto row) {
     hipLaunchKernelGGL((seed_pick_kernel<decltype(mc)::value, decltype(row)>), dim3(g.qtiles, g.splits), dim3(256), 0, st,
                        p);
   });
-  if (!known) return fail(ISL_ERR_INVALID_ARGUMENT, "unknown metric %d", (int)idx->cfg.metric);
   ISL_HIP(hipGetLastError());
   hipLaunchKernelGGL(seed_pick_finish_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, st, packed,
-                     idx->d_seed_ids.get(), p.seeds, p.nq, q_entry, q_evals, status, d_out_ids);
+                     idx->seeds.d_ids.get(), p.seeds, p.nq, q_entry, q_evals, status, d_out_ids);
   ISL_HIP(hipGetLastError());
   return ISL_OK;
 }
@@ -428,9 +406,9 @@ isl_status isl_index_entry_seeds(const isl_index* idx, uint64_t* out, uint64_t c
   if (!idx) return fail(ISL_ERR_INVALID_ARGUMENT, "index is NULL");
   if (cap && !out) return fail(ISL_ERR_INVALID_ARGUMENT, "out is NULL");
   std::lock_guard<std::mutex> lock(idx->mu);
-  const uint64_t E = idx->seed_count;
+  const uint64_t E = idx->seeds.count();
   if (count) *count = E;
-  std::copy(idx->seed_ids.begin(), idx->seed_ids.begin() + std::min(cap, E), out);
+  std::copy(idx->seeds.ids.begin(), idx->seeds.ids.begin() + std::min(cap, E), out);
   return ISL_OK;
 }
 
@@ -441,8 +419,8 @@ isl_status isl_index_pick_entries(const isl_index* idx, const float* queries, ui
   if (mem != ISL_MEM_HOST && mem != ISL_MEM_DEVICE) return fail(ISL_ERR_INVALID_ARGUMENT, "unknown memory space");
   if (nq > 0x7FFFFFFFull) return fail(ISL_ERR_INVALID_ARGUMENT, "too many queries");
   ISL_TRY(check_seedable(idx, "isl_index_pick_entries"));
-  if (!idx->seed_count) return fail(ISL_ERR_INVALID_ARGUMENT, "isl_index_pick_entries: the index has no entry seeds");
-  if (d != idx->emb_d) return isl::fail_dim(idx->emb_d, d);
+  if (!idx->seeds.count()) return fail(ISL_ERR_INVALID_ARGUMENT, "isl_index_pick_entries: the index has no entry seeds");
+  if (d != idx->rows.d()) return isl::fail_dim(idx->rows.d(), d);
   if (!nq) return ISL_OK;
   ISL_TRY(isl::use_device(idx->device));
   hipStream_t st = (hipStream_t)stream;

@@ -58,10 +58,10 @@ uint64_t level_of(const isl_index* c, uint64_t i) { return i < c->levels.size() 
 
 // node rows [i0, i0 + cnt) of the handle's f32 provider -> host
 isl_status read_rows(const isl_index* c, uint64_t i0, uint64_t cnt, float* out) {
-  if (!cnt || !c->emb_d) return ISL_OK;
-  if (!c->d_emb) return isl::fail(ISL_ERR_EMBEDDING, "Embedding error: no embedding provider attached");
+  if (!cnt || !c->rows.d()) return ISL_OK;
+  if (!c->rows.f32()) return isl::fail(ISL_ERR_EMBEDDING, "Embedding error: no embedding provider attached");
   ISL_TRY(isl::use_device(c->device));
-  ISL_HIP(hipMemcpy2D(out, c->emb_d * 4, c->d_emb + i0 * c->emb_stride, c->emb_stride * 4, c->emb_d * 4, cnt,
+  ISL_HIP(hipMemcpy2D(out, c->rows.d() * 4, c->rows.f32() + i0 * c->rows.stride(), c->rows.stride() * 4, c->rows.d() * 4, cnt,
                       hipMemcpyDeviceToHost));
   return ISL_OK;
 }
@@ -325,7 +325,7 @@ isl_status isl_hnsw_get_vector(const isl_hnsw* h, uint64_t node, float* out) {
 isl_status isl_hnsw_to_bytes(const isl_hnsw* h, uint8_t** out, size_t* len) {
   if (!h || !h->core || !out || !len) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   const isl_index* c = h->core;
-  const uint64_t n = c->num_nodes, d = n ? c->emb_d : 0;
+  const uint64_t n = c->num_nodes, d = n ? c->rows.d() : 0;
   try {
     std::lock_guard<std::mutex> lock(h->host_mu);
     ISL_TRY(ensure_host_layers(h));

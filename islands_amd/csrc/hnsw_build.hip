@@ -248,7 +248,7 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
     return fail(ISL_ERR_DEVICE, "cannot stage the build plan");
 
   DescentParams dp{};
-  dp.emb = g->d_emb; dp.norm2 = g->d_norm2; dp.stride = g->emb_stride; dp.d = (uint32_t)d;
+  dp.emb = g->rows.f32(); dp.norm2 = g->rows.norm2(); dp.stride = g->rows.stride(); dp.d = (uint32_t)d;
   dp.tab = d_tab; dp.deg = d_deg; dp.W = m + 1; dp.levels = d_lv;
   dp.cur_of = cur_of; dp.evals_of = evals_of;
   c.p.node_levels = d_lv;
@@ -260,7 +260,7 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
   for (const isl_plan::Step& s : steps) {
     const uint32_t* ids = d_order + s.first;
     dp.node_ids = ids; dp.B = s.count; dp.entry = (uint32_t)entry; dp.max_level = (uint32_t)max_level;
-    isl_build::by_metric(cfg.metric, [&](auto mc) {
+    isl::by_metric(cfg.metric, [&](auto mc) {
       hipLaunchKernelGGL(insert_descent_kernel<decltype(mc)::value>, dim3(s.count), dim3(64), isl_build::link_lds(d), 0, dp);
     });
     if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "descent launch failed");
@@ -270,7 +270,7 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
     for (uint64_t L = s.top + 1; L-- > 0;) {
       while (cnt < s.count && lv[order[s.first + cnt]] >= L) ++cnt;
       hipLaunchKernelGGL(gather_layer_kernel, dim3((uint32_t)(((uint64_t)cnt * d + 255) / 256)), dim3(256), 0, 0,
-                         g->d_emb, g->emb_stride, (uint32_t)d, ids, cnt, cur_of, evals_of, c.qbuf, g->build_q_entry,
+                         g->rows.f32(), g->rows.stride(), (uint32_t)d, ids, cnt, cur_of, evals_of, c.qbuf, g->build_q_entry,
                          g->build_q_evals);
       if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "gather launch failed");
       ISL_TRY(c.insert(tab[L], cnt, s.count > 1, 0, ids, (uint32_t)L));
@@ -302,7 +302,6 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
   h->ml = cfg.ml; h->max_layers = cfg.max_layers;
   h->device = device;
   ISL_TRY(isl::attach_upper_layers(h.get(), offs, adjs));
-  c.hand_rows_to(c.res);
   c.release();
   out = std::move(h);
   return ISL_OK;
@@ -374,7 +373,7 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const 
   uint64_t top = 0;
   ISL_TRY(all_levels(n0 ? core : nullptr, cfg, n0 + n_new, levels_in, level_seed, levels, top));
   if (n0) {
-    if (core->recompute || core->d_emb16 || !core->d_emb || !core->d_norm2 || core->nvec != n0 || core->emb_d != d ||
+    if (core->recompute || !core->rows.f32() || !core->rows.norm2() || core->nvec != n0 || core->rows.d() != d ||
         core->device < 0)
       return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert needs the graph's float32 rows resident on the device");
     if (!core->has_entry) return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the graph has nodes and no entry point");

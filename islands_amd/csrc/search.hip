@@ -282,7 +282,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   const bool resume = !warm && (plan.active != 0 || plan.exact != 0);
   // two-level search over bf16 rows: first the instantiation that keeps a bf16-valued query as bf16
   // in LDS, then the float32-query one over the queries it passed on (not in a retry's list mode)
-  const bool tl_qh = tl && !warm && !resume && idx->d_emb16 && plan.retry == 0 && cg.tl_hbits_q == cg.fg.hbits;
+  const bool tl_qh = tl && !warm && !resume && idx->rows.is_bf16() && plan.retry == 0 && cg.tl_hbits_q == cg.fg.hbits;
   const bool qh = cg.qh && !resume;  // (the fast kernel's bf16-query instantiation in front)
   // per-slot state is indexed by blockIdx.x < min(nq, slots) -- by the query when it can come back on
   // another wave
@@ -309,11 +309,11 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.ell_w = idx->d_ell ? idx->ell_w : 0u;
   p.ell_deg = idx->d_ell_deg;
   p.num_nodes = idx->num_nodes;
-  p.emb = idx->d_emb16 ? (const void*)idx->d_emb16 : (const void*)idx->d_emb;
-  p.emb_bf16 = idx->d_emb16 ? 1u : 0u;
-  p.norm2 = idx->d_norm2;
+  p.emb = idx->rows.data();
+  p.emb_bf16 = idx->rows.is_bf16() ? 1u : 0u;
+  p.norm2 = idx->rows.norm2();
   p.nvec = idx->nvec;
-  p.stride = idx->emb_stride;
+  p.stride = idx->rows.stride();
   p.d = (uint32_t)d;
   p.queries = c.queries;
   p.nq = warm ? 0u : (uint32_t)nq;
@@ -399,7 +399,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   }
   // entry seeds: a plain search over resident rows starts every query at the seed nearest to it (the pick is
   // launched below, ahead of the traversal); two-level searches and the recompute provider keep entry_point
-  const bool seeded = idx->seed_count != 0 && !tl && !idx->recompute && !idx->is_hnsw && !idx->build_q_entry &&
+  const bool seeded = idx->seeds.count() != 0 && !tl && !idx->recompute && !idx->is_hnsw && !idx->build_q_entry &&
                       !warm && !resume && nq != 0;
   if (seeded) {
     ISL_TRY(ws.q_entry.reserve(nq * 4, &ws.alloc_events));
@@ -727,10 +727,10 @@ isl_status precheck(const isl_index* idx, uint64_t nq, uint64_t d, uint64_t k, u
   if (!idx->has_entry) return isl::fail(ISL_ERR_INDEX_NOT_BUILT, "Index not built");  // :889
   if (idx->device < 0 || !idx->d_off)
     return isl::fail(ISL_ERR_DEVICE, "index is not resident on a device (isl_index_upload)");
-  if (!idx->d_emb && !idx->d_emb16)
+  if (!idx->rows.resident())
     return isl::fail(ISL_ERR_EMBEDDING, "Embedding error: no embedding provider attached");
-  if (d != idx->emb_d)  // metric.calculate length check, distance.rs:39-44
-    return isl::fail_dim(d, idx->emb_d);
+  if (d != idx->rows.d())  // metric.calculate length check, distance.rs:39-44
+    return isl::fail_dim(d, idx->rows.d());
   if (k == 0) {
     *done = 2;  // nothing to write but counts
   }
@@ -991,7 +991,7 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
   if (!idx) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "index is NULL");
   if (idx->device < 0 || !idx->d_off)
     return isl::fail(ISL_ERR_DEVICE, "index is not resident on a device (isl_index_upload)");
-  if (!idx->d_emb && !idx->d_emb16)
+  if (!idx->rows.resident())
     return isl::fail(ISL_ERR_EMBEDDING, "Embedding error: no embedding provider attached");
   if (lanes < 1 || lanes > isl::kSearchLanes)
     return isl::fail(ISL_ERR_INVALID_ARGUMENT, "lanes must be 1..%d", isl::kSearchLanes);
@@ -1001,7 +1001,7 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
     return isl::fail(ISL_ERR_UNSUPPORTED, "ef = %llu exceeds the device limit %u", (unsigned long long)max_ef,
                      kMaxExactEf);
   ISL_TRY(isl::use_device(idx->device));
-  const uint64_t d = idx->emb_d;
+  const uint64_t d = idx->rows.d();
   {
     std::lock_guard<std::mutex> lock(idx->mu);
     if (isl::any_lane_busy(idx))
@@ -1025,7 +1025,7 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
     ISL_TRY(prepare_host_staging(ws, max_nq, d, std::max<uint64_t>(max_k, 1)));
     if (idx->recompute) ISL_TRY(prepare_recompute(ws, max_nq, cg_max.state_words));
     if (idx->is_hnsw) ISL_TRY(ws.q_entry.reserve(max_nq * 2, &ws.alloc_events));
-    else if (idx->seed_count) ISL_TRY(ws.q_entry.reserve(max_nq * 4, &ws.alloc_events));  // entry, evals, packed minima
+    else if (idx->seeds.count()) ISL_TRY(ws.q_entry.reserve(max_nq * 4, &ws.alloc_events));  // entry, evals, packed minima
     if (idx->pq && idx->d_codes && !idx->is_hnsw && d == idx->pq->dimension)
       ISL_TRY(ws.tl_tables.reserve(max_nq * idx->pq->m * idx->pq->K, &ws.alloc_events));
     memset(ws.h_q, 0, max_nq * d * 4);

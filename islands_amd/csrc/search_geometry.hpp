@@ -151,7 +151,7 @@ inline isl_status call_geometry(const isl_index* idx, uint64_t d, uint64_t k, ui
   g.slots = resident_waves(ncu, g.fg.lds);
   // bf16 rows: first the kernel that keeps the query as bf16 in LDS (half the LDS per wave, more
   // waves per CU), then the float32-query kernel over the queries that one passed on
-  g.qh = g.use_fast && idx->d_emb16 && idx->max_degree <= 64;
+  g.qh = g.use_fast && idx->rows.is_bf16() && idx->max_degree <= 64;
   g.fgq = g.qh ? fast_geometry(ef, (uint32_t)d, 2, g.vhint, fixed_table) : g.fg;
   if (tl) {
     // Window of the approximate queue: ceil(a * |AQ|) must stay inside it.  |AQ| is bounded by the

@@ -175,8 +175,8 @@ namespace {
 isl_status begin_batch(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c, hipStream_t st) {
   if (!idx->keep_rows) {  // every call starts from an empty cache: each node is encoded once per call
     ISL_HIP(hipMemsetAsync(idx->d_slot_of, 0xFF, (idx->nvec + 1) * 4, st));
-    ISL_HIP(hipMemsetAsync(idx->d_owner, 0xFF, idx->slab_rows * 4, st));
-    ISL_HIP(hipMemsetAsync(idx->d_stamp, 0, idx->slab_rows * 4, st));
+    ISL_HIP(hipMemsetAsync(idx->d_owner, 0xFF, idx->rows.n() * 4, st));
+    ISL_HIP(hipMemsetAsync(idx->d_stamp, 0, idx->rows.n() * 4, st));
     ISL_HIP(hipMemsetAsync(idx->d_slab_head, 0, 8, st));
   }
   ISL_HIP(hipMemsetAsync(ws.qflag, 0, c.nq * 4, st));
@@ -217,7 +217,7 @@ EncodePolicy encode_policy(const isl_index* idx, bool tl, uint32_t in_flight) {
   // are encoded in the same round -- fewer, fuller rounds.  Only with a slab that has room to spare (the names are
   // guesses: under a small cache they would push out rows that hops are waiting for).  ISL_TL_PREFETCH=n overrides
   // (0 = off; read per call).
-  e.prefetch = (tl && idx->slab_rows >= (uint64_t)1024 * std::max<uint32_t>(1u, in_flight)) ? kTlPrefetchDefault : 0u;
+  e.prefetch = (tl && idx->rows.n() >= (uint64_t)1024 * std::max<uint32_t>(1u, in_flight)) ? kTlPrefetchDefault : 0u;
   if (const char* pe = getenv("ISL_TL_PREFETCH")) e.prefetch = tl ? (uint32_t)std::min(8, std::max(0, atoi(pe))) : 0u;
   return e;
 }
@@ -237,7 +237,7 @@ isl_status place_misses(const isl_index* idx, isl::SearchWorkspace& ws, hipStrea
                        idx->d_slot_of, ws.uniq, ws.uniq_count);
   // slots for the new rows (clock hand over the slab; rows asked for in this round stay)
   hipLaunchKernelGGL(assign_slots_kernel, dim3(1), dim3(64), 0, st, ws.uniq, ws.uniq_count, idx->round_no,
-                     (uint32_t)idx->slab_rows, idx->d_slab_head, idx->d_slot_of, idx->d_owner, idx->d_stamp,
+                     (uint32_t)idx->rows.n(), idx->d_slab_head, idx->d_slot_of, idx->d_owner, idx->d_stamp,
                      ws.uslots, ws.ticket + 15, enc.quantum, enc.chunk);
   ISL_HIP(hipGetLastError());
   copy_words(ws.ticket + 15, h_taken, 1, 1, 64, st);
@@ -249,11 +249,11 @@ isl_status place_misses(const isl_index* idx, isl::SearchWorkspace& ws, hipStrea
 // The placed rows: encoded into their slots, and their norms.
 isl_status encode_rows(const isl_index* idx, isl::SearchWorkspace& ws, hipStream_t st, uint32_t take) {
   ISL_TRY(isl::encoder_embed_nodes(idx->enc, idx->d_tokens, idx->d_lens, idx->tok_L, ws.uniq, take,
-                                   idx->enc_normalize, idx->d_emb, idx->emb_stride, st, ws.uslots));
+                                   idx->enc_normalize, idx->rows.f32(), idx->rows.stride(), st, ws.uslots));
   const size_t lds = (size_t)TILE_ROWS * TILE_LD * 4 + 64;
   if (take)
     hipLaunchKernelGGL(row_norm2_list_kernel, dim3(std::min<uint32_t>((take + 63) / 64, 4096)), dim3(64), lds, st,
-                       idx->d_emb, idx->emb_stride, (uint32_t)idx->emb_d, ws.uslots, take, idx->d_norm2);
+                       idx->rows.f32(), idx->rows.stride(), (uint32_t)idx->rows.d(), ws.uslots, take, idx->rows.norm2());
   ISL_HIP(hipGetLastError());
   return ISL_OK;
 }
@@ -277,13 +277,13 @@ isl_status recompute_rounds(const isl_index* idx, isl::SearchWorkspace& ws, cons
     const TwoLevelCall tl0{c.ratio};
     ISL_TRY(call_geometry(idx, c.d, c.k, c.ef, tl ? &tl0 : nullptr, cg0));
   }
-  const bool x_park = !tl && idx->slab_rows < idx->nvec;
+  const bool x_park = !tl && idx->rows.n() < idx->nvec;
   const isl_rounds::Kind kind = isl_rounds::batch_kind(tl, cg0.use_fast, x_park);
   ISL_TRY(prepare_recompute(ws, nq, kind == isl_rounds::Kind::PARK ? cg0.state_words : 1));  // (the heap-exact kernel parks in the pool)
   ISL_TRY(ensure_lane_stream(idx, ws));
   hipStream_t st = call_stream(ws, c);
   ISL_TRY(begin_batch(idx, ws, c, st));
-  const uint32_t in_flight = isl_rounds::max_in_flight(nq, idx->slab_rows, idx->nvec, tl, idx->max_degree);
+  const uint32_t in_flight = isl_rounds::max_in_flight(nq, idx->rows.n(), idx->nvec, tl, idx->max_degree);
   isl_rounds::RoundScheduler sched(kind, tl, (uint32_t)nq, in_flight, ws.h_qlist.get(), ws.h_xlist.get());
   sched.first();
   if (sched.listed() && sched.active()) copy_words(ws.h_qlist, ws.qlist, sched.active(), 16, 256, st);
@@ -331,7 +331,7 @@ isl_status recompute_rounds(const isl_index* idx, isl::SearchWorkspace& ws, cons
     if (rounds > max_rounds)
       return isl::fail(ISL_ERR_SEARCH, "Search error: %llu recompute rounds without completing the batch (row cache "
                        "%llu rows, %u queries in flight at a time)", (unsigned long long)rounds,
-                       (unsigned long long)idx->slab_rows, in_flight);
+                       (unsigned long long)idx->rows.n(), in_flight);
     if (!misses) continue;  // only fresh queries to start
     // place the misses, encode them, take their norms
     uint32_t take = 0;
@@ -339,7 +339,7 @@ isl_status recompute_rounds(const isl_index* idx, isl::SearchWorkspace& ws, cons
     // no row could be placed although rows are missing: every slot is held by a hop of this round
     if (take == 0 && ++stalled >= isl_rounds::stall_limit(kind))
       return isl::fail(ISL_ERR_SEARCH, "Search error: the recompute provider's row cache (%llu rows) is too small "
-                       "for this batch (no missing row could be placed)", (unsigned long long)idx->slab_rows);
+                       "for this batch (no missing row could be placed)", (unsigned long long)idx->rows.n());
     if (take) stalled = 0;
     ISL_TRY(encode_rows(idx, ws, st, take));
     encoded += take;

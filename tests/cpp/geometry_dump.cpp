@@ -30,7 +30,6 @@ int main() {
   isl_index* idx = new isl_index();
   idx->device = -1;
   idx->ncodes = 1000000;
-  uint16_t bf16_rows = 0;  // never read: only whether the index holds bf16 rows matters
   // plain, bf16 rows with a recorded evaluation count, recompute provider, two-level, two-level
   // retry (window_scale 4) over the recompute provider
   struct Variant { const char* name; int tl; bool bf16, recompute; };
@@ -41,8 +40,7 @@ int main() {
       for (uint32_t d : {100u, 768u, 4096u})
         for (const Variant& v : variants) {
           idx->max_degree = deg;
-          (void)idx->d_emb16.release();  // (not a device block: it must never reach the buffer's free)
-          if (v.bf16) idx->d_emb16.adopt(&bf16_rows, 1);
+          idx->rows.set_dtype(v.bf16 ? ISL_DTYPE_BF16 : ISL_DTYPE_F32);  // only the type matters: no block
           idx->recompute = v.recompute;
           idx->evals_hint.store(v.bf16 ? ((uint64_t)ef << 32) | 3100u : 0u);
           TwoLevelCall t{0.5f, v.tl == 2 ? 4u : 1u};
@@ -56,6 +54,5 @@ int main() {
           printf(" | %d %d %u %zu %u %u | %u %u %zu %zu\n", cg.segments, (int)cg.qh, cg.fgq.hbits, cg.fgq.lds,
                  cg.fgq.hcap, cg.slots_q, cg.state_words, cg.lane_slots, cg.exact_lds, cg.descent_lds);
         }
-  (void)idx->d_emb16.release();  // whatever the last variant was, no host address stays in an owning member
   return 0;
 }

@@ -44,6 +44,10 @@ def main():
     if not objs:
         sys.exit(__doc__)
     for obj in objs:
+        sections = subprocess.run(["objdump", "-h", obj], capture_output=True, text=True, check=True).stdout
+        if ".hip_fatbin" not in sections:  # a host-only unit
+            print(f"# {os.path.basename(obj)}: no device code")
+            continue
         with tempfile.TemporaryDirectory() as td:
             subprocess.check_call(["objcopy", "--dump-section", f".hip_fatbin={td}/fat.bin", obj])
             subprocess.check_call([LLVM + "clang-offload-bundler", "--unbundle", "--type=o", f"--input={td}/fat.bin",
