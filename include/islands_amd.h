@@ -168,6 +168,43 @@ isl_status isl_index_build_ex(const isl_leann_config* cfg, const isl_build_optio
 isl_status isl_index_build_rows(const isl_leann_config* cfg, const isl_build_options* opts, const void* rows,
                                 int32_t dtype, uint64_t n, uint64_t d, const uint64_t* levels, int32_t mem,
                                 int32_t device, isl_index** out);
+/* More rows into a built index, in place: nodes len .. len + n_new - 1 enter `idx` in id order under the config
+ * the handle carries.  rows = n_new x d elements of `dtype`, host or device (mem); opts = the rule and batch of
+ * this call as for isl_index_build_rows (NULL: the defaults); levels[i] stands for random_level() of node
+ * len + i (NULL: 0), taken as isl_index_build_rows takes them; *first_id (may be NULL) receives the old len,
+ * written only on ISL_OK.
+ * Definition: the graph afterwards is the state of LeannIndex::build's loop (leann.rs:578-615) continued at
+ * iteration id = len from adjacency = the index's lists in their stored order and entry_point / max_level =
+ * the index's.  With opts->batch == 1, on an index built here with batch 1, the result is therefore the
+ * isl_index_to_bytes image of isl_index_build_rows over all len + n_new rows with the concatenated levels, under
+ * either rule.  batch > 1 is the builder's throughput mode entered at node len: same rules, no parity claim.
+ * Rows: the index must hold resident in-memory rows (isl_set_embeddings or a build), and dtype must be their
+ * stored type -- nothing is converted.  bf16: the construction runs over the widened rows and the grown index
+ * keeps bf16 rows.  An index from isl_index_from_csr / _load / _from_bytes + isl_index_upload + isl_set_embeddings
+ * grows like a built one.  An empty handle takes the rows as isl_index_build_rows would with the handle's config,
+ * on the device it was uploaded to, else on device 0 (ISL_ENTRY_SEEDS is read by builds only).
+ * Strong guarantee: the grown graph is built beside the old one and moved into the handle at the end; on any
+ * failure idx is unchanged (bytes, rows, search answers) and the old rows are never modified.  Peak device
+ * memory: the old index whole, plus what isl_index_build_rows over len + n_new rows holds at its peak (the rows
+ * of all nodes, the (m0 + 1)-wide construction table, the CSR twice at compaction, the padded adjacency).
+ * What the handle keeps: its config, the visited-table hint, its prepared lanes (none of their buffers follows
+ * the node count) and its entry seeds AS THEY ARE -- ids and row copies of nodes the graph still has, so a
+ * plain search is still the reference search entered at the nearest seed; they are not re-selected.  What goes:
+ * the heap-exact kernel's pool (made again on demand) and the PQ codes, which no longer cover every node -- a
+ * two-level search afterwards answers as for an index that never had codes until isl_index_set_pq_codes is
+ * called again.
+ * The call is the reference's &mut self: not beside searches on the same handle (a busy lane ->
+ * ISL_ERR_SEARCH).  Checked in this order before any device call: NULL idx, or NULL rows with n_new > 0 ->
+ * ISL_ERR_INVALID_ARGUMENT; opts as in isl_index_build_ex; an unknown dtype -> ISL_ERR_INVALID_ARGUMENT;
+ * n_new == 0 -> ISL_OK, nothing changed; the core index of an HnswGraph (use isl_hnsw_insert) or an index on the
+ * recompute provider -> ISL_ERR_UNSUPPORTED; a non-empty index and d != its dimension ->
+ * ISL_ERR_DIMENSION_MISMATCH (expected, actual); d == 0 -> ISL_ERR_EMPTY_COLLECTION; a non-empty index without
+ * resident rows -> ISL_ERR_UNSUPPORTED; dtype != the stored type -> ISL_ERR_UNSUPPORTED; m0 > 128,
+ * ef_construction > 512 or too many nodes -> ISL_ERR_UNSUPPORTED.  Refused once the import kernel has looked,
+ * each with ISL_ERR_UNSUPPORTED and a message that says which: a list longer than m0; a device copy that is not
+ * the lists verbatim (ids repeated inside a list were removed at upload); an id not below len. */
+isl_status isl_index_insert(isl_index* idx, const isl_build_options* opts, const void* rows, int32_t dtype,
+                            uint64_t n_new, uint64_t d, const uint64_t* levels, int32_t mem, uint64_t* first_id);
 /* select() of ISL_SELECT_DIVERSE for nb base nodes of an index whose f32 rows are on the device
  * (bf16 rows or a recompute provider -> ISL_ERR_UNSUPPORTED): cand_ids is [nb][pitch] in any order
  * (the call computes d(base, c) and stable-sorts), cand_cnt[i] <= min(pitch, 512), cap <= 128;

@@ -157,6 +157,24 @@ class LeannIndex {
                                &idx.h_));
     return idx;
   }
+  // More rows into the index, in place (isl_index_insert): `vectors` is n rows of d floats, which become nodes
+  // len .. len + n - 1 under the index's config; returns the first new id.  opts: the rule and batch of this
+  // call; levels: one per row, or NULL.  With batch 1 the index afterwards is the one build() makes of all rows.
+  // On an error the index is unchanged.  Not beside searches on the same index.
+  uint64_t insert(const std::vector<float>& vectors, uint64_t n, uint64_t d,
+                  const isl_build_options& opts = build_options(), const uint64_t* levels = nullptr) {
+    uint64_t first = 0;
+    check(isl_index_insert(h_, &opts, n ? vectors.data() : nullptr, ISL_DTYPE_F32, n, d, levels, ISL_MEM_HOST, &first));
+    return first;
+  }
+  // ... of an index that stores bf16 rows: n rows of d bf16 bit patterns
+  uint64_t insert_bf16(const std::vector<uint16_t>& rows_bits, uint64_t n, uint64_t d,
+                       const isl_build_options& opts = build_options(), const uint64_t* levels = nullptr) {
+    uint64_t first = 0;
+    check(isl_index_insert(h_, &opts, n ? rows_bits.data() : nullptr, ISL_DTYPE_BF16, n, d, levels, ISL_MEM_HOST,
+                           &first));
+    return first;
+  }
   // select() of the diverse rule for one base node over candidates in any order (isl_select_neighbors)
   std::vector<uint64_t> select_neighbors(uint64_t base, const std::vector<uint64_t>& candidates, uint64_t cap,
                                          const isl_build_options& opts = build_options()) const {

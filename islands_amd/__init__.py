@@ -393,6 +393,55 @@ class LeannIndex:
                                                None if lv is None else _ptr(lv), mem, device, C.byref(h)))
         return cls(_handle=h)
 
+    def _insert(self, rows, dtype: int, levels, batch, select, alpha, keep_pruned) -> int:
+        want = "torch.float32" if dtype == 0 else ("torch.uint16", "torch.int16", "torch.bfloat16")
+        on_device = hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False)
+        if on_device:
+            v = rows.contiguous()
+            if str(v.dtype) not in want:
+                raise TypeError("device rows must be float32" if dtype == 0 else
+                                "device rows must be bf16 (or their 16-bit patterns)")
+            if v.dim() == 1:
+                v = v.reshape(1, -1)
+            n, d = int(v.shape[0]), int(v.shape[1])
+            vp = C.c_void_p(v.data_ptr())
+        else:
+            v = np.ascontiguousarray(rows, dtype=np.float32 if dtype == 0 else np.uint16)
+            if v.ndim == 1:
+                v = v.reshape(1, -1)
+            n, d = v.shape
+            vp = _ptr(v)
+        lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint64).reshape(-1)
+        if lv is not None and lv.size != n:
+            raise ValueError("one level per row")
+        o = self._build_options(select, alpha, keep_pruned, batch)
+        first = u64()
+        _check(_ffi.lib().isl_index_insert(self._h, C.byref(o), vp if n else None, dtype, n, d,
+                                           None if lv is None or not n else _ptr(lv),
+                                           MEM_DEVICE if on_device else MEM_HOST, C.byref(first)))
+        if n:
+            self._pq = None  # the codes were detached with the insert
+        return int(first.value)
+
+    def insert(self, rows, levels=None, batch: int = 1, select="reference", alpha: float = 1.0,
+               keep_pruned: bool = True) -> int:
+        """More rows into the index, in place (isl_index_insert): they become nodes len .. len + n - 1 under the
+        config the index carries; returns the first new id.  `levels`, `batch` and the rule are those of this
+        call, as for `build`.  The graph afterwards is the state of LeannIndex::build's loop continued at node
+        len; with batch = 1, on an index built with batch = 1, that is the index `build` makes of all rows, byte
+        for byte.  The index must hold float32 rows on the device (a build, or upload + set_embeddings); an empty
+        index takes the rows as `build` would.  Entry seeds are kept as they are (not re-selected), PQ codes are
+        detached.  On an error the index is unchanged.  `rows`: an array, or a float32 torch tensor resident on
+        the index's device.  Not beside searches on the same index."""
+        return self._insert(rows, 0, levels, batch, select, alpha, keep_pruned)
+
+    def insert_bf16(self, rows_bits, levels=None, batch: int = 1, select="reference", alpha: float = 1.0,
+                    keep_pruned: bool = True) -> int:
+        """insert() for an index that stores bf16 rows: `rows_bits` is [n, d] uint16 bit patterns (or a 16-bit
+        torch tensor on the index's device).  The construction runs over their exact f32 images; the grown index
+        keeps bf16 rows."""
+        return self._insert(rows_bits, 1, levels, batch, select, alpha, keep_pruned)
+
     def select_neighbors(self, base_ids, candidates, cap: int, alpha: float = 1.0,
                          keep_pruned: bool = True, counts=None):
         """isl_select_neighbors: the diverse rule's select() for every base node over its row of

@@ -834,20 +834,21 @@ isl_status isl_set_recompute_provider(isl_index* idx, isl_encoder* enc, const ui
 
 }  // extern "C"
 
-// The f32 provider of a graph that grows (Scaffold::open over rows from two sources): one table of
-// old's rows + n_new, the first of them copied on the device from `old` together with their norms (a row's
-// norm is a function of the row alone: the copied value is the bits a recomputation would give), the rest
-// taken from `rows` as isl_set_embeddings takes them (RowTable::fill).  `idx` is a fresh construction graph.
-isl_status isl::set_grown_embeddings(isl_index* idx, const isl_index* old, const float* rows, uint64_t n_new,
-                                     uint64_t d, int32_t mem) {
+// The in-memory provider of a graph that grows (Scaffold::open over rows from two sources): one table of
+// old's rows + n_new of old's stored type, the first of them copied on the device from `old` together with their
+// norms (a row's norm is a function of the row alone: the copied value is the bits a recomputation would give),
+// the rest taken from `rows` as isl_set_embeddings takes them (RowTable::fill).  `idx` is a fresh construction graph.
+isl_status isl::set_grown_embeddings(isl_index* idx, const isl_index* old, const void* rows, int32_t dtype,
+                                     uint64_t n_new, uint64_t d, int32_t mem) {
   const RowTable& o = old->rows;
   const uint64_t n0 = o.n(), n = n0 + n_new;
-  if (!o.f32() || !o.norm2() || o.d() != d)
-    return fail(ISL_ERR_UNSUPPORTED, "the graph's rows are not resident f32 rows of this dimension");
+  if (!o.resident() || !o.norm2() || o.d() != d || o.dtype() != dtype)
+    return fail(ISL_ERR_UNSUPPORTED, "the graph's rows are not resident rows of this type and dimension");
   ISL_TRY(use_device(idx->device));
   std::lock_guard<std::mutex> lock(idx->mu);
-  ISL_TRY(idx->rows.allocate(ISL_DTYPE_F32, n, d));
-  ISL_HIP(hipMemcpy(idx->rows.f32(), o.f32(), (size_t)n0 * o.stride() * 4, hipMemcpyDeviceToDevice));
+  ISL_TRY(idx->rows.allocate(dtype, n, d));
+  ISL_HIP(hipMemcpy(idx->rows.as<unsigned char>(), o.data(), (size_t)(n0 * o.stride() * isl_rows::elem_size(dtype)),
+                    hipMemcpyDeviceToDevice));
   ISL_HIP(hipMemcpy(idx->rows.norm2(), o.norm2(), (size_t)n0 * 4, hipMemcpyDeviceToDevice));
   idx->nvec = n;
   return idx->rows.fill(n0, n_new, rows, mem);

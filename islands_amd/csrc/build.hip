@@ -19,6 +19,11 @@
 // type as a template parameter and measure bf16 rows with the tile-free routine of device_common.hip.h over
 // the exact f32 images, so the graph is the one built from the widened rows.
 //
+// isl_index_insert continues that loop at node `len` of a finished index, in place: the index's CSR returns to the
+// construction table (csr_to_table_kernel), the rows of all nodes are the old table copied on the device plus the new
+// rows, and the grown graph, built beside the old one, moves into the caller's handle at the end (adopt_grown).
+// Build and insert are argument checks around one function, grow_flat.
+//
 // The HnswGraph builder (hnsw_build.hip) runs the same selection kernels and link_kernel's HNSW mode
 // over one fixed-width table per layer.  Both go through one host path, isl_build::Scaffold
 // (build_internal.hpp, defined below the kernels): the construction graph and everything allocated for
@@ -433,7 +438,7 @@ __global__ void ell_to_csr_kernel(const uint32_t* __restrict__ ell, const uint32
   for (uint32_t i = lane; i < deg[row]; i += 64) adj[off[row] + i] = ell[row * W + i];
 }
 
-// The inverse, for a finished graph that takes more nodes (isl_hnsw_insert): one wave per row reads the
+// The inverse, for a finished graph that takes more nodes (isl_index_insert, isl_hnsw_insert): one wave per row reads the
 // row's CSR slice, lane after lane, into its table row and leaves the degree.  Lists of up to 128 ids take
 // two slices of 64.  Nothing is written outside the row: what does not fit raises a flag instead.
 __global__ __launch_bounds__(256) void csr_to_table_kernel(const uint64_t* __restrict__ off,
@@ -553,8 +558,7 @@ isl_status Scaffold::alloc_bytes(void** out, uint64_t bytes, bool zero, bool kep
 isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw_, const void* vectors,
                           int32_t dtype, uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0,
                           uint32_t ef, const isl_index* old) {
-  if (dtype != ISL_DTYPE_F32 && (hnsw_ || old))
-    return isl::fail(ISL_ERR_UNSUPPORTED, "the HnswGraph builder keeps f32 vectors");
+  if (dtype != ISL_DTYPE_F32 && hnsw_) return isl::fail(ISL_ERR_UNSUPPORTED, "the HnswGraph builder keeps f32 vectors");
   ISL_TRY(isl_index_new(&cfg, &g));
   g->cfg.prune_ratio = 0.0f;  // construction searches do not prune (leann.rs:692-749)
   g->is_hnsw = hnsw_;         // HnswGraph heap order: distance alone
@@ -564,7 +568,7 @@ isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& 
   g->has_dimension = true;
   g->dimension = d;
   g->max_degree = m0;  // the widest row a construction search can meet: a row is back at <= m0 ids before the next search
-  if (old) ISL_TRY(isl::set_grown_embeddings(g, old, static_cast<const float*>(vectors), n - old->nvec, d, mem));
+  if (old) ISL_TRY(isl::set_grown_embeddings(g, old, vectors, dtype, n - old->nvec, d, mem));
   else ISL_TRY(isl_set_embeddings(g, vectors, n, d, dtype, mem));
   hnsw = hnsw_;
   diverse = opts.select_rule == ISL_SELECT_DIVERSE;
@@ -674,50 +678,60 @@ extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg, const isl_
   return isl_index_build_rows(cfg, opts, vectors, ISL_DTYPE_F32, n, d, levels, mem, device, out);
 }
 
-extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const isl_build_options* opts_in,
-                                           const void* vectors, int32_t dtype, uint64_t n, uint64_t d,
-                                           const uint64_t* levels, int32_t mem, int32_t device, isl_index** out) {
+namespace {
+
+// LeannIndex::build (leann.rs:578-615) for nodes n0 .. n-1 of a graph that holds n0 (`old`: a finished index
+// with resident rows of `dtype`, whose CSR returns to the builder's table in its stored order and whose
+// entry_point / max_level the loop continues from; NULL: nothing, node 0 starts the graph).  One loop over the
+// plan's steps, then compaction.  `old` is only read; the graph of all n nodes leaves in `out`, built beside
+// it, with the rows of all n nodes.  `levels`: of all n nodes, or empty (all 0).
+isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts, const isl_index* old,
+                     const void* vectors, int32_t dtype, uint64_t n_new, uint64_t d, const std::vector<uint64_t>& levels,
+                     int32_t mem, int32_t device, isl_index** out) {
   using isl::fail;
-  if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
-  isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
-  ISL_TRY(isl_build::check_row_dtype(dtype));
-  isl_leann_config cfg;
-  if (cfg_in) cfg = *cfg_in;
-  else isl_leann_config_paper_default(&cfg);
-  ISL_TRY(isl_leann_config_validate(&cfg));
-  if (n == 0) return isl_index_new(&cfg, out);  // build(&[]) -> Ok(()), leann.rs:565-567
-  if (d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
-  if (const char* why = isl_plan::shape_limit(cfg.m0, cfg.ef_construction, n)) return fail(ISL_ERR_UNSUPPORTED, "%s", why);
+  const uint64_t n0 = old ? old->num_nodes : 0, n = n0 + n_new;
   ISL_TRY(isl::use_device(device));
   // `levels` only name the entry point here (they are an input because random_level draws from thread_rng):
   // the steps are the planner's for all-zero levels, nodes in id order
   std::vector<isl_plan::Step> steps;
   {
     std::vector<uint32_t> order;
-    isl_plan::plan_steps(std::vector<uint32_t>(n, 0u), opts.batch ? opts.batch : 1, steps, order);
+    isl_plan::plan_steps_from(std::vector<uint32_t>(n, 0u), n0 ? n0 : 1, 0u, opts.batch ? opts.batch : 1, steps, order);
   }
   const uint32_t m0 = (uint32_t)cfg.m0, ef = (uint32_t)cfg.ef_construction;
 
   Scaffold c;
-  ISL_TRY(c.open(cfg, opts, false, vectors, dtype, n, d, mem, device, isl_plan::largest_step(steps), m0, ef));
+  ISL_TRY(c.open(cfg, opts, false, vectors, dtype, n, d, mem, device, isl_plan::largest_step(steps), m0, ef, old));
   Table t{nullptr, nullptr, m0};
   ISL_TRY(c.alloc(&t.ell, n * (m0 + 1)));
   ISL_TRY(c.alloc(&t.deg, n, true));
   isl_index* g = c.g;
 
-  bool has_entry = false;
-  uint64_t entry = 0, max_level = 0;
+  bool has_entry = old && old->has_entry;
+  uint64_t entry = has_entry ? old->entry_point : 0, max_level = old ? old->max_level : 0;
+  if (old) {
+    // the finished lists return to the table; rows n0 .. n-1 keep degree 0
+    uint32_t* d_flag = nullptr;
+    ISL_TRY(c.alloc(&d_flag, 1, true));
+    ISL_TRY(c.csr_to_table(t, old->d_off, old->d_adj, old->nnz, n0, d_flag));
+    uint32_t flag = 0;
+    if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(ISL_ERR_DEVICE, "importing the index's lists failed");
+    if (flag & 1u)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index has a list longer than m0 = %u", m0);
+    if (old->host_csr_valid && old->node_offsets.size() == n0 + 1 && old->node_offsets[n0] != old->nnz)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the device copy of the graph is not the lists verbatim (ids "
+                  "repeated inside a list were removed at upload)");
+    if (flag & 4u) return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: a list names an id that is not below len = %llu",
+                               (unsigned long long)n0);
+    if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index's offsets do not fit its lists");
+  }
   auto note_level = [&](uint64_t id) {  // :610-613
-    const uint64_t lv = levels ? levels[id] : 0;
+    const uint64_t lv = levels.empty() ? 0 : levels[id];
     if (!has_entry || lv > max_level) { has_entry = true; entry = id; max_level = lv; }
   };
-  // node 0: no neighbours (adjacency is empty, :585), becomes the entry point
-  note_level(0);
+  // node 0 of an empty graph: no neighbours (adjacency is empty, :585), becomes the entry point
+  if (!n0) note_level(0);
   for (const isl_plan::Step& s : steps) {
     g->has_entry = true;
     g->entry_point = entry;  // :669: entry_point.unwrap_or(0) as of the start of the step
@@ -740,8 +754,74 @@ extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const
   ISL_TRY(c.table_to_csr(t, n, false, &d_off, &d_adj));
   ISL_TRY(isl_index_from_device_csr(&cfg, device, n, d_off, d_adj, 1, entry, 1, d, &c.res));
   c.res->max_level = max_level;
-  if (levels) c.res->levels.assign(levels, levels + n);
-  isl_index* built = c.release();
+  c.res->levels = levels;
+  *out = c.release();
+  return ISL_OK;
+}
+
+// What isl_index_insert does to the handle once the grown graph stands beside it (under idx->mu, no lane busy):
+// every member that follows the node count takes the grown graph's value or goes.  Nothing here can fail.
+void adopt_grown(isl_index* idx, isl_index* grown) {
+  // host CSR (read back from the device on demand), levels, entry
+  idx->host_csr_valid = grown->host_csr_valid;
+  idx->node_offsets.swap(grown->node_offsets);
+  idx->neighbors.swap(grown->neighbors);
+  idx->levels.swap(grown->levels);
+  idx->degree_counts.swap(grown->degree_counts);
+  idx->num_nodes = grown->num_nodes;
+  idx->has_entry = grown->has_entry;
+  idx->entry_point = grown->entry_point;
+  idx->max_level = grown->max_level;
+  idx->has_dimension = grown->has_dimension;
+  idx->dimension = grown->dimension;
+  // device CSR and rows
+  idx->device = grown->device;
+  idx->d_off = std::move(grown->d_off);
+  idx->d_adj = std::move(grown->d_adj);
+  idx->nnz = grown->nnz;
+  idx->max_degree = grown->max_degree;
+  idx->rows = std::move(grown->rows);
+  idx->nvec = grown->nvec;
+  // the padded adjacency of the old graph goes.  In its place comes the grown graph's, which
+  // isl_index_from_device_csr has just made: the copy the next search would otherwise make again (absent when
+  // there was no memory for it; the searches then pad on demand or stay on the CSR)
+  idx->ell_copy = std::move(grown->ell_copy);
+  idx->ell_deg_copy = std::move(grown->ell_deg_copy);
+  idx->d_ell = idx->ell_copy; idx->d_ell_deg = idx->ell_deg_copy; idx->ell_w = grown->ell_w;
+  grown->d_ell = nullptr; grown->d_ell_deg = nullptr;
+  // vis_words / cand_cap follow the node count: the pool is made again on demand
+  isl::free_exact_pool(idx->pool);
+  // PQ codes no longer cover every node
+  idx->pq = nullptr; idx->d_codes.reset(); idx->ncodes = 0;
+  // kept: cfg, evals_hint, the entry seeds (ids and row copies of nodes the graph still has), the lanes (their
+  // buffers follow nq, k, ef, d and the wave count of a call, never the node count)
+}
+
+}  // namespace
+
+extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const isl_build_options* opts_in,
+                                           const void* vectors, int32_t dtype, uint64_t n, uint64_t d,
+                                           const uint64_t* levels, int32_t mem, int32_t device, isl_index** out) {
+  using isl::fail;
+  if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  isl_build_options opts;
+  isl_build_options_default(&opts);
+  if (opts_in) {
+    ISL_TRY(isl_build::check_build_options(opts_in, true));
+    opts = *opts_in;
+  }
+  ISL_TRY(isl_build::check_row_dtype(dtype));
+  isl_leann_config cfg;
+  if (cfg_in) cfg = *cfg_in;
+  else isl_leann_config_paper_default(&cfg);
+  ISL_TRY(isl_leann_config_validate(&cfg));
+  if (n == 0) return isl_index_new(&cfg, out);  // build(&[]) -> Ok(()), leann.rs:565-567
+  if (d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
+  if (const char* why = isl_plan::shape_limit(cfg.m0, cfg.ef_construction, n)) return fail(ISL_ERR_UNSUPPORTED, "%s", why);
+  std::vector<uint64_t> lv;
+  if (levels) lv.assign(levels, levels + n);
+  isl_index* built = nullptr;
+  ISL_TRY(grow_flat(cfg, opts, nullptr, vectors, dtype, n, d, lv, mem, device, &built));  // insert into nothing
   // ISL_ENTRY_SEEDS=N: the finished index leaves with N entry seeds selected (as isl_index_select_entry_seeds)
   const isl_status seeded = isl::env_entry_seeds(built);
   if (seeded != ISL_OK) {
@@ -751,6 +831,73 @@ extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const
     return seeded;
   }
   *out = built;
+  return ISL_OK;
+}
+
+extern "C" isl_status isl_index_insert(isl_index* idx, const isl_build_options* opts_in, const void* rows, int32_t dtype,
+                                       uint64_t n_new, uint64_t d, const uint64_t* levels, int32_t mem,
+                                       uint64_t* first_id) {
+  using isl::fail;
+  if (!idx || (!rows && n_new)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  isl_build_options opts;
+  isl_build_options_default(&opts);
+  if (opts_in) {
+    ISL_TRY(isl_build::check_build_options(opts_in, true));
+    opts = *opts_in;
+  }
+  ISL_TRY(isl_build::check_row_dtype(dtype));
+  const uint64_t n0 = idx->num_nodes;
+  if (n_new == 0) {
+    if (first_id) *first_id = n0;
+    return ISL_OK;
+  }
+  if (idx->is_hnsw)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: this is the core index of an HnswGraph, which grows through "
+                "isl_hnsw_insert");
+  if (idx->recompute)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: an index on the recompute provider does not take rows");
+  const isl::RowTable& old_rows = idx->rows;
+  if (n0) {
+    const bool known = idx->has_dimension || old_rows.resident();
+    const uint64_t have = idx->has_dimension ? idx->dimension : old_rows.d();
+    if (known && d != have) return isl::fail_dim(have, d);
+  }
+  if (d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
+  if (n0) {
+    if (idx->device < 0 || !idx->d_off || !old_rows.resident() || !old_rows.norm2() || old_rows.n() != n0 ||
+        idx->nvec != n0 || old_rows.d() != d)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert needs the index's rows resident on the device "
+                  "(isl_index_upload, isl_set_embeddings)");
+    if (old_rows.dtype() != dtype)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index stores %s rows and takes no other type",
+                  old_rows.is_bf16() ? "bf16" : "float32");
+  }
+  const isl_leann_config cfg = idx->cfg;
+  if (const char* why = isl_plan::shape_limit(cfg.m0, cfg.ef_construction, n0 + n_new))
+    return fail(ISL_ERR_UNSUPPORTED, "%s", why);
+  {  // the &mut self of the reference: not beside a search on the same handle
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (isl::any_lane_busy(idx))
+      return fail(ISL_ERR_SEARCH, "Search error: the index cannot grow while searches are in flight");
+  }
+  // levels of all nodes: the index's (all 0 where it keeps none), then the new nodes'
+  std::vector<uint64_t> lv(n0 + n_new, 0);
+  if (idx->levels.size() == n0) std::copy(idx->levels.begin(), idx->levels.end(), lv.begin());
+  if (levels) std::copy(levels, levels + n_new, lv.begin() + n0);
+  isl_index* grown = nullptr;
+  ISL_TRY(grow_flat(cfg, opts, n0 ? idx : nullptr, rows, dtype, n_new, d, lv, mem,
+                    idx->device >= 0 ? idx->device : 0, &grown));
+  // the move: the grown graph was built beside the old one, which nothing has touched so far
+  {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (isl::any_lane_busy(idx)) {
+      isl_index_free(grown);
+      return fail(ISL_ERR_SEARCH, "Search error: the index cannot grow while searches are in flight");
+    }
+    adopt_grown(idx, grown);
+  }
+  isl_index_free(grown);  // what is left of it: the old graph's host vectors
+  if (first_id) *first_id = n0;
   return ISL_OK;
 }
 

@@ -85,9 +85,10 @@ struct Scaffold {
   // The construction graph over `vectors` and the buffers of steps of up to B nodes, rows of up to m0 ids.
   // cfg: metric (and, for LeannIndex::build, the hub rule); opts: the selection rule.
   // dtype: what `vectors` holds and the construction graph stores (isl_set_embeddings); bf16 rows are for
-  // LeannIndex::build alone (not with hnsw, not with `old`).
-  // With `old` (a finished graph that grows, isl_hnsw_insert) the rows come from two sources: the first
-  // old->nvec of the n are old's rows and norms, copied on the device; `vectors` holds the n - old->nvec new ones.
+  // LeannIndex::build alone (not with hnsw).
+  // With `old` (a finished graph that grows, isl_index_insert / isl_hnsw_insert) the rows come from two sources:
+  // the first old->nvec of the n are old's rows and norms, copied on the device; `vectors` holds the
+  // n - old->nvec new ones, of old's stored type.
   isl_status open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw, const void* vectors,
                   int32_t dtype, uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0,
                   uint32_t ef, const isl_index* old = nullptr);

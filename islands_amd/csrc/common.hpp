@@ -304,10 +304,11 @@ isl_status search_device_sync(const isl_index* idx, const float* d_queries, uint
 // shard.hip: marks the queries of call `token` that failed with ISL_SHARD_POISON_COUNT in d_counts [nq]
 isl_status poison_failed_queries(const isl_index* idx, uint64_t token, uint32_t* d_counts, uint64_t nq, hipStream_t stream);
 isl_status materialise_host_csr(const isl_index* idx);
-// api_index.hip -- the f32 row table of a graph that grows: old's rows and norms copied on the device, then
-// n_new rows from `rows` (host or device, `mem`) and their norms; `idx` is a fresh construction graph
-isl_status set_grown_embeddings(isl_index* idx, const isl_index* old, const float* rows, uint64_t n_new, uint64_t d,
-                                int32_t mem);
+// api_index.hip -- the row table of a graph that grows: old's rows and norms copied on the device, then n_new
+// rows of the same stored type (`dtype`) from `rows` (host or device, `mem`) and their norms; `idx` is a fresh
+// construction graph
+isl_status set_grown_embeddings(isl_index* idx, const isl_index* old, const void* rows, int32_t dtype, uint64_t n_new,
+                                uint64_t d, int32_t mem);
 // build_distance_tables (pq.rs:307-338) for nq device-resident queries into d_tables [nq][m][K]
 isl_status pq_launch_tables(const isl_pq* pq, const float* d_queries, uint64_t nq, float* d_tables,
                             hipStream_t st);

@@ -1,5 +1,5 @@
 """Build time and quality of the device graph builder (isl_index_build_rows) in its batched mode.
-    python tools/build_perf.py [--nodes N] [--dim D] [--batch B] [--dataset G|M] [--select reference|diverse]
+    python tools/build_perf.py [build|insert] [--nodes N] [--dim D] [--batch B] [--dataset G|M] [--select reference|diverse]
                                [--alpha A] [--no-keep-pruned] [--ef 128,256] [--nq Q] [--check-truth]
                                [--row-dtype f32|bf16[,...]]
 Prints one JSON line per leg: build seconds, peak device memory during the build, recall@10 / evaluations /
@@ -7,7 +7,13 @@ hops per query at every ef, mean and minimum degree.  Dataset G = synth.make_row
 rows), M = synth.make_manifold.  --row-dtype names the legs, built one after the other in this process
 (f32,bf16,f32,bf16 alternates them).  With a bf16 leg the generated rows are rounded to bf16 once and every
 leg builds from those values -- the f32 legs from their widened images -- so all legs build the same graph
-problem, and the truth is the brute force over the widened rows."""
+problem, and the truth is the brute force over the widened rows.
+
+`insert` measures isl_index_insert instead (f32 rows; defaults: dataset M, diverse rule, 1024 queries, recall at
+the first --ef): an index of N - K rows (--insert-rows K, default 65536) takes the last K rows in one call; a second
+copy of it takes them in --insert-calls calls (default 16); then one more row goes into that copy -- the fixed
+cost of a call -- and the one-call build of all N rows stands beside them.  One JSON line: seconds per call and
+rows/s, and recall@10 of the two grown graphs and of the one-call graph against isl_bruteforce_topk."""
 import argparse, json, os, sys, threading, time
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
 import numpy as np, torch
@@ -16,19 +22,26 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import synth
 
 ap = argparse.ArgumentParser()
+ap.add_argument("mode", nargs="?", choices=["build", "insert"], default="build")
+ap.add_argument("--insert-rows", type=int, default=65536)
+ap.add_argument("--insert-calls", type=int, default=16)
 ap.add_argument("--nodes", type=int, default=1_000_000)
 ap.add_argument("--dim", type=int, default=768)
 ap.add_argument("--batch", type=int, default=4096)
-ap.add_argument("--dataset", choices=["G", "M"], default="G")
-ap.add_argument("--select", choices=["reference", "diverse"], default="reference")
+ap.add_argument("--dataset", choices=["G", "M"], default=None, help="default G (build), M (insert)")
+ap.add_argument("--select", choices=["reference", "diverse"], default=None, help="default reference (build), diverse (insert)")
 ap.add_argument("--alpha", type=float, default=1.0)
 ap.add_argument("--no-keep-pruned", action="store_true")
 ap.add_argument("--ef", default="128,256", help="comma-separated ef values of the recall measurement")
-ap.add_argument("--nq", type=int, default=512)
+ap.add_argument("--nq", type=int, default=None, help="default 512 (build), 1024 (insert)")
 ap.add_argument("--qstart", type=int, default=0, help="dataset G: first row of the query stream (bench.py's batch b starts at 1024 b)")
 ap.add_argument("--row-dtype", default="f32", help="comma-separated legs, each f32 or bf16")
 ap.add_argument("--check-truth", action="store_true", help="also report how far torch's brute force agrees with the truth")
 args = ap.parse_args()
+inserting = args.mode == "insert"
+args.dataset = args.dataset or ("M" if inserting else "G")
+args.select = args.select or ("diverse" if inserting else "reference")
+args.nq = args.nq or (1024 if inserting else 512)
 N, d, nq = args.nodes, args.dim, args.nq
 legs = args.row_dtype.split(",")
 if any(leg not in ("f32", "bf16") for leg in legs):
@@ -55,6 +68,60 @@ xbits = (xh.view(np.uint32) >> 16).astype(np.uint16) if rounded else None  # exa
 del x
 torch.cuda.empty_cache()
 cfg = ia.LeannConfig.paper_default()
+
+
+def recall_at_10(idx, ef):
+    ids, dist, cnt = idx.search_batch(qh, 10, ef)
+    hit = sum(len(set(ids[i, :cnt[i]].tolist()) & set(ti[i].tolist())) for i in range(nq))
+    return round(hit / (10.0 * nq), 4)
+
+
+def insert_mode():
+    K, calls = args.insert_rows, args.insert_calls
+    if legs != ["f32"] or not 0 < K < N or K % calls:
+        ap.error("insert: f32 rows, 0 < --insert-rows < --nodes, a multiple of --insert-calls")
+    n0, ef = N - K, int(args.ef.split(",")[0])
+    kw = dict(batch=args.batch, select=args.select, alpha=args.alpha, keep_pruned=not args.no_keep_pruned)
+
+    def timed(f):
+        t = time.time()
+        r = f()
+        return r, time.time() - t
+
+    one, base_s = timed(lambda: ia.LeannIndex.build(xh[:n0], cfg, **kw))
+    _, one_s = timed(lambda: one.insert(xh[n0:], **kw))
+    assert len(one) == N
+    recall_one = recall_at_10(one, ef)
+    del one
+    many = ia.LeannIndex.build(xh[:n0], cfg, **kw)
+    step, per_call = K // calls, []
+    for c in range(calls):
+        first, dt = timed(lambda: many.insert(xh[n0 + c * step:n0 + (c + 1) * step], **kw))
+        assert first == n0 + c * step
+        per_call.append(round(dt, 3))
+    recall_many = recall_at_10(many, ef)
+    extra = synth.make_manifold(1, d, 977, device=dev).cpu().numpy() if args.dataset == "M" else xh[:1] * np.float32(0.5)
+    _, single_s = timed(lambda: many.insert(extra, **kw))
+    assert len(many) == N + 1
+    del many
+    whole, whole_s = timed(lambda: ia.LeannIndex.build(xh, cfg, **kw))
+    print(json.dumps({
+        "what": "build_perf insert", "dataset": args.dataset, "nodes": N, "dim": d, "batch": args.batch,
+        "select": args.select, "alpha": args.alpha, "keep_pruned": not args.no_keep_pruned, "m0": cfg.m0,
+        "ef_construction": cfg.ef_construction, "inserted_rows": K, "build_base_s": round(base_s, 2),
+        "one_call": {"seconds": round(one_s, 3), "rows_per_s": round(K / one_s)},
+        "many_calls": {"calls": calls, "rows_per_call": step, "seconds_per_call": per_call,
+                       "seconds": round(sum(per_call), 3), "rows_per_s": round(K / sum(per_call))},
+        "one_row_call_s": round(single_s, 3),
+        "one_call_build": {"seconds": round(whole_s, 2), "nodes_per_s": round(N / whole_s)},
+        "queries": nq, "ef": ef,
+        "recall_at_10": {"grown_one_call": recall_one, "grown_many_calls": recall_many,
+                         "one_call_build": recall_at_10(whole, ef)}}), flush=True)
+
+
+if inserting:
+    insert_mode()
+    sys.exit(0)
 
 
 def used_bytes():
