@@ -205,6 +205,49 @@ isl_status isl_index_build_rows(const isl_leann_config* cfg, const isl_build_opt
  * the lists verbatim (ids repeated inside a list were removed at upload); an id not below len. */
 isl_status isl_index_insert(isl_index* idx, const isl_build_options* opts, const void* rows, int32_t dtype,
                             uint64_t n_new, uint64_t d, const uint64_t* levels, int32_t mem, uint64_t* first_id);
+/* Rows out of a built index, in place (extension: the reference has no removal on LeannIndex).  ids = n_ids node
+ * ids in host memory, repeated ids counting once: the set D.  opts = the selection rule of this call (select_rule,
+ * alpha, keep_pruned; NULL: the defaults; batch is not used).  out_remap [old len] (may be NULL) receives the new
+ * id of every old node or ISL_REMOVED, *out_len (may be NULL) the new len; both are written only on ISL_OK.
+ * Definition, over a flat index with len nodes, lists L[p] in their stored order and resident rows:
+ * 1. Repair over the old ids.  Every list is computed from the OLD lists only, so the result does not depend on
+ *    the order in which nodes are processed.  For each survivor p: if no id of L[p] is in D, L'[p] = L[p].
+ *    Otherwise the candidate list C(p): walk L[p] in stored order; a survivor x emits x; a removed x emits every y
+ *    of L[x], in stored order, with y not in D and y != p; the first occurrence of every id is kept; the walk
+ *    stops after ISL_REMOVE_MAX_CANDIDATES distinct ids (the builder's bound on a candidate list).  If |C(p)| <= m0,
+ *    L'[p] = C(p) in that order.  If |C(p)| > m0: d(p, c) = Distance::calculate(vec[p], vec[c]) through the
+ *    library's exact-order chain, C(p) stable-sorted ascending by it (NaN last, -0 == +0), then
+ *    ISL_SELECT_REFERENCE keeps the first m0 (prune_neighbors_temp, leann.rs:634-658, the builder's re-sort) and
+ *    ISL_SELECT_DIVERSE keeps select(p, sorted C(p), m0) as defined above.  high_degree_pruning / hub_percentile
+ *    play no part, as in the builder's re-sort.  A survivor whose candidates are all gone ends with an EMPTY
+ *    list: nothing is invented for it, and nothing may lead to it any more.
+ * 2. Compaction, order kept.  A survivor's new id is its old id minus the number of removed ids below it; lists,
+ *    levels, degree_counts, node_offsets and num_nodes follow.  Rows and norms of the survivors are copied bit
+ *    for bit on the device, f32 or bf16: nothing is converted, no norm is computed again.  Entry point: one that
+ *    survives is kept (remapped) and max_level stays; otherwise the new entry point is the lowest new id among the
+ *    survivors of the highest level and max_level is that level, which is what LeannIndex::build leaves for those
+ *    nodes (an index without entry point keeps none).  Removing every node leaves what isl_index_build_rows gives
+ *    for n == 0 under the handle's config.
+ * Strong guarantee: the shrunk graph is built beside the old one and moved into the handle at the end; on any
+ * failure idx is unchanged (bytes, rows, search answers).  Peak device memory: the old index whole, plus the
+ * (m0 + 1)-wide table over the old nodes, the shrunk CSR twice, its padded adjacency and the survivors' rows.
+ * What the handle keeps: its config, the visited-table hint and its prepared lanes (none of their buffers
+ * follows the node count), and its entry seeds REDUCED to the surviving seeds, under their new ids, their row
+ * copies gathered again from the shrunk table as isl_index_set_entry_seeds gathers them (no seed left, or no
+ * memory for the copies: no table, a plain search then starts at the entry point).  What goes: the heap-exact
+ * kernel's pool (made again on demand) and the PQ codes, detached exactly as isl_index_insert detaches them.
+ * The call is the reference's &mut self: not beside searches on the same handle.  Checked in this order before
+ * any device call: NULL idx, or NULL ids with n_ids > 0 -> ISL_ERR_INVALID_ARGUMENT; opts as in
+ * isl_index_build_ex; n_ids == 0 -> ISL_OK, nothing changed, out_remap the identity; the core index of an
+ * HnswGraph or an index on the recompute provider -> ISL_ERR_UNSUPPORTED; an id >= len ->
+ * ISL_ERR_NODE_NOT_FOUND (node); a non-empty index without resident rows -> ISL_ERR_UNSUPPORTED; m0 > 128 ->
+ * ISL_ERR_UNSUPPORTED; a busy lane -> ISL_ERR_SEARCH.  Refused once the import kernel has looked, as
+ * isl_index_insert refuses them, each with ISL_ERR_UNSUPPORTED and a message that says which: a list longer than
+ * m0; a device copy that is not the lists verbatim; an id not below len. */
+#define ISL_REMOVED UINT64_MAX
+#define ISL_REMOVE_MAX_CANDIDATES 512u
+isl_status isl_index_remove(isl_index* idx, const isl_build_options* opts, const uint64_t* ids, uint64_t n_ids,
+                            uint64_t* out_remap /* [old len], may be NULL */, uint64_t* out_len /* may be NULL */);
 /* select() of ISL_SELECT_DIVERSE for nb base nodes of an index whose f32 rows are on the device
  * (bf16 rows or a recompute provider -> ISL_ERR_UNSUPPORTED): cand_ids is [nb][pitch] in any order
  * (the call computes d(base, c) and stable-sorts), cand_cnt[i] <= min(pitch, 512), cap <= 128;

@@ -175,6 +175,15 @@ class LeannIndex {
                            &first));
     return first;
   }
+  // Rows out of the index, in place (isl_index_remove): the lists that named a removed id are repaired under
+  // opts' rule, the survivors keep their order and take new ids; returns remap[old] = new id or ISL_REMOVED.
+  // Entry seeds are reduced to the survivors, PQ codes are detached.  On an error the index is unchanged.  Not
+  // beside searches on the same index.
+  std::vector<uint64_t> remove(const std::vector<uint64_t>& ids, const isl_build_options& opts = build_options()) {
+    std::vector<uint64_t> remap(len());
+    check(isl_index_remove(h_, &opts, ids.empty() ? nullptr : ids.data(), ids.size(), remap.data(), nullptr));
+    return remap;
+  }
   // select() of the diverse rule for one base node over candidates in any order (isl_select_neighbors)
   std::vector<uint64_t> select_neighbors(uint64_t base, const std::vector<uint64_t>& candidates, uint64_t cap,
                                          const isl_build_options& opts = build_options()) const {

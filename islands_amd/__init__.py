@@ -30,6 +30,7 @@ __all__ = [
 MEM_HOST, MEM_DEVICE = 0, 1
 SELECT_REFERENCE, SELECT_DIVERSE = 0, 1  # ISL_SELECT_*
 _SELECT_RULES = {"reference": SELECT_REFERENCE, "diverse": SELECT_DIVERSE}
+REMOVED = 0xFFFFFFFFFFFFFFFF  # ISL_REMOVED: an id LeannIndex.remove took out, in the remap it returns
 
 
 class CoreError(Exception):
@@ -441,6 +442,24 @@ class LeannIndex:
         torch tensor on the index's device).  The construction runs over their exact f32 images; the grown index
         keeps bf16 rows."""
         return self._insert(rows_bits, 1, levels, batch, select, alpha, keep_pruned)
+
+    def remove(self, ids, select="reference", alpha: float = 1.0, keep_pruned: bool = True) -> np.ndarray:
+        """Rows out of the index, in place (isl_index_remove).  Every list that named a removed id is repaired from
+        the old lists alone: a removed neighbour is replaced by its own surviving neighbours, and a list that
+        outgrows m0 is cut to the m0 nearest ("reference") or re-selected by the occlusion rule ("diverse").  The
+        survivors keep their order and take new ids; their rows and norms are copied as bits.  Returns
+        remap[old id] = new id, or REMOVED.  Entry seeds are reduced to the surviving seeds, PQ codes are detached.
+        On an error the index is unchanged.  Not beside searches on the same index."""
+        a = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        o = self._build_options(select, alpha, keep_pruned)
+        n0 = len(self)
+        remap = np.zeros(max(n0, 1), dtype=np.uint64)
+        n = u64()
+        _check(_ffi.lib().isl_index_remove(self._h, C.byref(o), _ptr(a) if a.size else None, a.size, _ptr(remap),
+                                           C.byref(n)))
+        if a.size:
+            self._pq = None  # the codes were detached with the removal
+        return remap[:n0]
 
     def select_neighbors(self, base_ids, candidates, cap: int, alpha: float = 1.0,
                          keep_pruned: bool = True, counts=None):

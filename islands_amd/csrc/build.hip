@@ -24,6 +24,12 @@
 // rows, and the grown graph, built beside the old one, moves into the caller's handle at the end (adopt_grown).
 // Build and insert are argument checks around one function, grow_flat.
 //
+// isl_index_remove takes nodes out of a finished index, in place (shrink_flat): the lists return to the same table,
+// one wave per survivor that lost a neighbour rebuilds its row from the OLD CSR (repair_kernel: the removed
+// neighbours' own lists stand in for them; past m0 ids the builder's sort and selection decide), and the survivors'
+// lists, rows and norms are compacted into a graph built beside the old one, which moves in as a grown one does.
+// The remap, the entry-point rule and the LDS size are remove_plan.hpp's.
+//
 // The HnswGraph builder (hnsw_build.hip) runs the same selection kernels and link_kernel's HNSW mode
 // over one fixed-width table per layer.  Both go through one host path, isl_build::Scaffold
 // (build_internal.hpp, defined below the kernels): the construction graph and everything allocated for
@@ -31,9 +37,11 @@
 // sizes are build_plan.hpp's.
 #include "device_common.hip.h"
 #include "build_internal.hpp"
+#include "remove_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <vector>
 
 namespace {
@@ -476,6 +484,163 @@ __global__ void gather_rows_bf16_kernel(const uint16_t* __restrict__ emb, uint64
   out[i] = __uint_as_float((uint32_t)emb[(id0 + i / d) * stride + i % d] << 16);
 }
 
+// ---------------------------------------------------------------- isl_index_remove
+using isl_plan::kGone;
+
+// Survivors with at least one removed neighbour, in no particular order: one wave per row of the old CSR.
+// Runs after the import kernel has found every offset and id of the CSR in range.
+__global__ __launch_bounds__(256) void touched_kernel(const uint64_t* __restrict__ off, const uint32_t* __restrict__ adj,
+                                                      const uint32_t* __restrict__ remap, uint64_t n0,
+                                                      uint32_t* __restrict__ touched, uint32_t* __restrict__ count) {
+  const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (row >= n0 || remap[row] == kGone) return;
+  const uint64_t s = off[row];
+  const uint32_t dg = (uint32_t)(off[row + 1] - s);
+  bool hit = false;
+  for (uint32_t i = lane; i < dg; i += 64) hit |= remap[adj[s + i]] == kGone;
+  if (ballot(hit) && lane == 0) touched[atomicAdd(count, 1u)] = (uint32_t)row;  // at most one entry per row: < n0
+}
+
+struct RepairParams {
+  const void* emb;           // the OLD rows, by old id
+  const float* norm2;
+  uint64_t stride;
+  uint32_t d;
+  float alpha;
+  uint32_t keep_pruned;
+  const uint64_t* off;       // the OLD CSR: every list is computed from the old lists only
+  const uint32_t* adj;
+  const uint32_t* remap;     // [n0] new id or kGone
+  const uint32_t* touched;   // [grid]
+  uint32_t* ell;             // [n0][W] the table being written: row `node` alone, never read
+  uint32_t* deg;
+  uint32_t W, m0;
+  unsigned long long* total; // [1] sum of |C(p)| over the touched nodes
+};
+
+// The repair of include/islands_amd.h for one touched node per wave.  C(p) is streamed from the old CSR into
+// LDS: a surviving neighbour is one id on lane 0, a removed one its list in slices of 64; every slice is
+// looked up in the ids taken so far (a list of the device CSR holds no id twice, so a slice needs no look at
+// itself) and appended in lane order.  Nothing is written at or past kRemoveMaxCandidates, and the walk ends
+// there.  |C| <= m0: the row is C.  Otherwise d(p, c) in slices of 64, the rank sort of
+// select_neighbors_kernel (ordkey order: link_kernel's `<` order wherever no distance is a NaN, and a
+// permutation whatever the values), then the first m0 or select().
+template <int METRIC_API, bool DIVERSE, typename ROWT>
+__global__ __launch_bounds__(64) void repair_kernel(RepairParams p) {
+  constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
+  constexpr uint32_t CAP = isl_plan::kRemoveMaxCandidates;
+  extern __shared__ __align__(16) unsigned char smem[];
+  float* tile = reinterpret_cast<float*>(smem);
+  float* qs = tile + (kBf16<ROWT> ? 0 : TILE_ROWS * TILE_LD);
+  const SelState s = sel_state<ROWT>(qs, p.d, CAP);
+  const uint32_t lane = threadIdx.x;
+  const uint64_t below = (1ull << lane) - 1ull;
+  const uint32_t node = p.touched[blockIdx.x];
+  // the two lists the selection initialises itself hold the unsorted entries until then
+  uint32_t* raw_id = s.lst;
+  float* raw_d = reinterpret_cast<float*>(s.kept);
+  uint32_t n = 0;
+  auto take = [&](bool valid, uint32_t y) {
+    bool fresh = valid;
+    for (uint32_t j = 0; fresh && j < n; ++j) fresh = raw_id[j] != y;
+    const uint64_t m = ballot(fresh);
+    const uint32_t at = n + (uint32_t)__popcll(m & below);
+    if (fresh && at < CAP) raw_id[at] = y;
+    n += (uint32_t)__popcll(m);
+    n = n < CAP ? n : CAP;
+    __syncthreads();
+  };
+  const uint64_t ps = p.off[node];
+  const uint32_t pdeg = (uint32_t)(p.off[node + 1] - ps);
+  for (uint32_t t = 0; t < pdeg && n < CAP; ++t) {
+    const uint32_t x = uni(p.adj[ps + t]);
+    if (p.remap[x] != kGone) {
+      take(lane == 0, x);
+    } else {
+      const uint64_t xs = p.off[x];
+      const uint32_t xdeg = (uint32_t)(p.off[x + 1] - xs);
+      for (uint32_t base = 0; base < xdeg && n < CAP; base += 64) {
+        const bool in = base + lane < xdeg;
+        const uint32_t y = in ? p.adj[xs + base + lane] : 0u;
+        take(in && y != node && p.remap[y] != kGone, y);
+      }
+    }
+  }
+  if (lane == 0) atomicAdd(p.total, (unsigned long long)n);
+  uint32_t* row = p.ell + (uint64_t)node * p.W;
+  if (n <= p.m0) {
+    for (uint32_t i = lane; i < n; i += 64) row[i] = raw_id[i];
+    if (lane == 0) p.deg[node] = n;
+    return;
+  }
+  const SelCtxT<ROWT> c{static_cast<const ROWT*>(p.emb), p.norm2, p.stride, p.d, p.alpha, p.keep_pruned};
+  const float q_norm = load_row_query<METRIC>(c, node, qs);
+  for (uint32_t base = 0; base < n; base += 64) {
+    const uint32_t cnt = n - base < 64u ? n - base : 64u;
+    const bool valid = lane < cnt;
+    const uint32_t rid = valid ? raw_id[base + lane] : node;
+    const float aux = (METRIC == METRIC_COSINE_PRE && valid) ? p.norm2[rid] : 0.0f;
+    float ds;
+    if constexpr (kBf16<ROWT>) ds = direct_distances<METRIC, uint16_t>(c.emb, c.stride, c.d, rid, cnt, qs, q_norm, aux);
+    else ds = wave_distances<METRIC>(c.emb, c.stride, c.d, rid, cnt, qs, tile, q_norm, aux);
+    if (valid) raw_d[base + lane] = ds;
+  }
+  __syncthreads();
+  for (uint32_t i = lane; i < n; i += 64) {
+    const uint32_t ki = ordkey(raw_d[i]);
+    uint32_t r = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+      const uint32_t kj = ordkey(raw_d[j]);
+      r += (kj < ki) || (kj == ki && j < i);
+    }
+    s.cid[r] = raw_id[i];
+    s.cd[r] = raw_d[i];
+  }
+  __syncthreads();
+  uint32_t nk = p.m0;
+  if constexpr (DIVERSE) {
+    nk = diverse_select<METRIC>(c, n, p.m0, s, qs, tile);
+    for (uint32_t i = lane; i < nk; i += 64) row[i] = s.out[i];
+  } else {
+    for (uint32_t i = lane; i < nk; i += 64) row[i] = s.cid[i];
+  }
+  if (lane == 0) p.deg[node] = nk;
+}
+
+// Compaction of the lists: the table rows of the survivors, through the remap, into the new CSR (one wave per
+// old row).  A removed id left in a survivor's row raises the flag and is not written as an id out of range.
+__global__ __launch_bounds__(256) void table_to_csr_remap_kernel(const uint32_t* __restrict__ ell,
+                                                                 const uint32_t* __restrict__ deg, uint32_t W,
+                                                                 const uint32_t* __restrict__ remap,
+                                                                 const uint64_t* __restrict__ off, uint64_t n0,
+                                                                 uint32_t* __restrict__ adj, uint32_t* __restrict__ flag) {
+  const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (row >= n0) return;
+  const uint32_t to = remap[row];
+  if (to == kGone) return;
+  const uint32_t dg = deg[row] < W ? deg[row] : W - 1;
+  for (uint32_t i = lane; i < dg; i += 64) {
+    uint32_t id = remap[ell[row * W + i]];
+    if (id == kGone) { atomicOr(flag, 1u); id = 0; }
+    adj[off[to] + i] = id;
+  }
+}
+
+// ... and of the rows: survivor `s` of the old table becomes row s of the new one, every element of the stride
+// and the norm copied as bits
+template <typename T>
+__global__ __launch_bounds__(256) void gather_survivor_rows_kernel(const T* __restrict__ emb, uint64_t stride,
+                                                                   const float* __restrict__ norm2,
+                                                                   const uint32_t* __restrict__ survivors,
+                                                                   T* __restrict__ out, float* __restrict__ out_norm2) {
+  const uint64_t s = blockIdx.x;
+  const uint64_t id = survivors[s];
+  for (uint64_t j = threadIdx.x; j < stride; j += 256) out[s * stride + j] = emb[id * stride + j];
+  if (threadIdx.x == 0) out_norm2[s] = norm2[id];
+}
+
 constexpr size_t kTileBytes = (size_t)TILE_ROWS * TILE_LD * 4;
 // (bf16 rows: no tile)
 size_t sel_lds(bool bf16, uint64_t d, uint32_t nmax, uint32_t M) {
@@ -505,6 +670,17 @@ void launch_select_diverse(uint32_t metric, uint32_t grid, size_t lds, const Bui
       hipLaunchKernelGGL((select_diverse_kernel<decltype(mc)::value, uint16_t>), dim3(grid), dim3(64), lds, 0, p);
     else
       hipLaunchKernelGGL(select_diverse_kernel<decltype(mc)::value>, dim3(grid), dim3(64), lds, 0, p);
+  });
+}
+// one wave per touched node, the kernel instantiated for the index's metric, the rule and the row type
+void launch_repair(uint32_t metric, bool diverse, const isl::RowTable& rows, uint32_t grid, const RepairParams& p) {
+  const size_t lds = rows.is_bf16() ? isl_plan::repair_lds_bf16(p.d, p.m0) : isl_plan::repair_lds(kTileBytes, p.d, p.m0);
+  isl::by_metric(metric, [&](auto mc) {
+    rows.with_row_type([&](auto row) {
+      using T = decltype(row);
+      if (diverse) hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, true, T>), dim3(grid), dim3(64), lds, 0, p);
+      else hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, false, T>), dim3(grid), dim3(64), lds, 0, p);
+    });
   });
 }
 
@@ -761,6 +937,8 @@ isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts,
 
 // What isl_index_insert does to the handle once the grown graph stands beside it (under idx->mu, no lane busy):
 // every member that follows the node count takes the grown graph's value or goes.  Nothing here can fail.
+// isl_index_remove moves its shrunk graph in the same way (`grown` is then the smaller one) and deals with the
+// entry seeds itself.
 void adopt_grown(isl_index* idx, isl_index* grown) {
   // host CSR (read back from the device on demand), levels, entry
   idx->host_csr_valid = grown->host_csr_valid;
@@ -797,7 +975,184 @@ void adopt_grown(isl_index* idx, isl_index* grown) {
   // buffers follow nq, k, ef, d and the wave count of a call, never the node count)
 }
 
+// The graph of `old` without the nodes `remap` marks kGone (include/islands_amd.h, isl_index_remove): repair over
+// the old ids on the builder's table, then compaction of lists and rows.  `old` (non-empty, resident rows, at
+// least one survivor) is only read; the shrunk graph leaves in `out`, built beside it, with the survivors' rows.
+isl_status shrink_flat(const isl_build_options& opts, const isl_index* old, const std::vector<uint32_t>& remap,
+                       const std::vector<uint32_t>& survivors, isl_index** out) {
+  using isl::fail;
+  const isl_leann_config cfg = old->cfg;
+  const uint64_t n0 = old->num_nodes, n = survivors.size();
+  const uint32_t m0 = (uint32_t)cfg.m0;
+  const isl::RowTable& rows = old->rows;
+  ISL_TRY(isl::use_device(old->device));
+  Scaffold c;  // the staging buffers alone: no construction graph
+  Table t{nullptr, nullptr, m0};
+  ISL_TRY(c.alloc(&t.ell, n0 * (m0 + 1), true));
+  ISL_TRY(c.alloc(&t.deg, n0, true));
+  uint32_t *d_flag = nullptr, *d_remap = nullptr, *d_surv = nullptr, *d_touched = nullptr;
+  unsigned long long* d_total = nullptr;
+  ISL_TRY(c.alloc(&d_flag, 4, true));  // [0] import, [1] touched nodes, [2] compaction
+  ISL_TRY(c.alloc(&d_total, 1, true));
+  ISL_TRY(c.alloc(&d_remap, n0));
+  ISL_TRY(c.alloc(&d_surv, n));
+  ISL_TRY(c.alloc(&d_touched, n0));
+  // every list returns to the table in its stored order: an untouched row is finished with that copy
+  ISL_TRY(c.csr_to_table(t, old->d_off, old->d_adj, old->nnz, n0, d_flag));
+  uint32_t flag = 0;
+  if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "importing the index's lists failed");
+  if (flag & 1u) return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the index has a list longer than m0 = %u", m0);
+  if (old->host_csr_valid && old->node_offsets.size() == n0 + 1 && old->node_offsets[n0] != old->nnz)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the device copy of the graph is not the lists verbatim (ids "
+                "repeated inside a list were removed at upload)");
+  if (flag & 4u) return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: a list names an id that is not below len = %llu",
+                             (unsigned long long)n0);
+  if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the index's offsets do not fit its lists");
+  // the CSR is in range from here on: the kernels below index by its ids
+  if (hipMemcpy(d_remap, remap.data(), n0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_surv, survivors.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "cannot upload the remap");
+  hipLaunchKernelGGL(touched_kernel, dim3((uint32_t)((n0 + 3) / 4)), dim3(256), 0, 0, old->d_off.get(), old->d_adj.get(),
+                     d_remap, n0, d_touched, d_flag + 1);
+  uint32_t touched = 0;
+  if (hipGetLastError() != hipSuccess || hipMemcpy(&touched, d_flag + 1, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "listing the touched nodes failed");
+  if (touched > n) return fail(ISL_ERR_DEVICE, "listing the touched nodes failed: %u of %llu survivors", touched,
+                               (unsigned long long)n);
+  const bool debug = getenv("ISL_DEBUG") != nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (debug && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
+  if (touched) {
+    RepairParams p{};
+    p.emb = rows.data(); p.norm2 = rows.norm2(); p.stride = rows.stride(); p.d = (uint32_t)rows.d();
+    p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
+    p.off = old->d_off; p.adj = old->d_adj; p.remap = d_remap; p.touched = d_touched;
+    p.ell = t.ell; p.deg = t.deg; p.W = m0 + 1; p.m0 = m0; p.total = d_total;
+    if (ev0) (void)hipEventRecord(ev0, 0);
+    launch_repair(cfg.metric, opts.select_rule == ISL_SELECT_DIVERSE, rows, touched, p);
+    if (ev1) (void)hipEventRecord(ev1, 0);
+    if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "repair launch failed");
+  }
+  // compaction: degrees of the survivors -> offsets (host scan, as table_to_csr), lists through the remap
+  std::vector<uint32_t> hdeg(n0);
+  if (hipMemcpy(hdeg.data(), t.deg, n0 * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "repair kernel failed");
+  if (debug) {
+    unsigned long long total = 0;
+    float ms = 0.0f;
+    (void)hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost);
+    if (touched && ev0) (void)hipEventElapsedTime(&ms, ev0, ev1);
+    fprintf(stderr, "[isl] isl_index_remove: %llu of %llu nodes removed, touched %u, candidates %llu, repair kernel "
+            "%.3f ms\n", (unsigned long long)(n0 - n), (unsigned long long)n0, touched, total, ms);
+  }
+  if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
+  std::vector<uint64_t> hoff(n + 1, 0);
+  for (uint64_t i = 0; i < n; ++i) hoff[i + 1] = hoff[i] + std::min(hdeg[survivors[i]], m0);
+  uint64_t* d_off = nullptr;
+  uint32_t* d_adj = nullptr;
+  ISL_TRY(c.alloc(&d_off, n + 1));
+  ISL_TRY(c.alloc(&d_adj, hoff[n]));
+  if (hipMemcpy(d_off, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "cannot upload the CSR offsets");
+  hipLaunchKernelGGL(table_to_csr_remap_kernel, dim3((uint32_t)((n0 + 3) / 4)), dim3(256), 0, 0, t.ell, t.deg, m0 + 1,
+                     d_remap, d_off, n0, d_adj, d_flag + 2);
+  if (hipGetLastError() != hipSuccess || hipMemcpy(&flag, d_flag + 2, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "CSR compaction failed");
+  if (flag) return fail(ISL_ERR_DEVICE, "isl_index_remove: a repaired list kept a removed id");
+  // rows and norms of the survivors, bit for bit, into a table of the same type (row_table.hpp has the layout)
+  isl::RowTable shrunk;
+  if (shrunk.allocate(rows.dtype(), n, rows.d()) != ISL_OK)
+    return fail(ISL_ERR_DEVICE, "hipMalloc failed for the rows of the shrunk index");
+  const uint64_t es = isl_rows::elem_size(rows.dtype());
+  if (hipMemset(shrunk.as<unsigned char>() + n * shrunk.stride() * es, 0, (size_t)(isl_rows::slack(rows.dtype()) * es)) !=
+      hipSuccess)
+    return fail(ISL_ERR_DEVICE, "hipMemset failed");
+  rows.with_row_type([&](auto row) {
+    using T = decltype(row);
+    hipLaunchKernelGGL(gather_survivor_rows_kernel<T>, dim3((uint32_t)n), dim3(256), 0, 0, rows.as<const T>(),
+                       rows.stride(), rows.norm2(), d_surv, shrunk.as<T>(), shrunk.norm2());
+  });
+  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "row compaction failed");
+  const std::vector<uint64_t> old_levels = old->levels.size() == n0 ? old->levels : std::vector<uint64_t>();
+  const isl_plan::Entry e = isl_plan::entry_after(old_levels, remap, survivors, old->has_entry, old->entry_point,
+                                                  old->max_level);
+  ISL_TRY(isl_index_from_device_csr(&cfg, old->device, n, d_off, d_adj, e.has ? 1 : 0, e.id, old->has_dimension ? 1 : 0,
+                                    old->dimension, &c.res));
+  c.res->max_level = e.max_level;
+  c.res->levels = isl_plan::levels_after(old_levels, survivors);
+  c.res->rows = std::move(shrunk);
+  c.res->nvec = n;
+  *out = c.res;
+  c.res = nullptr;
+  return ISL_OK;
+}
+
 }  // namespace
+
+extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* opts_in, const uint64_t* ids,
+                                       uint64_t n_ids, uint64_t* out_remap, uint64_t* out_len) {
+  using isl::fail;
+  if (!idx || (!ids && n_ids)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
+  isl_build_options opts;
+  isl_build_options_default(&opts);
+  if (opts_in) {
+    ISL_TRY(isl_build::check_build_options(opts_in, true));
+    opts = *opts_in;
+  }
+  const uint64_t n0 = idx->num_nodes;
+  if (n_ids == 0) {
+    if (out_remap)
+      for (uint64_t i = 0; i < n0; ++i) out_remap[i] = i;
+    if (out_len) *out_len = n0;
+    return ISL_OK;
+  }
+  if (idx->is_hnsw)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: this is the core index of an HnswGraph, which does not shrink");
+  if (idx->recompute)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: an index on the recompute provider does not give rows up");
+  uint64_t bad = 0;
+  if (isl_plan::first_unknown_id(ids, n_ids, n0, &bad)) return isl::fail_node(bad);
+  const isl::RowTable& old_rows = idx->rows;
+  if (idx->device < 0 || !idx->d_off || !old_rows.resident() || !old_rows.norm2() || old_rows.n() != n0 || idx->nvec != n0)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove needs the index's rows resident on the device "
+                "(isl_index_upload, isl_set_embeddings)");
+  if (idx->cfg.m0 > isl_plan::kMaxM0) return fail(ISL_ERR_UNSUPPORTED, "%s", isl_plan::shape_limit(idx->cfg.m0, 0, 0));
+  {  // the &mut self of the reference: not beside a search on the same handle
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (isl::any_lane_busy(idx))
+      return fail(ISL_ERR_SEARCH, "Search error: the index cannot shrink while searches are in flight");
+  }
+  std::vector<uint32_t> remap, survivors;
+  const uint64_t n = isl_plan::build_remap(n0, ids, n_ids, remap, survivors);
+  isl_index* shrunk = nullptr;
+  // every node gone: what isl_index_build_rows gives for n == 0 under the handle's config
+  if (n == 0) ISL_TRY(isl_index_new(&idx->cfg, &shrunk));
+  else ISL_TRY(shrink_flat(opts, idx, remap, survivors, &shrunk));
+  // the entry seeds that survive, under their new ids
+  std::vector<uint64_t> seeds;
+  for (uint64_t s : idx->seeds.ids)
+    if (s < n0 && remap[s] != isl_plan::kGone) seeds.push_back(remap[s]);
+  // the move: the shrunk graph was built beside the old one, which nothing has touched so far
+  {
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (isl::any_lane_busy(idx)) {
+      isl_index_free(shrunk);
+      return fail(ISL_ERR_SEARCH, "Search error: the index cannot shrink while searches are in flight");
+    }
+    adopt_grown(idx, shrunk);
+    idx->seeds = {};  // ids and row copies of the old numbering
+  }
+  isl_index_free(shrunk);  // what is left of it: the old graph's host vectors
+  // their rows are gathered again from the shrunk table; a table that cannot be made stays dropped, and a plain
+  // search then starts at the entry point: the graph, the rows and the remap stand either way
+  if (!seeds.empty() && isl_index_set_entry_seeds(idx, seeds.data(), seeds.size()) != ISL_OK) isl::last_error() = {};
+  if (out_remap)
+    for (uint64_t i = 0; i < n0; ++i) out_remap[i] = remap[i] == isl_plan::kGone ? ISL_REMOVED : (uint64_t)remap[i];
+  if (out_len) *out_len = n;
+  return ISL_OK;
+}
 
 extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const isl_build_options* opts_in,
                                            const void* vectors, int32_t dtype, uint64_t n, uint64_t d,

@@ -1,5 +1,5 @@
 """Build time and quality of the device graph builder (isl_index_build_rows) in its batched mode.
-    python tools/build_perf.py [build|insert] [--nodes N] [--dim D] [--batch B] [--dataset G|M] [--select reference|diverse]
+    python tools/build_perf.py [build|insert|remove] [--nodes N] [--dim D] [--batch B] [--dataset G|M] [--select reference|diverse]
                                [--alpha A] [--no-keep-pruned] [--ef 128,256] [--nq Q] [--check-truth]
                                [--row-dtype f32|bf16[,...]]
 Prints one JSON line per leg: build seconds, peak device memory during the build, recall@10 / evaluations /
@@ -13,7 +13,14 @@ problem, and the truth is the brute force over the widened rows.
 the first --ef): an index of N - K rows (--insert-rows K, default 65536) takes the last K rows in one call; a second
 copy of it takes them in --insert-calls calls (default 16); then one more row goes into that copy -- the fixed
 cost of a call -- and the one-call build of all N rows stands beside them.  One JSON line: seconds per call and
-rows/s, and recall@10 of the two grown graphs and of the one-call graph against isl_bruteforce_topk."""
+rows/s, and recall@10 of the two grown graphs and of the one-call graph against isl_bruteforce_topk.
+
+`remove` measures isl_index_remove (same defaults): K random rows (--insert-rows) leave an index of N rows in one
+call; a copy of it loses them in --insert-calls calls; one more row leaves that copy -- the fixed cost of a call.
+Beside them stand the one-call build of the survivors (the yardstick for time and for recall) and the same graph
+with the removed ids merely dropped from the lists.  A third copy repeats the one-call removal under ISL_DEBUG for
+the number of touched nodes, the sum of |C(p)| and the repair kernel's time, with the device's memory polled.  The
+truth is isl_bruteforce_topk over the survivors."""
 import argparse, json, os, sys, threading, time
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
 import numpy as np, torch
@@ -22,7 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import synth
 
 ap = argparse.ArgumentParser()
-ap.add_argument("mode", nargs="?", choices=["build", "insert"], default="build")
+ap.add_argument("mode", nargs="?", choices=["build", "insert", "remove"], default="build")
 ap.add_argument("--insert-rows", type=int, default=65536)
 ap.add_argument("--insert-calls", type=int, default=16)
 ap.add_argument("--nodes", type=int, default=1_000_000)
@@ -38,7 +45,8 @@ ap.add_argument("--qstart", type=int, default=0, help="dataset G: first row of t
 ap.add_argument("--row-dtype", default="f32", help="comma-separated legs, each f32 or bf16")
 ap.add_argument("--check-truth", action="store_true", help="also report how far torch's brute force agrees with the truth")
 args = ap.parse_args()
-inserting = args.mode == "insert"
+removing = args.mode == "remove"
+inserting = args.mode == "insert" or removing
 args.dataset = args.dataset or ("M" if inserting else "G")
 args.select = args.select or ("diverse" if inserting else "reference")
 args.nq = args.nq or (1024 if inserting else 512)
@@ -119,14 +127,125 @@ def insert_mode():
                          "one_call_build": recall_at_10(whole, ef)}}), flush=True)
 
 
-if inserting:
-    insert_mode()
-    sys.exit(0)
-
-
 def used_bytes():
     free, total = torch.cuda.mem_get_info(0)  # hipMemGetInfo: the whole device, whoever allocated
     return total - free
+
+
+def remove_mode():
+    import re, tempfile
+    global ti
+    K, calls = args.insert_rows, args.insert_calls
+    if legs != ["f32"] or not 0 < K < N or K % calls:
+        ap.error("remove: f32 rows, 0 < --insert-rows < --nodes, a multiple of --insert-calls")
+    ef = int(args.ef.split(",")[0])
+    kw = dict(batch=args.batch, select=args.select, alpha=args.alpha, keep_pruned=not args.no_keep_pruned)
+    rule = dict(select=args.select, alpha=args.alpha, keep_pruned=not args.no_keep_pruned)
+    gone = np.sort(np.random.default_rng(7).choice(N, K, replace=False)).astype(np.uint64)
+    mask = np.ones(N, bool)
+    mask[gone] = False
+    xs = np.ascontiguousarray(xh[mask])
+    xd = torch.from_numpy(xs).to(dev)
+    ti = synth.brute_force_topk_native(xd, q, 10)[0].cpu().numpy()  # the truth over the survivors, in their new ids
+    del xd
+    torch.cuda.empty_cache()
+
+    def timed(f):
+        t = time.time()
+        r = f()
+        return r, time.time() - t
+
+    def copy_of(blob, rows):
+        return ia.LeannIndex.from_bytes(blob).upload(0).set_embeddings(rows)
+
+    scratch, scratch_s = timed(lambda: ia.LeannIndex.build(xs, cfg, **kw))
+    recall_scratch = recall_at_10(scratch, ef)
+    del scratch
+    one, whole_s = timed(lambda: ia.LeannIndex.build(xh, cfg, **kw))
+    blob = one.to_bytes()
+    # the old graph with the removed ids merely dropped from the lists
+    remap0 = np.full(N, -1, np.int64)
+    remap0[mask] = np.arange(N - K)
+    lists = [one.get_neighbors(int(p)) for p in np.flatnonzero(mask)]
+    touched_host = sum(1 for r in lists if r.size and (remap0[r.astype(np.int64)] < 0).any())
+    kept = [remap0[r.astype(np.int64)] for r in lists]
+    kept = [r[r >= 0].astype(np.uint64) for r in kept]
+    off = np.zeros(N - K + 1, np.uint64)
+    off[1:] = np.cumsum([r.size for r in kept])
+    g = ia.CsrGraph(node_offsets=off, neighbors=np.concatenate(kept), levels=np.zeros(N - K, np.uint64),
+                    entry_point=max(int(remap0[one.entry_point]), 0), num_nodes=N - K,
+                    degree_counts=np.diff(off.astype(np.int64)).astype(np.uint64))
+    dropped = ia.LeannIndex.from_csr(g, cfg, dimension=d).upload(0).set_embeddings(xs)
+    recall_dropped = recall_at_10(dropped, ef)
+    del dropped, lists, kept, g
+    remap, one_s = timed(lambda: one.remove(gone, **rule))
+    assert len(one) == N - K and (remap[mask] == np.arange(N - K, dtype=np.uint64)).all()
+    recall_one = recall_at_10(one, ef)
+    del one
+    many = copy_of(blob, xh)
+    step, per_call, left = K // calls, [], gone.copy()
+    for c in range(calls):
+        r, dt = timed(lambda: many.remove(left[:step], **rule))
+        left = r[left[step:]]  # the ids still to go, in the numbering the call left
+        per_call.append(round(dt, 3))
+    assert len(many) == N - K
+    recall_many = recall_at_10(many, ef)
+    _, single_s = timed(lambda: many.remove([(N - K) // 2], **rule))
+    del many
+    # once more under ISL_DEBUG (read by the call itself), stderr to a file, the device's memory polled
+    dbg = copy_of(blob, xh)
+    before, peak, stop = used_bytes(), [0], threading.Event()
+
+    def poll():
+        while not stop.is_set():
+            peak[0] = max(peak[0], used_bytes())
+            time.sleep(0.005)
+
+    th = threading.Thread(target=poll, daemon=True)
+    th.start()
+    with tempfile.TemporaryFile() as f:
+        sys.stderr.flush()
+        saved = os.dup(2)
+        os.dup2(f.fileno(), 2)
+        os.environ["ISL_DEBUG"] = "1"
+        try:
+            dbg.remove(gone, **rule)
+        finally:
+            del os.environ["ISL_DEBUG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        stop.set()
+        th.join()
+        f.seek(0)
+        text = f.read().decode(errors="replace")
+    m = re.search(r"touched (\d+), candidates (\d+), repair kernel ([0-9.]+) ms", text)
+    touched, cands, kernel_ms = (int(m.group(1)), int(m.group(2)), float(m.group(3))) if m else (None, None, None)
+    after = used_bytes()
+    del dbg
+    row_bytes = None if not m else cands * d * 4
+    print(json.dumps({
+        "what": "build_perf remove", "dataset": args.dataset, "nodes": N, "dim": d, "batch": args.batch,
+        "select": args.select, "alpha": args.alpha, "keep_pruned": not args.no_keep_pruned, "m0": cfg.m0,
+        "ef_construction": cfg.ef_construction, "removed_rows": K, "build_all_s": round(whole_s, 2),
+        "one_call": {"seconds": round(one_s, 3), "rows_per_s": round(K / one_s)},
+        "many_calls": {"calls": calls, "rows_per_call": step, "seconds_per_call": per_call,
+                       "seconds": round(sum(per_call), 3), "rows_per_s": round(K / sum(per_call))},
+        "one_row_call_s": round(single_s, 3),
+        "one_call_build_of_survivors": {"seconds": round(scratch_s, 2), "nodes_per_s": round((N - K) / scratch_s)},
+        "queries": nq, "ef": ef,
+        "recall_at_10": {"repaired_one_call": recall_one, "repaired_many_calls": recall_many,
+                         "build_of_survivors": recall_scratch, "removed_ids_merely_dropped": recall_dropped},
+        "touched_nodes": touched, "touched_nodes_counted_on_host": touched_host, "sum_candidates": cands,
+        "mean_candidates": None if not touched else round(cands / touched, 2),
+        "repair_kernel_ms": kernel_ms, "repair_row_bytes": row_bytes,
+        "repair_row_gbytes_per_s": None if not kernel_ms else round(row_bytes / kernel_ms / 1e6, 1),
+        "device_bytes_before": before, "device_bytes_peak_in_remove": max(peak[0], before),
+        "device_bytes_after": after}), flush=True)
+
+
+if inserting:
+    remove_mode() if removing else insert_mode()
+    sys.exit(0)
 
 
 for leg in legs:
