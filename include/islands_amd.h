@@ -393,7 +393,23 @@ isl_status isl_search_batch_device(const isl_index* idx, const float* d_queries,
  * encoder gets fuller passes (Searcher::search_batch, search.rs:179-181, hands batches over one by one;
  * how they are batched on the device is the library's business).  Each call's answers, status and
  * counters are its own (recompute_rounds / encoded_nodes of its statistics are the shared rounds'); if
- * the union fails, every member is run by itself and gets its own error. */
+ * the union fails, every member is run by itself and gets its own error.
+ *
+ * In-memory provider: a call of this form that finds the chip full -- at least as many queries of the
+ * index in flight as the call's launch has resident waves -- is HELD, not enqueued: a process has only a
+ * few hardware queues (GPU_MAX_HW_QUEUES, 4 unless set before HIP starts), in one queue the next call's
+ * kernel starts only when the previous call's slowest query has finished, so the call would wait on the
+ * device anyway.  Held calls that agree in d, k and ef go out TOGETHER as one launch over the union of
+ * their queries: when they reach ISL_GROUP_CAP queries (default 4096), at the next entry into the library
+ * that finds room (another call of this form, isl_search_wait[_stats], isl_search_stream_wait), or when
+ * one of them is waited for.  Each call keeps its token, its output buffers, its status and its counters;
+ * kernel_ms of its statistics is then the shared launch's.  Calls are held only in a process that had
+ * GPU_MAX_HW_QUEUES below 8 in its environment when the library was loaded (or none: HIP's default is 4);
+ * with more queues every call is enqueued at once, as ISL_NO_GROUP=1 makes it everywhere (ISL_NO_GROUP=0:
+ * held whatever the queues).  A caller that wants a call started at once leaves room or sets
+ * ISL_NO_GROUP=1 (read, like ISL_GROUP_CAP and ISL_GROUP_ROOM, when the index handle is created).
+ * Recompute provider, two-level search, HnswGraph, host-buffer calls and runs with
+ * ISL_TIMELINE / ISL_DEBUG keep one launch per call. */
 isl_status isl_search_batch_device_async(const isl_index* idx, const float* d_queries, uint64_t nq,
                                          uint64_t d, uint64_t k, uint64_t ef, uint64_t* d_out_ids,
                                          float* d_out_dist, uint32_t* d_out_count, void* stream,
@@ -408,6 +424,11 @@ isl_status isl_search_wait(const isl_index* idx, uint64_t token);
  * shard exchange of a multi-GPU search issues its all-gather behind this -- while the host keeps
  * submitting.  The call still has to be completed with isl_search_wait[_stats]. */
 isl_status isl_search_stream_wait(const isl_index* idx, uint64_t token, void* stream);
+/* How the asynchronous device-pointer calls of this index went out so far: launches submitted by the
+ * group path, those of them that served several calls, and the calls those served.  Zeros for an index
+ * no such call has reached.  Any of the pointers may be NULL. */
+isl_status isl_index_group_counters(const isl_index* idx, uint64_t* launches, uint64_t* shared_launches,
+                                    uint64_t* shared_calls);
 /* LeannIndex::search, leann.rs:858-865: one query, ef = config.ef_search. */
 isl_status isl_search(const isl_index* idx, const float* query, uint64_t d, uint64_t k,
                       uint64_t* out_ids, float* out_dist, uint32_t* out_count);

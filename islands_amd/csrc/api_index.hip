@@ -95,7 +95,15 @@ using namespace isl;
 // Up to kSearchLanes searches overlap on their own streams; the runtime's default of 4 hardware
 // queues per process would make them share queues and serialise.  Effective when the library is
 // loaded before the HIP runtime initialises (an explicit setting in the environment wins).
-__attribute__((constructor)) static void isl_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "32", 0); }
+static int g_hw_queues_at_load = 4;
+__attribute__((constructor)) static void isl_default_hw_queues() {
+  if (const char* e = getenv("GPU_MAX_HW_QUEUES")) {
+    const int v = atoi(e);
+    if (v > 0) g_hw_queues_at_load = v;
+  }
+  setenv("GPU_MAX_HW_QUEUES", "32", 0);
+}
+int isl::hw_queues_at_load() { return g_hw_queues_at_load; }
 
 extern "C" {
 
@@ -262,6 +270,7 @@ void isl_index_free(isl_index* idx) {
   if (idx->device >= 0) {
     (void)hipSetDevice(idx->device);
     join_lane_workers(idx);
+    if (idx->group) free_group_state(idx);  // (held calls go out first: their lanes are drained below)
     for (auto& w : idx->ws)
       if (w.busy && w.st_inflight) (void)hipStreamSynchronize(w.st_inflight);
     for (auto& w : idx->ws) free_workspace(w);  // (their events)

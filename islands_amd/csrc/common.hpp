@@ -4,8 +4,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
+#include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <atomic>
@@ -151,9 +153,50 @@ struct SearchWorkspace {
   uint64_t alloc_events = 0;
   uint64_t alloc_mark = 0;       // alloc_events when the call in flight was claimed
   isl_search_stats stats{};      // statistics of the call that finished last on this lane
+  // ---- grouped launches (search_group.hip) ----
+  // A lane whose call went in through the group path (all under the group state's mutex until the call's wait
+  // has passed group_before_wait):
+  bool grp = false;                        // the call is the group state's: held, or a member of a launch
+  SearchWorkspace* grp_launch = nullptr;   // the group workspace whose launch answers it (NULL: held, or alone on this lane)
+  uint32_t grp_offset = 0;                 // its first query in that launch's union
+  hipEvent_t grp_ready = nullptr;          // recorded behind the last kernel that writes the call's outputs
+  uint64_t grp_allocs = 0;                 // what the launch's workspace had to set up (isl_search_stats::allocations)
+  bool grp_failed = false;                 // the launch could not be enqueued: the wait returns grp_status / grp_error
+  isl_status grp_status = ISL_OK;
+  ErrorRecord grp_error;
+  // A group workspace (never one of isl_index::ws):
+  int32_t pool_lane = -1;                  // which stream of the device's pool it runs on (a lane: its own index)
+  bool union_launch = false;               // search_enqueue leaves publishing to the group's scatter kernel
+  PinnedBuffer<uint64_t> h_members;        // member table of the launch in flight, read by the gather / scatter kernels
+  DeviceBuffer<uint32_t> grp_scratch;      // per-member counts and the scatter kernel's block counters (zero between launches)
 };
 
 constexpr int kSearchLanes = 32;  // independent workspaces = searches that may be in flight (on <= 16 pooled streams)
+
+// GPU_MAX_HW_QUEUES as the process had it when the library was loaded; HIP's own default, 4, when it had none
+// (api_index.hip: what the library sets itself at load comes too late once HIP has started, and cannot be told apart)
+int hw_queues_at_load();
+// Calls wait for company only where the hardware queues are the bottleneck.  With 32 queues the dispatcher
+// already is the queue and holding calls back costs 2-7 % (profiles/search_group_ab.json, 32-queue leg); with four
+// it gains 35-40 %.  Measured at 4 and at 32 only; in between, eight queues hold the eight launches that
+// overlap at 32, so grouping is on below eight.
+constexpr int kGroupBelowQueues = 8;
+// ISL_NO_GROUP=1: no call waits for company (one launch per call, as before the group path existed), =0: calls do
+// whatever the queues are, unset: by the queues; ISL_GROUP_CAP=<queries>: the most one launch takes;
+// ISL_GROUP_ROOM=<queries>: stands in for the resident waves in "is there room on the chip" (small tests force
+// holding with it).  0 = not set.
+struct GroupSwitches { bool off; uint32_t cap, room; };
+inline GroupSwitches group_switches() {
+  auto num = [](const char* name) -> uint32_t {
+    const char* e = getenv(name);
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (uint32_t)std::min<long long>(v, 0x7FFFFFFF) : 0u;
+  };
+  const char* off = getenv("ISL_NO_GROUP");
+  const bool is_off = (off && *off) ? strcmp(off, "0") != 0 : hw_queues_at_load() >= kGroupBelowQueues;
+  return GroupSwitches{is_off, num("ISL_GROUP_CAP"), num("ISL_GROUP_ROOM")};
+}
+struct GroupState;  // search_group.hip
 
 // Scratch of the heap-exact kernel, ONE pool per index shared by every lane: a workgroup that
 // finds work in its redo queue claims a free slot (lock word per slot), so concurrent searches
@@ -275,6 +318,12 @@ struct isl_index {
   mutable isl::SearchWorkspace ws[isl::kSearchLanes];
   mutable isl::ExactPool pool;
   mutable uint64_t next_token = 1;
+  // grouped launches of asynchronous device-pointer calls (search_group.hip; rules: search_group_plan.hpp).
+  // The switches are read when the handle is created; the state comes with the first such call or with
+  // isl_index_prepare and goes with the handle.
+  const isl::GroupSwitches group_sw = isl::group_switches();
+  mutable std::mutex group_mu;              // guards `group` and everything in it; never taken under `mu`
+  mutable isl::GroupState* group = nullptr;
 };
 
 // HnswGraph handle (hnsw.hip, hnsw_build.hip).
@@ -327,6 +376,9 @@ void free_exact_pool(ExactPool& pool);
 bool any_lane_busy(const isl_index* idx);
 // joins the host threads of asynchronous calls still running on the index's lanes (isl_index_free)
 void join_lane_workers(const isl_index* idx);
+// search_group.hip (isl_index_free, where idx->group is set): submits what is held, drains the group workspaces'
+// streams and frees the state
+void free_group_state(isl_index* idx);
 // Builds the padded adjacency (64 ids per node + degrees) the traversal reads; under idx->mu.
 isl_status ensure_padded_adjacency(isl_index* idx);
 // hnsw.hip -- HnswConfig::validate (hnsw.rs:72-85) and the metric's range

@@ -112,7 +112,8 @@ hipStream_t pool_stream(int32_t device, uint32_t lane, bool* created) {
 isl_status isl_lane::ensure_lane_stream(const isl_index* idx, isl::SearchWorkspace& ws) {
   if (ws.stream) return ISL_OK;
   bool created = false;
-  hipStream_t st = pool_stream(idx->device, (uint32_t)(&ws - idx->ws), &created);
+  // (a group workspace is not one of idx->ws: it names its pool stream itself)
+  hipStream_t st = pool_stream(idx->device, ws.pool_lane >= 0 ? (uint32_t)ws.pool_lane : (uint32_t)(&ws - idx->ws), &created);
   if (!st) return isl::fail(ISL_ERR_DEVICE, "hipStreamCreate failed for a search lane");
   if (created) ws.alloc_events++;
   if (!ws.ev_done) { ISL_HIP(hipEventCreateWithFlags(&ws.ev_done, hipEventDisableTiming)); ws.alloc_events++; }
@@ -132,10 +133,8 @@ void isl_lane::copy_words(const uint32_t* src, uint32_t* dst, uint64_t n, uint32
   hipLaunchKernelGGL(copy_u32_kernel, dim3(grid), dim3(block), 0, st, src, dst, n);
 }
 
-namespace {
-
-isl_status prepare_workspace(const isl_index* idx, isl::SearchWorkspace& ws, uint32_t nq, uint32_t slots,
-                             uint32_t plog_cap) {
+isl_status isl_lane::prepare_workspace(const isl_index* idx, isl::SearchWorkspace& ws, uint32_t nq, uint32_t slots,
+                                       uint32_t plog_cap) {
   ISL_TRY(ensure_lane_stream(idx, ws));
   uint64_t* const ev = &ws.alloc_events;
   const uint64_t cap = nq < 1024 ? 1024 : nq;  // the per-query arrays' floor
@@ -167,6 +166,8 @@ isl_status prepare_workspace(const isl_index* idx, isl::SearchWorkspace& ws, uin
   ISL_TRY(ws.qsel_h.reserve(cap, ev));
   return ws.plog.reserve(ws.status.capacity() * plog_cap, ev);
 }
+
+namespace {
 
 // Staging of the host-pointer entry points: device buffers + pinned host mirrors.
 isl_status prepare_host_staging(isl::SearchWorkspace& ws, uint64_t nq, uint64_t d, uint64_t k) {
@@ -298,8 +299,8 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     if (idx->d_ell != before) ws.alloc_events += 2;
   }
   hipStream_t st = call_stream(ws, c);
-  if (c.mode == StreamMode::OWN_AFTER_USER) {
-    ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));
+  if (c.mode == StreamMode::OWN_AFTER_USER || c.mode == StreamMode::OWN_AFTER_EVENT) {
+    if (c.mode == StreamMode::OWN_AFTER_USER) ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));
     ISL_HIP(hipStreamWaitEvent(ws.stream, ws.ev_in, 0));
   }
 
@@ -516,9 +517,11 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   ws.st_inflight = st;
   if (warm) return ISL_OK;
 
-  ISL_TRY(publish(ws, nq, k, st));
-  // the call's own completion event: lanes may share a stream, and a caller's stream carries its other work
-  ISL_HIP(hipEventRecord(ws.ev_done, st));
+  if (!ws.union_launch) {  // (a group launch: its scatter kernel publishes per member, search_group.hip)
+    ISL_TRY(publish(ws, nq, k, st));
+    // the call's own completion event: lanes may share a stream, and a caller's stream carries its other work
+    ISL_HIP(hipEventRecord(ws.ev_done, st));
+  }
   ws.enqueued = true;
   ws.nq_inflight = nq;
   ws.k_inflight = k;
@@ -566,13 +569,15 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
   ws.enqueued = false;
   const uint64_t nq = ws.nq_inflight;
   const bool use_fast = ws.fast_inflight;
-  ISL_HIP(hipEventSynchronize(ws.ev_done));
+  // a member of a group launch: that launch's events (the scatter kernel has filled this lane's mirrors)
+  const isl::SearchWorkspace& lw = ws.grp_launch ? *ws.grp_launch : ws;
+  ISL_HIP(hipEventSynchronize(lw.ev_done));
   const uint32_t* status = ws.h_status;
   const uint32_t* ctr = ws.h_ctr;
   const uint32_t* head = ws.h_head;
   isl::DeviceBuffer<uint64_t> d_prof = std::move(ws.d_prof);
   float ms = 0.0f;
-  (void)hipEventElapsedTime(&ms, ws.ev0, ws.ev1);
+  (void)hipEventElapsedTime(&ms, lw.ev0, lw.ev1);
 
   isl_search_stats& ss = ws.stats;
   ss = isl_search_stats{};
@@ -580,7 +585,7 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
   ss.exact_path = head[1];
   ss.replayed = head[3];
   ss.kernel_ms = ms;
-  ss.allocations = ws.alloc_events - ws.alloc_mark;
+  ss.allocations = ws.alloc_events - ws.alloc_mark + ws.grp_allocs;
   for (uint64_t i = 0; i < nq; i++) {
     ss.expansions += ctr[i * 4 + 0];
     ss.edges += ctr[i * 4 + 1];
@@ -654,7 +659,8 @@ isl_status isl_lane::search_statuses(isl::SearchWorkspace& ws, uint64_t nq) {
     if (status[i] == QS_OK) continue;
     if (status[i] == QS_NODE_NOT_FOUND) {
       uint64_t node = 0;
-      ISL_HIP(hipMemcpy(&node, ws.payload + i, 8, hipMemcpyDeviceToHost));
+      const uint64_t* payload = ws.grp_launch ? ws.grp_launch->payload + ws.grp_offset : ws.payload;
+      ISL_HIP(hipMemcpy(&node, payload + i, 8, hipMemcpyDeviceToHost));
       return isl::fail_node(node);
     }
     if (status[i] == QS_SCRATCH)
@@ -767,6 +773,7 @@ isl::SearchWorkspace* claim_lane(const isl_index* idx) {
       w.alloc_mark = w.alloc_events;
       w.u_ids = nullptr; w.u_dist = nullptr; w.u_count = nullptr;
       w.publish_results = false;
+      w.grp = false; w.grp_launch = nullptr; w.grp_offset = 0; w.grp_allocs = 0; w.grp_failed = false;
       return &w;
     }
   return nullptr;
@@ -965,7 +972,10 @@ isl_status poison_failed_queries(const isl_index* idx, uint64_t token, uint32_t*
   {
     std::lock_guard<std::mutex> lock(idx->mu);
     for (auto& w : idx->ws)
-      if (w.busy && w.token == token) { status = w.status; break; }
+      if (w.busy && w.token == token) {
+        status = w.grp_launch ? w.grp_launch->status + w.grp_offset : w.status;  // (a member of a group launch)
+        break;
+      }
   }
   if (!status) return fail(ISL_ERR_INVALID_ARGUMENT, "unknown or already completed search token");
   hipLaunchKernelGGL(poison_failed_kernel, dim3((uint32_t)((nq + 255) / 256)), dim3(256), 0, stream, status, d_counts,
@@ -1061,6 +1071,9 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
     for (int i = 0; i < lanes; ++i) ISL_HIP(hipStreamSynchronize(idx->ws[i].stream));
   }
   for (int i = 0; i < lanes; ++i) idx->ws[i].alloc_mark = idx->ws[i].alloc_events;
+  // the group workspaces beside the lanes (calls that find the chip full share launches: search_group.hip)
+  ISL_TRY(group_prepare(idx, max_nq, max_ef, max_k, lanes,
+                        (uint32_t)(isl::device_cu_count(idx->device) * kMaxWavesPerCu), cg_max.plog_cap));
   return ISL_OK;
 }
 
@@ -1092,6 +1105,8 @@ static isl_status search_batch_device_async(const isl_index* idx, SearchCall c, 
     ISL_TRY(start_worker(idx, ws, [=]() {
       return idx->recompute ? recompute_coalesced(idx, *ws, c) : search_sync(idx, *ws, c);
     }));
+  } else if (group_takes(idx, c)) {
+    ISL_TRY(group_arrive(idx, *ws, c));  // submitted now, or held for company (search_group_plan.hpp)
   } else {
     c.mode = StreamMode::OWN_AFTER_USER;
     ISL_TRY(search_enqueue(idx, *ws, c));
@@ -1158,7 +1173,15 @@ isl_status isl_search_wait_stats(const isl_index* idx, uint64_t token, isl_searc
   if (!ws) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "unknown or already completed search token");
   LaneGuard guard{idx, ws};
   isl_status st = ISL_OK;
-  if (!join_worker(*ws, &st)) st = search_finish(idx, *ws);  // the D2H result copies sit on the same stream
+  const bool grouped = ws->grp;
+  if (grouped) {  // a held call goes out now; whatever else the rules release goes with this entry
+    st = group_before_wait(idx, *ws);
+    if (st == ISL_OK) st = search_finish(idx, *ws);
+    group_after_wait(idx, *ws);
+  } else {
+    group_pump(idx);
+    if (!join_worker(*ws, &st)) st = search_finish(idx, *ws);  // the D2H result copies sit on the same stream
+  }
   if (st == ISL_OK && ws->u_count) host_copy_out(*ws, ws->nq_inflight, ws->k_inflight, ws->u_ids, ws->u_dist, ws->u_count);
   if (stats) *stats = ws->stats;
   note_last_stats(idx, ws->stats);
@@ -1172,10 +1195,12 @@ isl_status isl_search_stream_wait(const isl_index* idx, uint64_t token, void* st
   if (token == 0) return ISL_OK;
   ISL_TRY(isl::use_device(idx->device));
   isl::SearchWorkspace* found = nullptr;
+  isl::SearchWorkspace* grouped = nullptr;
   {
     std::lock_guard<std::mutex> lock(idx->mu);
     for (auto& w : idx->ws)
       if (w.busy && w.token == token) {
+        if (w.grp) { grouped = &w; break; }
         if (!w.threaded) {
           ISL_HIP(hipStreamWaitEvent((hipStream_t)stream, w.ev1, 0));  // recorded behind the last search kernel
           return ISL_OK;
@@ -1186,6 +1211,12 @@ isl_status isl_search_stream_wait(const isl_index* idx, uint64_t token, void* st
         w.waiting = true;  // (keeps isl_search_wait of another thread off the lane while we join)
         break;
       }
+  }
+  if (grouped) {
+    // a call of the group path: submitted now if it is still held (its enqueue status stays with the lane for
+    // isl_search_wait); `stream` then waits for the last kernel that writes its outputs
+    if (group_before_wait(idx, *grouped) == ISL_OK) ISL_HIP(hipStreamWaitEvent((hipStream_t)stream, grouped->grp_ready, 0));
+    return ISL_OK;
   }
   if (!found) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "unknown or already completed search token");
   // a call that runs on a worker thread (recompute provider, two-level search): its kernels are
