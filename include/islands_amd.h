@@ -58,8 +58,9 @@ enum {
 enum { ISL_METRIC_COSINE = 0, ISL_METRIC_EUCLIDEAN = 1, ISL_METRIC_DOT = 2, ISL_METRIC_MANHATTAN = 3 };
 /* PruningStrategy, src/core/leann.rs:168-178. */
 enum { ISL_PRUNE_GLOBAL = 0, ISL_PRUNE_LOCAL = 1, ISL_PRUNE_PROPORTIONAL = 2 };
-/* Row element types accepted by isl_set_embeddings. */
-enum { ISL_DTYPE_F32 = 0, ISL_DTYPE_BF16 = 1 };
+/* Row element types accepted by isl_set_embeddings.  ISL_DTYPE_FP8_E4M3: one byte per element, OCP e4m3fn
+ * (isl_set_embeddings_fp8); the builders, isl_index_insert and the encoder take F32 and BF16 only. */
+enum { ISL_DTYPE_F32 = 0, ISL_DTYPE_BF16 = 1, ISL_DTYPE_FP8_E4M3 = 2 };
 /* Where a caller's buffer lives. */
 enum { ISL_MEM_HOST = 0, ISL_MEM_DEVICE = 1 };
 
@@ -318,6 +319,27 @@ isl_status isl_index_upload(isl_index* idx, int32_t device);
  * builder, isl_select_neighbors and the distance / PQ entry points take f32.) */
 isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
                               int32_t dtype, int32_t mem);
+
+/* The same provider over fp8 rows: `codes` holds n x d bytes, each an OCP e4m3fn code (1 sign bit, 4 exponent
+ * bits with bias 7, 3 mantissa bits; subnormals m * 2^-9, largest value 448, 0x7F and 0xFF are NaN, no
+ * infinities -- not the fnuz encoding), and the table carries one power-of-two scale: the provider's vector
+ * element of code c is e4m3(c) * 2^scale_exp, an exact float32.  A quarter of the HBM bytes of float32 rows per
+ * visited node.  The arithmetic stays the reference's f32 chain over those images (queries stay float32), so
+ * results equal the reference's on them: ids, distance bits, counters.  A NaN code is a NaN element; the upload
+ * does not look for them.  Checks are those of isl_set_embeddings in the same order; scale_exp outside
+ * [-32, 32] -> ISL_ERR_INVALID_ARGUMENT before any device call; the HnswGraph facade -> ISL_ERR_UNSUPPORTED.
+ * isl_set_embeddings(..., ISL_DTYPE_FP8_E4M3, ...) is this call with scale_exp = 0.
+ * Every plain search form runs over fp8 rows.  An index that holds them refuses, with ISL_ERR_UNSUPPORTED and
+ * before any launch: isl_index_insert, isl_index_remove, isl_index_select_entry_seeds,
+ * isl_index_set_entry_seeds (count > 0), isl_index_pick_entries and the two-level searches.  Attaching the
+ * rows drops the entry seeds, as every provider swap does. */
+isl_status isl_set_embeddings_fp8(isl_index* idx, const void* codes, uint64_t n, uint64_t d, int32_t scale_exp,
+                                  int32_t mem);
+
+/* What the index's in-memory rows cost: their stored type (ISL_DTYPE_*), the scale exponent (0 unless fp8) and
+ * the bytes of the row block in HBM (rows at their 16-byte-aligned pitch plus 1 KiB of slack).  Any out
+ * pointer may be NULL.  No resident rows (none attached, or the recompute provider) -> ISL_DTYPE_F32, 0, 0. */
+isl_status isl_index_row_storage(const isl_index* idx, int32_t* dtype, int32_t* scale_exp, uint64_t* block_bytes);
 
 /* ---- search ---- */
 /* Work counters of one search call (summed over the batch): the inputs of the roofline formula

@@ -225,6 +225,19 @@ class LeannIndex {
   void attach(const InMemoryEmbeddingProvider& p) {
     check(isl_set_embeddings(h_, p.embeddings.data(), p.len(), p.dim, ISL_DTYPE_F32, ISL_MEM_HOST));
   }
+  // fp8 rows: n x d OCP e4m3fn codes under one power-of-two scale (host memory, or the index's device with
+  // mem = ISL_MEM_DEVICE); the provider's vectors are the exact f32 images e4m3(c) * 2^scale_exp
+  void set_embeddings_fp8(const uint8_t* codes, uint64_t n, uint64_t d, int32_t scale_exp = 0,
+                          int32_t mem = ISL_MEM_HOST) {
+    check(isl_set_embeddings_fp8(h_, codes, n, d, scale_exp, mem));
+  }
+  // what the in-memory rows cost: stored type (ISL_DTYPE_*), scale exponent (fp8), bytes of the row block in HBM
+  struct RowStorage { int32_t dtype; int32_t scale_exp; uint64_t block_bytes; };
+  RowStorage row_storage() const {
+    RowStorage s{};
+    check(isl_index_row_storage(h_, &s.dtype, &s.scale_exp, &s.block_bytes));
+    return s;
+  }
   // recompute mode: EmbeddingProvider backed by the encoder (leann.rs:82-99); the embedder is
   // borrowed and must outlive the index
   void attach_recompute(isl_encoder* enc, const std::vector<uint16_t>& tokens, uint64_t n, uint64_t L,

@@ -25,6 +25,7 @@ __all__ = [
     "bruteforce_topk", "merge_topk", "merge_service",
     "device_count", "HnswGraph", "SearchConfig", "Searcher", "MultiIndexSearcher",
     "mean_pool_normalize", "service_search", "BertConfig", "CandleEmbedder", "IndexMetadata",
+    "fp8_e4m3_to_f32", "quantize_fp8_e4m3",
 ]
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -75,6 +76,77 @@ def _f32(a):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# ------------------------------------------------------------------ fp8 rows
+DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3 = 0, 1, 2  # ISL_DTYPE_*
+FP8_E4M3_MAX = 448.0
+FP8_MIN_SCALE_EXP, FP8_MAX_SCALE_EXP = -32, 32
+
+
+def _fp8_e4m3_table() -> np.ndarray:
+    """The 256 values of OCP e4m3fn from the format's definition: 1 sign bit, 4 exponent bits with bias 7,
+    3 mantissa bits; exponent field 0 is subnormal (m * 2^-9); 0x7F and 0xFF are NaN; no infinities."""
+    t = np.empty(256, dtype=np.float32)
+    for c in range(256):
+        e, m = (c >> 3) & 15, c & 7
+        if e == 15 and m == 7:
+            v = float("nan")
+        elif e == 0:
+            v = m * 2.0 ** -9
+        else:
+            v = (8 + m) * 2.0 ** (e - 10)
+        t[c] = -v if c & 0x80 else v
+    return t
+
+
+_FP8_E4M3 = _fp8_e4m3_table()
+
+
+def _check_scale_exp(scale_exp: int) -> int:
+    e = int(scale_exp)
+    if not FP8_MIN_SCALE_EXP <= e <= FP8_MAX_SCALE_EXP:
+        raise ValueError(f"scale_exp = {e} is outside [{FP8_MIN_SCALE_EXP}, {FP8_MAX_SCALE_EXP}]")
+    return e
+
+
+def fp8_e4m3_to_f32(codes, scale_exp: int = 0) -> np.ndarray:
+    """The exact float32 images e4m3(c) * 2^scale_exp of fp8 codes (uint8, any shape): the vectors an index
+    with these rows attached (LeannIndex.set_embeddings_fp8) searches over."""
+    e = _check_scale_exp(scale_exp)
+    c = np.asarray(codes)
+    if c.dtype != np.uint8:
+        raise TypeError("fp8 codes are uint8")
+    return np.ldexp(_FP8_E4M3[c], e).astype(np.float32)
+
+
+def quantize_fp8_e4m3(rows_f32):
+    """float32 values -> (codes uint8 of the same shape, scale_exp).  scale_exp is the smallest exponent in
+    [-32, 32] with max|x| * 2^-scale_exp <= 448; a code is x * 2^-scale_exp rounded to the nearest e4m3 value,
+    ties to the even code; magnitudes above 448 * 2^scale_exp saturate to +-448.  A NaN raises ValueError."""
+    x = np.asarray(rows_f32, dtype=np.float32)
+    if np.isnan(x).any():
+        raise ValueError("quantize_fp8_e4m3: NaN in the input")
+    a = np.abs(x.astype(np.float64))
+    top = float(a.max()) if a.size else 0.0
+    e = FP8_MIN_SCALE_EXP
+    while e < FP8_MAX_SCALE_EXP and top > FP8_E4M3_MAX * 2.0 ** e:  # (both sides exact in float64)
+        e += 1
+    y = np.minimum(np.ldexp(a, -e), FP8_E4M3_MAX)  # exact: a power-of-two multiple of a float32
+    # the spacing of e4m3 at y: 2^(E - 3) in the binade 2^E, 2^-9 below 2^-6 (the subnormals)
+    _, ex = np.frexp(y)  # y = m * 2^ex, m in [0.5, 1)
+    step = np.maximum(ex - 1, -6) - 3
+    q = np.rint(np.ldexp(y, -step))  # round half to even, on an exact quotient: 0 .. 16
+    v = np.ldexp(q, step)
+    # the code of the e4m3 value v
+    _, vx = np.frexp(v)
+    E = vx - 1
+    sub = E < -6
+    field = np.where(sub, 0, E + 7)
+    mant = np.where(sub, np.ldexp(v, 9), np.ldexp(v, 3 - np.where(sub, 0, E)) - 8)
+    code = np.where(v == 0, 0, field * 8 + mant).astype(np.uint8)
+    code |= (np.signbit(x).astype(np.uint8) << 7)
+    return code, e
 
 
 # --------------------------------------------------------------- distance.rs
@@ -680,6 +752,30 @@ class LeannIndex:
                 raise CoreError(2, "Empty vector collection")
             _check(_ffi.lib().isl_set_embeddings(self._h, _ptr(r), r.shape[0], r.shape[1], 1, MEM_HOST))
         return self
+
+    def set_embeddings_fp8(self, codes_u8, scale_exp: int = 0, device_ptr: int | None = None, n: int | None = None,
+                           d: int | None = None) -> "LeannIndex":
+        """In-memory provider with fp8 storage: `codes_u8` [n, d] OCP e4m3fn codes (or a device pointer to
+        them) under one power-of-two scale.  The provider's vectors are the exact f32 images
+        fp8_e4m3_to_f32(codes_u8, scale_exp); quantize_fp8_e4m3 makes codes and exponent from float32 rows.
+        The plain searches run over them; insert, remove, entry seeds and the two-level search refuse."""
+        if device_ptr is not None:
+            _check(_ffi.lib().isl_set_embeddings_fp8(self._h, C.c_void_p(device_ptr), n, d, int(scale_exp), MEM_DEVICE))
+        else:
+            r = np.ascontiguousarray(codes_u8)
+            if r.dtype != np.uint8:
+                raise TypeError("fp8 codes are uint8")
+            if r.ndim != 2 or r.shape[0] == 0:
+                raise CoreError(2, "Empty vector collection")
+            _check(_ffi.lib().isl_set_embeddings_fp8(self._h, _ptr(r), r.shape[0], r.shape[1], int(scale_exp), MEM_HOST))
+        return self
+
+    def row_storage(self) -> dict:
+        """What the in-memory rows cost: {"dtype": ISL_DTYPE_* (0 f32, 1 bf16, 2 fp8 e4m3), "scale_exp",
+        "block_bytes": bytes of the row block in HBM}."""
+        dt, se, nb = _ffi.i32(0), _ffi.i32(0), u64(0)
+        _check(_ffi.lib().isl_index_row_storage(self._h, C.byref(dt), C.byref(se), C.byref(nb)))
+        return {"dtype": int(dt.value), "scale_exp": int(se.value), "block_bytes": int(nb.value)}
 
     def _attach(self, provider):
         if isinstance(provider, InMemoryEmbeddingProvider):

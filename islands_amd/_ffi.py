@@ -97,6 +97,8 @@ SIGNATURES = {
     "isl_index_get_neighbors": (i32, [C.c_void_p, u64, P(P(u64)), P(C.c_size_t)]),
     "isl_index_upload": (i32, [C.c_void_p, i32]),
     "isl_set_embeddings": (i32, [C.c_void_p, C.c_void_p, u64, u64, i32, i32]),
+    "isl_set_embeddings_fp8": (i32, [C.c_void_p, C.c_void_p, u64, u64, i32, i32]),
+    "isl_index_row_storage": (i32, [C.c_void_p, P(i32), P(i32), P(u64)]),
     "isl_search_batch": (i32, [C.c_void_p, C.c_void_p, u64, u64, u64, u64, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "isl_hnsw_from_bytes": (i32, [C.c_void_p, C.c_size_t, i32, P(C.c_void_p)]),

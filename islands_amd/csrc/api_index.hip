@@ -480,6 +480,15 @@ __global__ void widen_bf16_kernel(const uint16_t* __restrict__ src, uint64_t sst
   dst[r * dstride + c] = __uint_as_float((uint32_t)src[r * sstride + c] << 16);
 }
 
+// fp8 e4m3 codes -> their exact f32 images e4m3(c) * scale (scale = 2^scale_exp of the table)
+__global__ void widen_fp8_kernel(const uint8_t* __restrict__ src, uint64_t sstride, uint32_t d, uint64_t n,
+                                 float scale, float* __restrict__ dst, uint64_t dstride) {
+  uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * d) return;
+  const uint64_t r = i / d, c = i % d;
+  dst[r * dstride + c] = isl_dev::fp8_image(src[r * sstride + c], scale);
+}
+
 // norm2[i] = sum_j rows[i][j]^2, sequential in j (one lane per row, rows staged through LDS).
 __global__ __launch_bounds__(64) void row_norm2_kernel(const float* __restrict__ rows, uint64_t n,
                                                        uint32_t d, uint64_t stride,
@@ -705,19 +714,24 @@ isl_status isl::RowTable::fill(uint64_t first, uint64_t count, const void* src, 
   const hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (stride == d) ISL_HIP(hipMemcpy(at, src, (size_t)(count * d * es), kind));
   else ISL_HIP(hipMemcpy2D(at, stride * es, src, d * es, d * es, count, kind));
-  if (!is_bf16()) {
+  if (dtype_ == ISL_DTYPE_F32) {
     launch_row_norm2(f32() + first * stride, count, d, stride, norm2_ + first);
   } else {
-    // bf16 rows are bit patterns and the provider's vectors their exact f32 images: widen a chunk of rows to
-    // f32 and reuse the f32 kernel
+    // bf16 rows are bit patterns, fp8 rows codes, and the provider's vectors their exact f32 images: widen a
+    // chunk of rows to f32 and reuse the f32 kernel
     const uint64_t stride32 = isl_rows::stride(ISL_DTYPE_F32, d), chunk = isl_rows::norm_chunk_rows(count, d);
     DeviceBuffer<float> tmp;
     ISL_TRY(tmp.reserve(isl_rows::norm_chunk_floats(chunk, d)));
     ISL_HIP(hipMemset(tmp, 0, (size_t)isl_rows::norm_chunk_floats(chunk, d) * 4));
     for (uint64_t o = 0; o < count; o += chunk) {
       const uint64_t c = std::min(chunk, count - o);
-      hipLaunchKernelGGL(widen_bf16_kernel, dim3((uint32_t)((c * d + 255) / 256)), dim3(256), 0, 0,
-                         bf16() + (first + o) * stride, stride, (uint32_t)d, c, tmp.get(), stride32);
+      const dim3 wgrid((uint32_t)((c * d + 255) / 256));
+      if (is_fp8())
+        hipLaunchKernelGGL(widen_fp8_kernel, wgrid, dim3(256), 0, 0, fp8() + (first + o) * stride, stride, (uint32_t)d, c,
+                           std::ldexp(1.0f, scale_exp_), tmp.get(), stride32);
+      else
+        hipLaunchKernelGGL(widen_bf16_kernel, wgrid, dim3(256), 0, 0, bf16() + (first + o) * stride, stride, (uint32_t)d,
+                           c, tmp.get(), stride32);
       launch_row_norm2(tmp, c, d, stride32, norm2_ + first + o);
     }
   }
@@ -732,15 +746,16 @@ isl_status isl::RowTable::zero() {
   return ISL_OK;
 }
 
-extern "C" {
-
-// InMemoryEmbeddingProvider::new, leann.rs:111-120
-isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
-                              int32_t dtype, int32_t mem) {
+// InMemoryEmbeddingProvider::new, leann.rs:111-120, over rows of any stored type (scale_exp: fp8 rows only)
+static isl_status set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d, int32_t dtype,
+                                 int32_t scale_exp, int32_t mem) {
   if (!idx || (!rows && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   if (n == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
-  if (dtype != ISL_DTYPE_F32 && dtype != ISL_DTYPE_BF16)
+  if (dtype != ISL_DTYPE_F32 && dtype != ISL_DTYPE_BF16 && dtype != ISL_DTYPE_FP8_E4M3)
     return fail(ISL_ERR_INVALID_ARGUMENT, "unknown row dtype");
+  if (scale_exp < isl_rows::kMinScaleExp || scale_exp > isl_rows::kMaxScaleExp)
+    return fail(ISL_ERR_INVALID_ARGUMENT, "fp8 rows: scale_exp = %d is outside [%d, %d]", scale_exp, isl_rows::kMinScaleExp,
+                isl_rows::kMaxScaleExp);
   if (d == 0 || d > 65536) return fail(ISL_ERR_INVALID_ARGUMENT, "dimension out of range");
   if (idx->device < 0)
     return fail(ISL_ERR_DEVICE, "call isl_index_upload before attaching embeddings");
@@ -748,14 +763,38 @@ isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint
   std::lock_guard<std::mutex> lock(idx->mu);
   if (any_lane_busy(idx))  // their kernels read the tables freed below
     return fail(ISL_ERR_SEARCH, "Search error: the embedding provider cannot be swapped while searches are in flight");
-  if (dtype == ISL_DTYPE_BF16 && idx->is_hnsw) return fail(ISL_ERR_UNSUPPORTED, "the HnswGraph facade keeps f32 vectors");
+  if (dtype != ISL_DTYPE_F32 && idx->is_hnsw) return fail(ISL_ERR_UNSUPPORTED, "the HnswGraph facade keeps f32 vectors");
   // every check is above: from here on the old provider goes
   idx->seeds = {};  // copies of rows that are about to go
   free_exact_pool(idx->pool);  // sized by the row count: rebuilt by the next prepare / search
   idx->recompute = false;  // back to the in-memory provider
   ISL_TRY(idx->rows.allocate(dtype, n, d));
+  idx->rows.set_scale_exp(dtype == ISL_DTYPE_FP8_E4M3 ? scale_exp : 0);  // (before the fill: the norms are the images')
   idx->nvec = n;
   return idx->rows.fill(0, n, rows, mem);
+}
+
+extern "C" {
+
+isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
+                              int32_t dtype, int32_t mem) {
+  return set_embeddings(idx, rows, n, d, dtype, 0, mem);
+}
+
+isl_status isl_set_embeddings_fp8(isl_index* idx, const void* codes, uint64_t n, uint64_t d, int32_t scale_exp,
+                                  int32_t mem) {
+  return set_embeddings(idx, codes, n, d, ISL_DTYPE_FP8_E4M3, scale_exp, mem);
+}
+
+isl_status isl_index_row_storage(const isl_index* idx, int32_t* dtype, int32_t* scale_exp, uint64_t* block_bytes) {
+  if (!idx) return fail(ISL_ERR_INVALID_ARGUMENT, "index is NULL");
+  std::lock_guard<std::mutex> lock(idx->mu);
+  const RowTable& t = idx->rows;
+  const bool held = t.resident() && !idx->recompute;
+  if (dtype) *dtype = held ? t.dtype() : ISL_DTYPE_F32;
+  if (scale_exp) *scale_exp = held ? t.scale_exp() : 0;
+  if (block_bytes) *block_bytes = held ? isl_rows::alloc_elems(t.dtype(), t.n(), t.d()) * isl_rows::elem_size(t.dtype()) : 0;
+  return ISL_OK;
 }
 
 // (re)allocates the recompute provider's row cache: slot map, owners and, last, the slab of `rows` rows of d

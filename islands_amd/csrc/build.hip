@@ -678,8 +678,10 @@ void launch_repair(uint32_t metric, bool diverse, const isl::RowTable& rows, uin
   isl::by_metric(metric, [&](auto mc) {
     rows.with_row_type([&](auto row) {
       using T = decltype(row);
-      if (diverse) hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, true, T>), dim3(grid), dim3(64), lds, 0, p);
-      else hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, false, T>), dim3(grid), dim3(64), lds, 0, p);
+      if constexpr (!std::is_same<T, isl::fp8_e4m3>::value) {  // (isl_index_remove refuses fp8 rows)
+        if (diverse) hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, true, T>), dim3(grid), dim3(64), lds, 0, p);
+        else hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, false, T>), dim3(grid), dim3(64), lds, 0, p);
+      }
     });
   });
 }
@@ -1070,8 +1072,9 @@ isl_status shrink_flat(const isl_build_options& opts, const isl_index* old, cons
     return fail(ISL_ERR_DEVICE, "hipMemset failed");
   rows.with_row_type([&](auto row) {
     using T = decltype(row);
-    hipLaunchKernelGGL(gather_survivor_rows_kernel<T>, dim3((uint32_t)n), dim3(256), 0, 0, rows.as<const T>(),
-                       rows.stride(), rows.norm2(), d_surv, shrunk.as<T>(), shrunk.norm2());
+    if constexpr (!std::is_same<T, isl::fp8_e4m3>::value)
+      hipLaunchKernelGGL(gather_survivor_rows_kernel<T>, dim3((uint32_t)n), dim3(256), 0, 0, rows.as<const T>(),
+                         rows.stride(), rows.norm2(), d_surv, shrunk.as<T>(), shrunk.norm2());
   });
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return fail(ISL_ERR_DEVICE, "row compaction failed");
@@ -1112,6 +1115,8 @@ extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* 
     return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: this is the core index of an HnswGraph, which does not shrink");
   if (idx->recompute)
     return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: an index on the recompute provider does not give rows up");
+  if (idx->rows.is_fp8())
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the index holds fp8 rows, which the repair does not read");
   uint64_t bad = 0;
   if (isl_plan::first_unknown_id(ids, n_ids, n0, &bad)) return isl::fail_node(bad);
   const isl::RowTable& old_rows = idx->rows;
@@ -1211,6 +1216,8 @@ extern "C" isl_status isl_index_insert(isl_index* idx, const isl_build_options* 
                 "isl_hnsw_insert");
   if (idx->recompute)
     return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: an index on the recompute provider does not take rows");
+  if (idx->rows.is_fp8())
+    return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index holds fp8 rows, which the builder does not read");
   const isl::RowTable& old_rows = idx->rows;
   if (n0) {
     const bool known = idx->has_dimension || old_rows.resident();

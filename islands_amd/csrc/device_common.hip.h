@@ -636,18 +636,216 @@ __device__ __forceinline__ float direct_group_bf16(const uint16_t* __restrict__ 
 }
 #undef ISL_RING
 
+// fp8 rows (ISL_DTYPE_FP8_E4M3, OCP e4m3fn codes with one power-of-two scale per table): the same quad
+// layout with 16 codes per 16-byte load, so a step covers 64 elements (lane s of the quad owns elements
+// 64i + 16s .. + 15) and a turn of the chain adds 16 terms, left to right.  A code's image e4m3(c) * scale is
+// an exact f32 (scale = 2^e, |e| <= 32: never a subnormal, never an overflow) and is what the hardware's scaled
+// convert returns for every code (v_cvt_scalef32_pk_f32_fp8, two codes of one half-word at a time; checked
+// against the format's definition over all 256 codes and all 65 scales): the arithmetic is the f32 chain of
+// the reference run on the images.  The query stays f32 in LDS.
+// The ring is RING_FP8 = 4 loads deep, not 12: a step's chain is four times as long as an f32 step's, so four
+// loads in flight are 256 elements of chain ahead of their use (the f32 ring: 192), and a step holds 16 terms
+// and the 16 query elements of the next one where the f32 step holds 4 and 4 -- with twelve slots the kernels
+// needed 144-168 VGPRs and, at S = 8, a scratch frame.
+constexpr int RING_FP8 = 4;
+typedef float v2f __attribute__((ext_vector_type(2)));
+struct QStep16 {
+  float4 a, b, c, e;
+  __device__ __forceinline__ void load(const float* qs, uint32_t at) {
+    a = *reinterpret_cast<const float4*>(qs + at);
+    b = *reinterpret_cast<const float4*>(qs + at + 4u);
+    c = *reinterpret_cast<const float4*>(qs + at + 8u);
+    e = *reinterpret_cast<const float4*>(qs + at + 12u);
+  }
+  // `qs` holds d rounded up to 4 floats
+  __device__ __forceinline__ void load_guarded(const float* qs, uint32_t at, uint32_t d) {
+    const uint32_t dq = (d + 3u) & ~3u;
+    a = make_float4(0.f, 0.f, 0.f, 0.f);
+    b = a; c = a; e = a;
+    if (at < dq) a = *reinterpret_cast<const float4*>(qs + at);
+    if (at + 4u < dq) b = *reinterpret_cast<const float4*>(qs + at + 4u);
+    if (at + 8u < dq) c = *reinterpret_cast<const float4*>(qs + at + 8u);
+    if (at + 12u < dq) e = *reinterpret_cast<const float4*>(qs + at + 12u);
+  }
+};
+#define ISL_RING(F) F(0) F(1) F(2) F(3)
+#define ISL_E16(F) F(0) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15)
+#define ISL_E15(F) F(1) F(2) F(3) F(4) F(5) F(6) F(7) F(8) F(9) F(10) F(11) F(12) F(13) F(14) F(15)
+template <int METRIC>
+__device__ __forceinline__ float direct_group_fp8(const uint8_t* __restrict__ emb, uint64_t stride,
+                                                  uint32_t d, uint32_t rid, uint32_t g0, uint32_t Rg,
+                                                  const float* qs, float q_norm, float row_aux, float scale) {
+  const int lane = threadIdx.x;
+  const uint32_t r = (uint32_t)lane >> 2;
+  const uint32_t s16 = ((uint32_t)lane & 3u) * 16u;
+  const uint32_t row = (uint32_t)__shfl((int)rid, (int)((g0 + (r < Rg ? r : 0u)) & 63u));
+  float a0 = 0.0f, a1 = 0.0f;
+  if (r < Rg) {
+    const uint8_t* rp = emb + (uint64_t)row * stride + s16;
+    const uint32_t nF = d >> 6;          // steps whose 64 elements all exist
+    const uint32_t nS = (d + 63u) >> 6;  // steps in total
+#define ISL_ADD_P(c) a0 += p##c;
+#define ISL_ADD_N(c) a1 += n##c;
+#define ISL_TURN(ss)                                                                          \
+  a0 = quad_prev(a0) + p0; ISL_E15(ISL_ADD_P)                                                  \
+  if constexpr (METRIC == ISL_METRIC_COSINE) { a1 = quad_prev(a1) + n0; ISL_E15(ISL_ADD_N) }
+#define ISL_ADD_G1(c) if (eg_ + (c) < d) { a0 += p##c; if constexpr (METRIC == ISL_METRIC_COSINE) a1 += n##c; }
+#define ISL_TURN_G(ss)                                                                        \
+  {                                                                                           \
+    a0 = quad_prev(a0);                                                                        \
+    if constexpr (METRIC == ISL_METRIC_COSINE) a1 = quad_prev(a1);                             \
+    const uint32_t eg_ = e0 + 16u * (ss);                                                      \
+    ISL_E16(ISL_ADD_G1)                                                                        \
+  }
+  // word j of the load holds codes 4j .. 4j + 3, lowest byte first; a convert takes the two codes of one half-word
+#define ISL_WIDEN                                                                               \
+  const v2f c0 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.x, scale, false),                 \
+            c1 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.x, scale, true),                  \
+            c2 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.y, scale, false),                 \
+            c3 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.y, scale, true),                  \
+            c4 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.z, scale, false),                 \
+            c5 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.z, scale, true),                  \
+            c6 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.w, scale, false),                 \
+            c7 = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8(xv.w, scale, true);                  \
+  const float w0 = c0.x, w1 = c0.y, w2 = c1.x, w3 = c1.y, w4 = c2.x, w5 = c2.y, w6 = c3.x, w7 = c3.y,       \
+              w8 = c4.x, w9 = c4.y, w10 = c5.x, w11 = c5.y, w12 = c6.x, w13 = c6.y, w14 = c7.x, w15 = c7.y;
+#define ISL_TERMS                                                                               \
+  const float p0 = dterm<METRIC>(qv.a.x, w0), p1 = dterm<METRIC>(qv.a.y, w1),                  \
+              p2 = dterm<METRIC>(qv.a.z, w2), p3 = dterm<METRIC>(qv.a.w, w3),                  \
+              p4 = dterm<METRIC>(qv.b.x, w4), p5 = dterm<METRIC>(qv.b.y, w5),                  \
+              p6 = dterm<METRIC>(qv.b.z, w6), p7 = dterm<METRIC>(qv.b.w, w7),                  \
+              p8 = dterm<METRIC>(qv.c.x, w8), p9 = dterm<METRIC>(qv.c.y, w9),                  \
+              p10 = dterm<METRIC>(qv.c.z, w10), p11 = dterm<METRIC>(qv.c.w, w11),              \
+              p12 = dterm<METRIC>(qv.e.x, w12), p13 = dterm<METRIC>(qv.e.y, w13),              \
+              p14 = dterm<METRIC>(qv.e.z, w14), p15 = dterm<METRIC>(qv.e.w, w15);              \
+  const float n0 = w0 * w0, n1 = w1 * w1, n2 = w2 * w2, n3 = w3 * w3, n4 = w4 * w4, n5 = w5 * w5,          \
+              n6 = w6 * w6, n7 = w7 * w7, n8 = w8 * w8, n9 = w9 * w9, n10 = w10 * w10, n11 = w11 * w11,    \
+              n12 = w12 * w12, n13 = w13 * w13, n14 = w14 * w14, n15 = w15 * w15;              \
+  (void)n0; (void)n1; (void)n2; (void)n3; (void)n4; (void)n5; (void)n6; (void)n7;              \
+  (void)n8; (void)n9; (void)n10; (void)n11; (void)n12; (void)n13; (void)n14; (void)n15;
+#define ISL_DECLX(k) v4u x##k;
+#define ISL_ISSUE(k) x##k = *reinterpret_cast<const v4u*>(rp + 64u * (base + (k)));
+#define ISL_PIN __builtin_amdgcn_sched_barrier(0x40F);
+#define ISL_TAKE(k)                                                               \
+    v4u xv = x##k;                                                                \
+    asm volatile("" : "+v"(xv));
+  // (the operand after the ring's last full step belongs to the guarded tail, which loads its own: the
+  // prefetch stays on a full step, inside the query)
+#define ISL_QNEXT(k)                                                              \
+    {                                                                             \
+      const uint32_t sn_ = base + (k) + 1u < nF ? base + (k) + 1u : nF - 1u;      \
+      qn.load(qs, s16 + 64u * sn_);                                               \
+    }
+#define ISL_ALL_ADDS ISL_TURN(0) ISL_TURN(1) ISL_TURN(2) ISL_TURN(3)
+#define ISL_STEP_RELOAD(k)                                                        \
+  {                                                                               \
+    ISL_TAKE(k)                                                                   \
+    const QStep16 qv = qn;                                                        \
+    ISL_WIDEN                                                                     \
+    ISL_TERMS                                                                     \
+    ISL_PIN                                                                       \
+    x##k = *reinterpret_cast<const v4u*>(rp + 64u * (base + RING_FP8 + (k)));         \
+    ISL_QNEXT(k)                                                                  \
+    ISL_PIN                                                                       \
+    ISL_ALL_ADDS                                                                  \
+  }
+#define ISL_STEP(k)                                                               \
+  {                                                                               \
+    ISL_TAKE(k)                                                                   \
+    const QStep16 qv = qn;                                                        \
+    ISL_WIDEN                                                                     \
+    ISL_TERMS                                                                     \
+    ISL_PIN                                                                       \
+    ISL_QNEXT(k)                                                                  \
+    ISL_PIN                                                                       \
+    ISL_ALL_ADDS                                                                  \
+  }
+    ISL_RING(ISL_DECLX)
+    uint32_t base = 0;
+    if (nF >= (uint32_t)RING_FP8) {
+      ISL_RING(ISL_ISSUE)
+      QStep16 qn;
+      qn.load(qs, s16);
+      ISL_PIN
+      while (base + 2u * RING_FP8 <= nF) {
+        ISL_RING(ISL_STEP_RELOAD)
+        base += RING_FP8;
+      }
+      ISL_RING(ISL_STEP)
+      base += RING_FP8;
+    }
+    if (base < nS) {
+      // fewer than RING_FP8 + 1 steps left (all of them when d < 64 * RING_FP8 = 256): loads first, clamped to the last
+      // step so that they stay unconditional (it ends at most 63 bytes past the row: in the next row or the
+      // block's slack), then the guarded chains
+      const uint32_t rem = nS - base;
+      const uint32_t last = nS - 1u;
+#define ISL_ISSUE_C(k)                                                              \
+  {                                                                                 \
+    const uint32_t st_ = base + (k) < last ? base + (k) : last;                     \
+    x##k = *reinterpret_cast<const v4u*>(rp + 64u * st_);                           \
+  }
+#define ISL_STEP_G(k)                                                               \
+  if ((uint32_t)(k) < rem) {                                                        \
+    const uint32_t e0 = 64u * (base + (k));                                         \
+    ISL_TAKE(k)                                                                     \
+    QStep16 qv;                                                                     \
+    qv.load_guarded(qs, e0 + s16, d);                                               \
+    ISL_WIDEN                                                                       \
+    ISL_TERMS                                                                       \
+    ISL_TURN_G(0) ISL_TURN_G(1) ISL_TURN_G(2) ISL_TURN_G(3)                         \
+  }
+      ISL_RING(ISL_ISSUE_C)
+      ISL_RING(ISL_STEP_G)
+#undef ISL_ISSUE_C
+#undef ISL_STEP_G
+    }
+#undef ISL_ADD_P
+#undef ISL_ADD_N
+#undef ISL_TURN
+#undef ISL_ADD_G1
+#undef ISL_TURN_G
+#undef ISL_WIDEN
+#undef ISL_TERMS
+#undef ISL_DECLX
+#undef ISL_ISSUE
+#undef ISL_PIN
+#undef ISL_TAKE
+#undef ISL_QNEXT
+#undef ISL_ALL_ADDS
+#undef ISL_STEP_RELOAD
+#undef ISL_STEP
+  }
+  a0 = quad_bcast<3>(a0);  // the sums end their round in lane 3
+  a1 = quad_bcast<3>(a1);
+  if (METRIC == METRIC_COSINE_PRE) a1 = __shfl(row_aux, (int)((g0 + r) & 63u));
+  return dfinish<METRIC>(a0, a1, q_norm);
+}
+#undef ISL_RING
+#undef ISL_E16
+#undef ISL_E15
+
+// the exact f32 image of one fp8 code: e4m3(c) * scale
+__device__ __forceinline__ float fp8_image(uint8_t c, float scale) {
+  const v2f pair = __builtin_amdgcn_cvt_scalef32_pk_f32_fp8((uint32_t)c, scale, false);
+  return pair.x;
+}
+
 // Tile-free counterpart of wave_distances: lane j < R receives the distance of row rid(j).
-// ROWT = float or uint16_t (bf16 bits).
+// ROWT = float, uint16_t (bf16 bits) or isl::fp8_e4m3 (codes; `scale` = 2^scale_exp of their table).
 template <int METRIC, typename ROWT = float, bool QH = false>
 __device__ __forceinline__ float direct_distances(const ROWT* __restrict__ emb, uint64_t stride,
                                                   uint32_t d, uint32_t rid, uint32_t R,
-                                                  const float* qs, float q_norm, float row_aux = 0.0f) {
+                                                  const float* qs, float q_norm, float row_aux = 0.0f,
+                                                  float scale = 1.0f) {
   const int lane = threadIdx.x;
   float result = 0.0f;
   for (uint32_t g0 = 0; g0 < R; g0 += GROUP) {
     const uint32_t Rg = R - g0 < (uint32_t)GROUP ? R - g0 : (uint32_t)GROUP;
     float dist;
-    if constexpr (sizeof(ROWT) == 2)
+    if constexpr (std::is_same<ROWT, isl::fp8_e4m3>::value)
+      dist = direct_group_fp8<METRIC>(reinterpret_cast<const uint8_t*>(emb), stride, d, rid, g0, Rg, qs, q_norm, row_aux, scale);
+    else if constexpr (sizeof(ROWT) == 2)
       dist = direct_group_bf16<METRIC, QH>(reinterpret_cast<const uint16_t*>(emb), stride, d, rid, g0, Rg, qs, q_norm, row_aux);
     else
       dist = direct_group<METRIC>(reinterpret_cast<const float*>(emb), stride, d, rid, g0, Rg, qs, q_norm, row_aux);
@@ -666,6 +864,20 @@ __device__ __forceinline__ float lane_distances_bf16(const uint16_t* __restrict_
   if ((uint32_t)threadIdx.x < R) {
     const uint16_t* rp = emb + (uint64_t)rid * stride;
     for (uint32_t j = 0; j < d; ++j) dstep<METRIC>(qs[j], __uint_as_float((uint32_t)rp[j] << 16), a0, a1);
+  }
+  if (METRIC == METRIC_COSINE_PRE) a1 = row_aux;
+  return dfinish<METRIC>(a0, a1, q_norm);
+}
+
+// ... and for fp8 rows (scale = 2^scale_exp of their table)
+template <int METRIC>
+__device__ __forceinline__ float lane_distances_fp8(const uint8_t* __restrict__ emb, uint64_t stride,
+                                                    uint32_t d, uint32_t rid, uint32_t R,
+                                                    const float* qs, float q_norm, float row_aux, float scale) {
+  float a0 = 0.0f, a1 = 0.0f;
+  if ((uint32_t)threadIdx.x < R) {
+    const uint8_t* rp = emb + (uint64_t)rid * stride;
+    for (uint32_t j = 0; j < d; ++j) dstep<METRIC>(qs[j], fp8_image(rp[j], scale), a0, a1);
   }
   if (METRIC == METRIC_COSINE_PRE) a1 = row_aux;
   return dfinish<METRIC>(a0, a1, q_norm);

@@ -12,6 +12,10 @@
 
 namespace isl {
 
+// the row type tag of fp8 rows (OCP e4m3fn codes): a type of its own, so that no `sizeof(ROWT)` test written for
+// float and uint16_t rows takes it for one of them
+struct fp8_e4m3 { uint8_t v; };
+
 class RowTable {
  public:
   RowTable() = default;
@@ -20,7 +24,7 @@ class RowTable {
     if (this != &o) {
       block_ = std::move(o.block_);
       norm2_ = std::move(o.norm2_);
-      dtype_ = o.dtype_; n_ = o.n_; d_ = o.d_; stride_ = o.stride_;
+      dtype_ = o.dtype_; scale_exp_ = o.scale_exp_; n_ = o.n_; d_ = o.d_; stride_ = o.stride_;
       o.reset();
     }
     return *this;
@@ -28,22 +32,30 @@ class RowTable {
 
   int32_t dtype() const { return dtype_; }
   bool is_bf16() const { return dtype_ == ISL_DTYPE_BF16; }
+  bool is_fp8() const { return dtype_ == ISL_DTYPE_FP8_E4M3; }
+  // fp8 rows: the element of code c is e4m3(c) * 2^scale_exp (0 for the other types)
+  int32_t scale_exp() const { return scale_exp_; }
+  void set_scale_exp(int32_t e) { scale_exp_ = e; }
   bool resident() const { return block_.get() != nullptr; }
   uint64_t n() const { return n_; }  // rows in the block
   uint64_t d() const { return d_; }
   uint64_t stride() const { return stride_; }  // in elements of the stored type
   const void* data() const { return block_.get(); }
-  // the block as rows of T; f32() / bf16() are NULL for a table of the other type
+  // the block as rows of T; f32() / bf16() / fp8() are NULL for a table of another type
   template <typename T>
   T* as() const { return reinterpret_cast<T*>(block_.get()); }
-  float* f32() const { return is_bf16() ? nullptr : as<float>(); }
+  float* f32() const { return dtype_ == ISL_DTYPE_F32 ? as<float>() : nullptr; }
   uint16_t* bf16() const { return is_bf16() ? as<uint16_t>() : nullptr; }
+  uint8_t* fp8() const { return is_fp8() ? as<uint8_t>() : nullptr; }
   float* norm2() const { return norm2_.get(); }  // [n], the reference's summation order
 
-  // f(float{}) or f(uint16_t{}): the one place a kernel template's row type is chosen at run time
+  // f(float{}), f(uint16_t{}) or f(fp8_e4m3{}): the one place a kernel template's row type is chosen at run
+  // time.  A caller whose kernels do not take fp8 rows (build, repair, entry seeds) refuses such a table before
+  // it gets here and leaves the third tag's branch empty (`if constexpr`), so that nothing is instantiated for it.
   template <typename F>
   void with_row_type(F&& f) const {
-    if (is_bf16()) f(uint16_t{});
+    if (is_fp8()) f(fp8_e4m3{});
+    else if (is_bf16()) f(uint16_t{});
     else f(float{});
   }
 
@@ -53,6 +65,7 @@ class RowTable {
     block_.reset();
     norm2_.reset();
     dtype_ = ISL_DTYPE_F32;
+    scale_exp_ = 0;
     n_ = d_ = stride_ = 0;
   }
   // A block and norms for n rows of d elements, contents undefined.  What the table held goes first (it may be
@@ -77,7 +90,7 @@ class RowTable {
  private:
   DeviceBuffer<unsigned char> block_;
   DeviceBuffer<float> norm2_;
-  int32_t dtype_ = ISL_DTYPE_F32;
+  int32_t dtype_ = ISL_DTYPE_F32, scale_exp_ = 0;
   uint64_t n_ = 0, d_ = 0, stride_ = 0;
 };
 

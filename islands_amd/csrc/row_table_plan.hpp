@@ -1,4 +1,4 @@
-// Host-only arithmetic of a row table (row_table.hpp): how rows of either stored type are laid out on the
+// Host-only arithmetic of a row table (row_table.hpp): how rows of any stored type are laid out on the
 // device and what the passes over them are cut into.  Plain C++ without a device header, so that
 // tests/cpp/row_table_dump.cpp prints it without a device.  This is the one place the layout rule is written:
 // a row starts 16-byte aligned, the block ends in 1 KiB of slack for whole-tile reads past the last row,
@@ -13,21 +13,22 @@
 namespace isl_rows {
 
 constexpr uint64_t kRowAlignBytes = 16, kSlackBytes = 1024;
-constexpr uint64_t kNormChunkBytes = 256ull << 20;  // f32 images of bf16 rows widened at a time for their norms
+constexpr uint64_t kNormChunkBytes = 256ull << 20;  // f32 images of bf16 / fp8 rows widened at a time for their norms
+constexpr int32_t kMinScaleExp = -32, kMaxScaleExp = 32;  // the power-of-two scale of an fp8 table
 
-// bytes of one element of a row of `dtype` (ISL_DTYPE_F32 / ISL_DTYPE_BF16)
-inline uint64_t elem_size(int32_t dtype) { return dtype == ISL_DTYPE_BF16 ? 2 : 4; }
-// elements from one row to the next: d rounded up to 4 floats / 8 bf16
+// bytes of one element of a row of `dtype` (ISL_DTYPE_F32 / ISL_DTYPE_BF16 / ISL_DTYPE_FP8_E4M3)
+inline uint64_t elem_size(int32_t dtype) { return dtype == ISL_DTYPE_FP8_E4M3 ? 1 : dtype == ISL_DTYPE_BF16 ? 2 : 4; }
+// elements from one row to the next: d rounded up to 4 floats / 8 bf16 / 16 fp8 codes
 inline uint64_t stride(int32_t dtype, uint64_t d) {
   const uint64_t per = kRowAlignBytes / elem_size(dtype);
   return (d + per - 1) / per * per;
 }
-// elements of slack behind the last row: 256 floats / 512 bf16
+// elements of slack behind the last row: 256 floats / 512 bf16 / 1024 fp8 codes
 inline uint64_t slack(int32_t dtype) { return kSlackBytes / elem_size(dtype); }
 // elements of a block of n rows
 inline uint64_t alloc_elems(int32_t dtype, uint64_t n, uint64_t d) { return n * stride(dtype, d) + slack(dtype); }
 
-// The norms of bf16 rows come from the f32 kernel over widened chunks: rows per chunk, and the floats of the
+// The norms of bf16 and fp8 rows come from the f32 kernel over widened chunks: rows per chunk, and the floats of the
 // chunk buffer (an f32 table of that many rows).
 inline uint64_t norm_chunk_rows(uint64_t n, uint64_t d) {
   return std::max<uint64_t>(1, std::min<uint64_t>(n, kNormChunkBytes / (stride(ISL_DTYPE_F32, d) * 4)));

@@ -25,6 +25,8 @@
 #include "search_geometry.hpp"
 #include "search_internal.hpp"
 
+#include <cmath>
+
 using namespace isl_lane;
 
 namespace {
@@ -311,7 +313,8 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.ell_deg = idx->d_ell_deg;
   p.num_nodes = idx->num_nodes;
   p.emb = idx->rows.data();
-  p.emb_bf16 = idx->rows.is_bf16() ? 1u : 0u;
+  p.emb_dtype = (uint32_t)idx->rows.dtype();
+  p.emb_scale = std::ldexp(1.0f, idx->rows.scale_exp());
   p.norm2 = idx->rows.norm2();
   p.nvec = idx->nvec;
   p.stride = idx->rows.stride();
@@ -452,7 +455,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
       isl_launch::launch_two_level(metric, true, false, false, grid, cg.tl_lds, st, &p);
       p.qsel_mode = 0;
     } else {
-      isl_launch::launch_two_level(metric, p.emb_bf16 != 0, resume || (warm && idx->recompute), false, grid, cg.tl_lds, st, &p);
+      isl_launch::launch_two_level(metric, idx->rows.is_bf16(), resume || (warm && idx->recompute), false, grid, cg.tl_lds, st, &p);
     }
     ISL_HIP(hipGetLastError());
     p.nq = warm ? 0u : (uint32_t)nq;
@@ -477,7 +480,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     if (resume) p.nq = plan.active;  // the fast kernel runs this round's queries; nothing else reads nq
     uint32_t grid = (uint32_t)std::min<uint64_t>(resume ? plan.active : nq_grid, cg.slots);
     const bool skip_fast = resume && plan.active == 0;  // only queries parked in the heap-exact kernel this round
-    isl_launch::FastKernel fk{cg.segments, metric, idx->max_degree > 64, p.emb_bf16 != 0, resume, false};
+    isl_launch::FastKernel fk{cg.segments, metric, idx->max_degree > 64, idx->rows.dtype(), resume, false};
     if (qh) {
       p.qsel = ws.qsel;
       p.qsel_h = ws.qsel_h;
@@ -744,6 +747,8 @@ isl_status precheck(const isl_index* idx, uint64_t nq, uint64_t d, uint64_t k, u
 }
 
 isl_status precheck_two_level(const isl_index* idx, uint64_t d) {
+  // (first: an index that holds fp8 rows gets this answer with or without PQ codes)
+  if (idx->rows.is_fp8()) return isl::fail(ISL_ERR_UNSUPPORTED, "two-level search does not run over fp8 rows");
   if (!idx->pq || !idx->d_codes)
     return isl::fail(ISL_ERR_PQ, "PQ error: no PQ codes attached (isl_index_set_pq_codes)");
   if (idx->is_hnsw) return isl::fail(ISL_ERR_UNSUPPORTED, "two-level search runs on a LeannIndex");
@@ -1058,7 +1063,7 @@ isl_status isl_index_prepare(isl_index* idx, uint64_t max_nq, uint64_t max_ef, u
         warm_call.ef = e;
         ISL_TRY(search_enqueue(idx, ws, warm_call, RoundPlan{}, true));
       }
-      if (idx->pq && idx->d_codes && !idx->is_hnsw && d == idx->pq->dimension) {
+      if (idx->pq && idx->d_codes && !idx->is_hnsw && !idx->rows.is_fp8() && d == idx->pq->dimension) {
         warm_call.k = std::min<uint64_t>(max_k, max_ef);
         warm_call.ef = max_ef;
         warm_call.two_level = true;

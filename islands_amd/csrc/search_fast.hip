@@ -28,9 +28,12 @@ void isl_launch::launch_fast_segments(const FastKernel& k, uint32_t grid, size_t
   } else if (k.resume) {  // searches over the recompute provider (f32 rows) that park and resume
     if (k.wide) launch_t<float, true, true>(k.metric, grid, lds, st, p);
     else launch_t<float, false, true>(k.metric, grid, lds, st, p);
-  } else if (k.bf16) {
+  } else if (k.dtype == ISL_DTYPE_BF16) {
     if (k.wide) launch_t<uint16_t, true>(k.metric, grid, lds, st, p);
     else launch_t<uint16_t, false>(k.metric, grid, lds, st, p);
+  } else if (k.dtype == ISL_DTYPE_FP8_E4M3) {  // f32 queries over fp8 codes: the f32-query launch geometry
+    if (k.wide) launch_t<isl::fp8_e4m3, true>(k.metric, grid, lds, st, p);
+    else launch_t<isl::fp8_e4m3, false>(k.metric, grid, lds, st, p);
   } else {
     if (k.wide) launch_t<float, true>(k.metric, grid, lds, st, p);
     else launch_t<float, false>(k.metric, grid, lds, st, p);

@@ -25,8 +25,9 @@ struct SearchParams {
   const uint64_t* off;
   const uint32_t* adj;
   uint64_t num_nodes;
-  const void* emb;     // rows: f32, or bf16 bits when emb_bf16
-  uint32_t emb_bf16;
+  const void* emb;     // rows: f32, bf16 bits or fp8 codes, as emb_dtype (ISL_DTYPE_*) says
+  uint32_t emb_dtype;
+  float emb_scale;     // fp8 rows: 2^scale_exp of their table (1 otherwise)
   const float* norm2;  // per-row sum of squares (cosine only), reference order
   uint64_t nvec;
   uint64_t stride;  // floats between rows
@@ -606,6 +607,7 @@ __global__ __launch_bounds__(64) void classify_queries_kernel(SearchParams p) {
 template <int S, int METRIC_API, typename ROWT, bool WIDE, bool RESUME = false, bool QH = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void leann_search_fast(SearchParams p) {
   static_assert(!QH || (sizeof(ROWT) == 2 && !RESUME), "the bf16 query operand goes with bf16 rows");
+  static_assert(!std::is_same<ROWT, isl::fp8_e4m3>::value || !RESUME, "fp8 rows are in-memory rows: nothing parks");
   constexpr uint32_t kMaxDeg = WIDE ? 128u : 64u;
   // parked state of one query, in words: 16 scalars, tie list, the hop's unvisited ids (2 x 64),
   // result set (S x (64 keys + 64 ids)), visited table
@@ -731,7 +733,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void le
       const uint32_t entry = p.q_entry ? p.q_entry[qi] : p.entry;
       const uint32_t erow = row_index(p, entry, true);
       float e_aux = METRIC == METRIC_COSINE_PRE ? p.norm2[erow] : 0.0f;
-      float ed = direct_distances<METRIC, ROWT, QH>(emb, p.stride, p.d, erow, 1, qs, q_norm, e_aux);
+      float ed = direct_distances<METRIC, ROWT, QH>(emb, p.stride, p.d, erow, 1, qs, q_norm, e_aux, p.emb_scale);
       ed = rl_f(ed, 0);
       cV = p.q_entry ? p.q_evals[qi] : 1;
       if (lane == 0) htab[hslot_cap(entry, hcap)] = entry;
@@ -893,7 +895,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void le
       ngroups += (keep + 15) / 16;
       const uint32_t rix = row_index(p, uid, (uint32_t)lane < keep);
       float r_aux = (METRIC == METRIC_COSINE_PRE && (uint32_t)lane < keep) ? p.norm2[rix] : 0.0f;
-      float nd = direct_distances<METRIC, ROWT, QH>(emb, p.stride, p.d, rix, keep, qs, q_norm, r_aux);
+      float nd = direct_distances<METRIC, ROWT, QH>(emb, p.stride, p.d, rix, keep, qs, q_norm, r_aux, p.emb_scale);
       ISL_MARK(tp2)  // row fetch + distances
 
       // leann.rs:953-970 in CSR order; worst = results.peek().  NaN / -0.0 distances have no
@@ -1041,11 +1043,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) void le
 }
 
 
-// rows of the exact kernel: the LDS-tile routine for f32 rows, a plain per-lane walk for bf16
+// rows of the exact kernel: the LDS-tile routine for f32 rows, a plain per-lane walk for bf16 and fp8
 template <int METRIC>
 __device__ __forceinline__ float exact_rows(const SearchParams& p, uint32_t rid, uint32_t R,
                                             const float* qs, float* tile, float q_norm, float aux) {
-  if (p.emb_bf16)
+  if (p.emb_dtype == ISL_DTYPE_FP8_E4M3)
+    return lane_distances_fp8<METRIC>(reinterpret_cast<const uint8_t*>(p.emb), p.stride, p.d, rid, R, qs, q_norm,
+                                      aux, p.emb_scale);
+  if (p.emb_dtype == ISL_DTYPE_BF16)
     return lane_distances_bf16<METRIC>(reinterpret_cast<const uint16_t*>(p.emb), p.stride, p.d, rid, R, qs,
                                        q_norm, aux);
   return wave_distances<METRIC>(reinterpret_cast<const float*>(p.emb), p.stride, p.d, rid, R, qs, tile, q_norm, aux);
@@ -1880,10 +1885,12 @@ namespace isl_launch {
 // (1, 2, 4, 8); wide = the index has adjacency rows of 65..128 ids (its own instantiation: the common
 // case keeps its register budget); resume = the RESUME instantiation (recompute provider; f32 rows
 // only); qh = the QH instantiation (bf16 rows of up to 64 ids per adjacency row, query held as bf16
-// in LDS)
+// in LDS); dtype = the stored type of the rows (ISL_DTYPE_*; fp8 rows have neither a resume nor a qh form)
 struct FastKernel {
   int S, metric;
-  bool wide, bf16, resume, qh;
+  bool wide;
+  int dtype;
+  bool resume, qh;
 };
 // defined and instantiated for one S by search_fast.hip, which is compiled once per S; search.hip
 // holds the switch over S (launch_fast)
