@@ -853,6 +853,51 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg, const isl_build_options* o
 isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts, const float* vectors, uint64_t n_new,
                            uint64_t d, const uint64_t* levels, uint64_t level_seed, int32_t mem,
                            uint64_t* first_id);
+/* Rows out of a built HnswGraph, in place (extension: the reference has no removal).  `h` may have been built
+ * here, grown by isl_hnsw_insert, read by isl_hnsw_from_bytes or handed over with isl_hnsw_from_layers.  ids =
+ * n_ids node ids in host memory, repeated ids counting once: the set D.  opts = the selection rule of this call
+ * (select_rule, alpha, keep_pruned; NULL: the defaults; batch is not used); the rule is not recorded in the graph,
+ * as with isl_hnsw_insert.  out_remap [old len] (may be NULL) receives the new id of every old node or ISL_REMOVED,
+ * *out_len (may be NULL) the new len; both are written only on ISL_OK.
+ * Definition, over a graph with layers 0 .. max_level, L_L[p] = neighbors_at(L) of node p in stored order,
+ * M_L = m0 on layer 0 and m above, and resident f32 rows:
+ * 1. Repair, per layer.  Every layer is repaired independently and every list comes from the OLD lists of that
+ *    layer only.  For every layer L and every survivor p with level[p] >= L: if no id of L_L[p] is in D,
+ *    L'_L[p] = L_L[p].  Otherwise the candidate list C_L(p), built as isl_index_remove builds C(p) but on layer L:
+ *    walk L_L[p] in stored order; a survivor x emits x, also where x does not have layer L (HnswGraph::insert
+ *    leaves such lists behind a node that rises above the top layer, and they are kept as they are); a removed x
+ *    emits every y of L_L[x], in stored order, with y not in D and y != p, and nothing where it does not have
+ *    layer L; first occurrences only; the walk stops after ISL_REMOVE_MAX_CANDIDATES distinct ids.  If
+ *    |C_L(p)| <= M_L, L'_L[p] = C_L(p).  If |C_L(p)| > M_L: d(p, c) = Distance::calculate(vec[p], vec[c]) through
+ *    the library's exact-order chain, a stable ascending sort (NaN last, -0 == +0), then ISL_SELECT_REFERENCE
+ *    keeps the first M_L and ISL_SELECT_DIVERSE keeps select(p, sorted C_L(p), M_L).  A list whose candidates are
+ *    all gone ends EMPTY: nothing is invented.
+ * 2. Compaction, order kept.  New id = old id minus the removed ids below it; the levels of the survivors are
+ *    kept; their rows and norms are copied bit for bit on the device.  Entry point: one that survives is kept
+ *    (remapped) and max_level stays; otherwise the lowest new id among the survivors of the highest surviving
+ *    level takes over and max_level becomes that level; the layers above the new max_level cease to exist.
+ *    isl_hnsw_to_bytes afterwards writes next_id = the new len.  Removing every node leaves what isl_hnsw_build
+ *    gives for n == 0 under the handle's config (m, m0, ef_construction, metric, ml, max_layers, device): no entry
+ *    point, no dimension; a later isl_hnsw_insert starts the graph again.
+ * After ISL_OK the handle satisfies every precondition of isl_hnsw_insert (levels match layers, lists <= M_L,
+ * layer 0 verbatim) and serves isl_hnsw_search_batch; lanes and the padded adjacency are set up again at the
+ * first search, as after isl_hnsw_insert.
+ * Strong guarantee: the shrunk graph is built beside the old one and swapped into the handle at the end; on any
+ * failure `h` is unchanged (bytes, rows, search answers).  Peak device memory: the old graph whole, plus one table
+ * per old layer over the OLD nodes ([len][m0 + 1] ids on layer 0, [len][m + 1] per layer above, and len degrees
+ * each), the touched list (8 bytes per surviving list), the shrunk layer 0 twice and its padded adjacency, the
+ * shrunk upper layers (len' + 1 offsets each) and the survivors' rows.
+ * The call is the reference's &mut self: not beside searches on the same handle.  Checked in this order before any
+ * device call: NULL h, or NULL ids with n_ids > 0 -> ISL_ERR_INVALID_ARGUMENT; opts as in isl_hnsw_build;
+ * n_ids == 0 -> ISL_OK, nothing changed, out_remap the identity; an id >= len -> ISL_ERR_NODE_NOT_FOUND (node); a
+ * non-empty graph whose rows are not resident f32 rows -> ISL_ERR_UNSUPPORTED; nodes but no entry point, or levels
+ * that do not match the layers (as isl_hnsw_insert refuses them) -> ISL_ERR_UNSUPPORTED; m0 > 128 or more than 64
+ * layers -> ISL_ERR_UNSUPPORTED; a busy lane -> ISL_ERR_SEARCH.  Refused once the import kernel has looked, each
+ * with ISL_ERR_UNSUPPORTED and a message that says which: a list longer than its layer's M_L; a layer-0 device
+ * copy that is not the lists verbatim; an id or offset outside the graph.
+ * isl_index_remove on the core index of an HnswGraph stays ISL_ERR_UNSUPPORTED. */
+isl_status isl_hnsw_remove(isl_hnsw* h, const isl_build_options* opts, const uint64_t* ids, uint64_t n_ids,
+                           uint64_t* out_remap /* [old len], may be NULL */, uint64_t* out_len /* may be NULL */);
 /* Read-back into host buffers, for every isl_hnsw handle (built, from_layers, from_bytes). */
 isl_status isl_hnsw_info(const isl_hnsw* h, int32_t* has_entry, uint64_t* entry, uint64_t* max_level,
                          uint64_t* dim);

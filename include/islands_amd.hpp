@@ -384,6 +384,17 @@ class HnswGraph {
     if (n) vectors_.clear();  // the host copy of the smaller graph's rows: get_vector asks the device now
     return first;
   }
+  // Rows out of the graph, in place (isl_hnsw_remove): on every layer the lists that named a removed id are
+  // repaired under opts' rule, the survivors keep their order and levels and take new ids; returns
+  // remap[old] = new id or ISL_REMOVED.  On an error the graph is unchanged.  Not beside searches on the same
+  // graph.
+  std::vector<uint64_t> remove(const std::vector<uint64_t>& ids,
+                               const isl_build_options& opts = LeannIndex::build_options()) {
+    std::vector<uint64_t> remap(len());
+    check(isl_hnsw_remove(h_, &opts, ids.empty() ? nullptr : ids.data(), ids.size(), remap.data(), nullptr));
+    if (!ids.empty()) vectors_.clear();  // the host copy of the larger graph's rows: get_vector asks the device now
+    return remap;
+  }
   // HnswGraph::to_bytes, hnsw.rs:507-509 (nodes in ascending id)
   std::vector<uint8_t> to_bytes() const {
     uint8_t* p = nullptr;

@@ -1186,6 +1186,27 @@ class HnswGraph:
         self._keep = None
         return int(first.value)
 
+    def remove(self, ids, select="reference", alpha: float = 1.0, keep_pruned: bool = True) -> np.ndarray:
+        """Rows out of the graph, in place (isl_hnsw_remove).  On every layer a list that named a removed id is
+        repaired from that layer's old lists alone: a removed neighbour is replaced by its own surviving
+        neighbours there, and a list that outgrows its layer's cap is cut to the nearest ("reference") or
+        re-selected by the occlusion rule ("diverse").  The survivors keep their order, their levels and take new
+        ids; a removed entry point passes to the lowest new id of the highest surviving level, and the layers
+        above that level go.  Returns remap[old id] = new id, or REMOVED.  On an error the graph is unchanged.
+        Not beside searches on the same graph."""
+        a = np.ascontiguousarray(ids, dtype=np.uint64).ravel()
+        o = LeannIndex._build_options(select, alpha, keep_pruned)
+        n0 = len(self)
+        remap = np.zeros(max(n0, 1), dtype=np.uint64)
+        n = u64()
+        _check(_ffi.lib().isl_hnsw_remove(self._h, C.byref(o), _ptr(a) if a.size else None, a.size, _ptr(remap),
+                                          C.byref(n)))
+        if a.size:  # what the object kept of the larger graph: the library answers for the shrunk one
+            self._levels = None
+            self.vectors = None
+            self._keep = None
+        return remap[:n0]
+
     @staticmethod
     def random_levels(n: int, ml: float | None = None, max_layers: int = 16, seed: int = 0) -> np.ndarray:
         """isl_hnsw_random_levels: random_level (hnsw.rs:206-211) for n nodes from a seeded generator."""

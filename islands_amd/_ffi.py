@@ -211,6 +211,7 @@ SIGNATURES = {
     "isl_index_insert": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, i32, u64, u64, C.c_void_p, i32, P(u64)]),
     "isl_index_remove": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, C.c_void_p, P(u64)]),
     "isl_hnsw_insert": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, u64, C.c_void_p, u64, i32, P(u64)]),
+    "isl_hnsw_remove": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, C.c_void_p, P(u64)]),
     "isl_hnsw_info": (i32, [C.c_void_p, P(i32), P(u64), P(u64), P(u64)]),
     "isl_hnsw_levels": (i32, [C.c_void_p, C.c_void_p]),
     "isl_hnsw_get_neighbors": (i32, [C.c_void_p, u64, u64, C.c_void_p, u64, P(u64), P(i32)]),

@@ -28,7 +28,9 @@
 // one wave per survivor that lost a neighbour rebuilds its row from the OLD CSR (repair_kernel: the removed
 // neighbours' own lists stand in for them; past m0 ids the builder's sort and selection decide), and the survivors'
 // lists, rows and norms are compacted into a graph built beside the old one, which moves in as a grown one does.
-// The remap, the entry-point rule and the LDS size are remove_plan.hpp's.
+// The remap, the entry-point rule and the LDS size are remove_plan.hpp's.  The removal kernels read their graph as
+// an array of layers (RemoveLayer, build_internal.hpp) -- one for a flat index -- and are launched through isl_build,
+// so that isl_hnsw_remove (hnsw_build.hip) runs the same kernels over every layer of an HnswGraph in one pass.
 //
 // The HnswGraph builder (hnsw_build.hip) runs the same selection kernels and link_kernel's HNSW mode
 // over one fixed-width table per layer.  Both go through one host path, isl_build::Scaffold
@@ -37,7 +39,7 @@
 // sizes are build_plan.hpp's.
 #include "device_common.hip.h"
 #include "build_internal.hpp"
-#include "remove_plan.hpp"
+#include "hnsw_remove_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -487,39 +489,37 @@ __global__ void gather_rows_bf16_kernel(const uint16_t* __restrict__ emb, uint64
 // ---------------------------------------------------------------- isl_index_remove
 using isl_plan::kGone;
 
-// Survivors with at least one removed neighbour, in no particular order: one wave per row of the old CSR.
-// Runs after the import kernel has found every offset and id of the CSR in range.
-__global__ __launch_bounds__(256) void touched_kernel(const uint64_t* __restrict__ off, const uint32_t* __restrict__ adj,
+using isl_build::RemoveLayer;
+using isl_build::RepairParams;
+
+// Survivors with at least one removed neighbour on a layer, as (layer, node) pairs in no particular order: one wave
+// per row of every layer's old CSR (blockIdx.y = layer; a flat index is one layer without levels).  Runs after the
+// import kernel has found every offset and id of the CSRs in range.  counts[0] = all pairs, counts[1 + L] = those of
+// layer L; a pair past `cap` is counted and not written.
+__global__ __launch_bounds__(256) void touched_kernel(const RemoveLayer* __restrict__ layers,
+                                                      const uint32_t* __restrict__ levels,
                                                       const uint32_t* __restrict__ remap, uint64_t n0,
-                                                      uint32_t* __restrict__ touched, uint32_t* __restrict__ count) {
+                                                      uint64_t* __restrict__ pairs, uint32_t cap,
+                                                      uint32_t* __restrict__ counts) {
   const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t lane = threadIdx.x & 63, layer = blockIdx.y;
   if (row >= n0 || remap[row] == kGone) return;
+  if (levels && levels[row] < layer) return;  // no list on this layer
+  const uint64_t* off = layers[layer].off;
+  const uint32_t* adj = layers[layer].adj;
   const uint64_t s = off[row];
   const uint32_t dg = (uint32_t)(off[row + 1] - s);
   bool hit = false;
   for (uint32_t i = lane; i < dg; i += 64) hit |= remap[adj[s + i]] == kGone;
-  if (ballot(hit) && lane == 0) touched[atomicAdd(count, 1u)] = (uint32_t)row;  // at most one entry per row: < n0
+  if (ballot(hit) && lane == 0) {  // at most one pair per row and layer
+    const uint32_t at = atomicAdd(counts, 1u);
+    if (at < cap) pairs[at] = isl_plan::touched_pair(layer, (uint32_t)row);
+    atomicAdd(counts + 1 + layer, 1u);
+  }
 }
 
-struct RepairParams {
-  const void* emb;           // the OLD rows, by old id
-  const float* norm2;
-  uint64_t stride;
-  uint32_t d;
-  float alpha;
-  uint32_t keep_pruned;
-  const uint64_t* off;       // the OLD CSR: every list is computed from the old lists only
-  const uint32_t* adj;
-  const uint32_t* remap;     // [n0] new id or kGone
-  const uint32_t* touched;   // [grid]
-  uint32_t* ell;             // [n0][W] the table being written: row `node` alone, never read
-  uint32_t* deg;
-  uint32_t W, m0;
-  unsigned long long* total; // [1] sum of |C(p)| over the touched nodes
-};
-
-// The repair of include/islands_amd.h for one touched node per wave.  C(p) is streamed from the old CSR into
+// The repair of include/islands_amd.h for one touched (layer, node) pair per wave, over that layer's old CSR and
+// M_L; a removed neighbour that lacks the layer has no list there.  C(p) is streamed from the old CSR into
 // LDS: a surviving neighbour is one id on lane 0, a removed one its list in slices of 64; every slice is
 // looked up in the ids taken so far (a list of the device CSR holds no id twice, so a slice needs no look at
 // itself) and appended in lane order.  Nothing is written at or past kRemoveMaxCandidates, and the walk ends
@@ -536,7 +536,9 @@ __global__ __launch_bounds__(64) void repair_kernel(RepairParams p) {
   const SelState s = sel_state<ROWT>(qs, p.d, CAP);
   const uint32_t lane = threadIdx.x;
   const uint64_t below = (1ull << lane) - 1ull;
-  const uint32_t node = p.touched[blockIdx.x];
+  const uint64_t pair = p.touched[blockIdx.x];
+  const uint32_t node = isl_plan::pair_node(pair), layer = isl_plan::pair_layer(pair);
+  const RemoveLayer ly = p.layers[layer];
   // the two lists the selection initialises itself hold the unsorted entries until then
   uint32_t* raw_id = s.lst;
   float* raw_d = reinterpret_cast<float*>(s.kept);
@@ -551,27 +553,27 @@ __global__ __launch_bounds__(64) void repair_kernel(RepairParams p) {
     n = n < CAP ? n : CAP;
     __syncthreads();
   };
-  const uint64_t ps = p.off[node];
-  const uint32_t pdeg = (uint32_t)(p.off[node + 1] - ps);
+  const uint64_t ps = ly.off[node];
+  const uint32_t pdeg = (uint32_t)(ly.off[node + 1] - ps);
   for (uint32_t t = 0; t < pdeg && n < CAP; ++t) {
-    const uint32_t x = uni(p.adj[ps + t]);
+    const uint32_t x = uni(ly.adj[ps + t]);
     if (p.remap[x] != kGone) {
       take(lane == 0, x);
     } else {
-      const uint64_t xs = p.off[x];
-      const uint32_t xdeg = (uint32_t)(p.off[x + 1] - xs);
+      const uint64_t xs = ly.off[x];
+      const uint32_t xdeg = (p.levels && p.levels[x] < layer) ? 0u : (uint32_t)(ly.off[x + 1] - xs);
       for (uint32_t base = 0; base < xdeg && n < CAP; base += 64) {
         const bool in = base + lane < xdeg;
-        const uint32_t y = in ? p.adj[xs + base + lane] : 0u;
+        const uint32_t y = in ? ly.adj[xs + base + lane] : 0u;
         take(in && y != node && p.remap[y] != kGone, y);
       }
     }
   }
   if (lane == 0) atomicAdd(p.total, (unsigned long long)n);
-  uint32_t* row = p.ell + (uint64_t)node * p.W;
-  if (n <= p.m0) {
+  uint32_t* row = ly.ell + (uint64_t)node * (ly.M + 1);
+  if (n <= ly.M) {
     for (uint32_t i = lane; i < n; i += 64) row[i] = raw_id[i];
-    if (lane == 0) p.deg[node] = n;
+    if (lane == 0) ly.deg[node] = n;
     return;
   }
   const SelCtxT<ROWT> c{static_cast<const ROWT*>(p.emb), p.norm2, p.stride, p.d, p.alpha, p.keep_pruned};
@@ -598,33 +600,36 @@ __global__ __launch_bounds__(64) void repair_kernel(RepairParams p) {
     s.cd[r] = raw_d[i];
   }
   __syncthreads();
-  uint32_t nk = p.m0;
+  uint32_t nk = ly.M;
   if constexpr (DIVERSE) {
-    nk = diverse_select<METRIC>(c, n, p.m0, s, qs, tile);
+    nk = diverse_select<METRIC>(c, n, ly.M, s, qs, tile);
     for (uint32_t i = lane; i < nk; i += 64) row[i] = s.out[i];
   } else {
     for (uint32_t i = lane; i < nk; i += 64) row[i] = s.cid[i];
   }
-  if (lane == 0) p.deg[node] = nk;
+  if (lane == 0) ly.deg[node] = nk;
 }
 
-// Compaction of the lists: the table rows of the survivors, through the remap, into the new CSR (one wave per
-// old row).  A removed id left in a survivor's row raises the flag and is not written as an id out of range.
-__global__ __launch_bounds__(256) void table_to_csr_remap_kernel(const uint32_t* __restrict__ ell,
-                                                                 const uint32_t* __restrict__ deg, uint32_t W,
-                                                                 const uint32_t* __restrict__ remap,
-                                                                 const uint64_t* __restrict__ off, uint64_t n0,
-                                                                 uint32_t* __restrict__ adj, uint32_t* __restrict__ flag) {
+// Compaction of the lists: the table rows of the survivors, through the remap, into the new CSRs (one wave per old
+// row and layer, blockIdx.y = layer).  A row of a node that lacks the layer is empty in the new CSR and is not
+// read.  A removed id left in a survivor's row raises the flag and is not written as an id out of range.
+__global__ __launch_bounds__(256) void table_to_csr_remap_kernel(const RemoveLayer* __restrict__ layers,
+                                                                 const uint32_t* __restrict__ levels,
+                                                                 const uint32_t* __restrict__ remap, uint64_t n0,
+                                                                 uint32_t* __restrict__ flag) {
   const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t lane = threadIdx.x & 63, layer = blockIdx.y;
   if (row >= n0) return;
   const uint32_t to = remap[row];
-  if (to == kGone) return;
-  const uint32_t dg = deg[row] < W ? deg[row] : W - 1;
+  if (to == kGone || (levels && levels[row] < layer)) return;
+  const RemoveLayer ly = layers[layer];
+  const uint32_t W = ly.M + 1;
+  const uint32_t dg = ly.deg[row] < W ? ly.deg[row] : ly.M;
+  const uint64_t at = ly.new_off[to];
   for (uint32_t i = lane; i < dg; i += 64) {
-    uint32_t id = remap[ell[row * W + i]];
+    uint32_t id = remap[ly.ell[row * W + i]];
     if (id == kGone) { atomicOr(flag, 1u); id = 0; }
-    adj[off[to] + i] = id;
+    ly.new_adj[at + i] = id;
   }
 }
 
@@ -672,23 +677,64 @@ void launch_select_diverse(uint32_t metric, uint32_t grid, size_t lds, const Bui
       hipLaunchKernelGGL(select_diverse_kernel<decltype(mc)::value>, dim3(grid), dim3(64), lds, 0, p);
   });
 }
-// one wave per touched node, the kernel instantiated for the index's metric, the rule and the row type
-void launch_repair(uint32_t metric, bool diverse, const isl::RowTable& rows, uint32_t grid, const RepairParams& p) {
-  const size_t lds = rows.is_bf16() ? isl_plan::repair_lds_bf16(p.d, p.m0) : isl_plan::repair_lds(kTileBytes, p.d, p.m0);
+}  // namespace
+
+namespace isl_build {
+
+// ---- what isl_index_remove and isl_hnsw_remove share
+size_t repair_lds(const isl::RowTable& rows, uint32_t widest) {
+  return rows.is_bf16() ? isl_plan::repair_lds_bf16((uint32_t)rows.d(), widest)
+                        : isl_plan::repair_lds(kTileBytes, (uint32_t)rows.d(), widest);
+}
+
+isl_status list_touched(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
+                        uint64_t n0, uint64_t* d_pairs, uint32_t cap, uint32_t* d_counts) {
+  hipLaunchKernelGGL(touched_kernel, dim3((uint32_t)((n0 + 3) / 4), layers), dim3(256), 0, 0, d_layers, d_levels, d_remap,
+                     n0, d_pairs, cap, d_counts);
+  if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "listing the touched nodes failed");
+  return ISL_OK;
+}
+
+// one wave per touched pair, the kernel instantiated for the graph's metric, the rule and the row type
+isl_status launch_repair(uint32_t metric, bool diverse, const isl::RowTable& rows, uint32_t grid, size_t lds,
+                         const RepairParams& p) {
   isl::by_metric(metric, [&](auto mc) {
     rows.with_row_type([&](auto row) {
       using T = decltype(row);
-      if constexpr (!std::is_same<T, isl::fp8_e4m3>::value) {  // (isl_index_remove refuses fp8 rows)
+      if constexpr (!std::is_same<T, isl::fp8_e4m3>::value) {  // (the removals refuse fp8 rows)
         if (diverse) hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, true, T>), dim3(grid), dim3(64), lds, 0, p);
         else hipLaunchKernelGGL((repair_kernel<decltype(mc)::value, false, T>), dim3(grid), dim3(64), lds, 0, p);
       }
     });
   });
+  if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "repair launch failed");
+  return ISL_OK;
 }
 
-}  // namespace
+isl_status compact_lists(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
+                         uint64_t n0, uint32_t* d_flag) {
+  hipLaunchKernelGGL(table_to_csr_remap_kernel, dim3((uint32_t)((n0 + 3) / 4), layers), dim3(256), 0, 0, d_layers,
+                     d_levels, d_remap, n0, d_flag);
+  if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "CSR compaction failed");
+  return ISL_OK;
+}
 
-namespace isl_build {
+isl_status gather_survivors(const isl::RowTable& rows, const uint32_t* d_surv, uint64_t n, isl::RowTable& out) {
+  if (out.allocate(rows.dtype(), n, rows.d()) != ISL_OK)
+    return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed for the rows of the shrunk graph");
+  const uint64_t es = isl_rows::elem_size(rows.dtype());
+  if (hipMemset(out.as<unsigned char>() + n * out.stride() * es, 0, (size_t)(isl_rows::slack(rows.dtype()) * es)) !=
+      hipSuccess)
+    return isl::fail(ISL_ERR_DEVICE, "hipMemset failed");
+  rows.with_row_type([&](auto row) {
+    using T = decltype(row);
+    if constexpr (!std::is_same<T, isl::fp8_e4m3>::value)
+      hipLaunchKernelGGL(gather_survivor_rows_kernel<T>, dim3((uint32_t)n), dim3(256), 0, 0, rows.as<const T>(),
+                         rows.stride(), rows.norm2(), d_surv, out.as<T>(), out.norm2());
+  });
+  if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "row compaction failed");
+  return ISL_OK;
+}
 
 isl_status check_build_options(const isl_build_options* o, bool need_rule) {
   using isl::fail;
@@ -992,13 +1038,16 @@ isl_status shrink_flat(const isl_build_options& opts, const isl_index* old, cons
   Table t{nullptr, nullptr, m0};
   ISL_TRY(c.alloc(&t.ell, n0 * (m0 + 1), true));
   ISL_TRY(c.alloc(&t.deg, n0, true));
-  uint32_t *d_flag = nullptr, *d_remap = nullptr, *d_surv = nullptr, *d_touched = nullptr;
+  uint32_t *d_flag = nullptr, *d_remap = nullptr, *d_surv = nullptr;
+  uint64_t* d_touched = nullptr;
   unsigned long long* d_total = nullptr;
-  ISL_TRY(c.alloc(&d_flag, 4, true));  // [0] import, [1] touched nodes, [2] compaction
+  isl_build::RemoveLayer* d_layer = nullptr;  // the one layer of a flat index
+  ISL_TRY(c.alloc(&d_flag, 4, true));  // [0] import, [1] touched nodes, [2] those of layer 0, [3] compaction
   ISL_TRY(c.alloc(&d_total, 1, true));
   ISL_TRY(c.alloc(&d_remap, n0));
   ISL_TRY(c.alloc(&d_surv, n));
-  ISL_TRY(c.alloc(&d_touched, n0));
+  ISL_TRY(c.alloc(&d_touched, n));
+  ISL_TRY(c.alloc(&d_layer, 1));
   // every list returns to the table in its stored order: an untouched row is finished with that copy
   ISL_TRY(c.csr_to_table(t, old->d_off, old->d_adj, old->nnz, n0, d_flag));
   uint32_t flag = 0;
@@ -1012,13 +1061,14 @@ isl_status shrink_flat(const isl_build_options& opts, const isl_index* old, cons
                              (unsigned long long)n0);
   if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the index's offsets do not fit its lists");
   // the CSR is in range from here on: the kernels below index by its ids
+  isl_build::RemoveLayer layer{old->d_off.get(), old->d_adj.get(), t.ell, t.deg, m0, 0u, nullptr, nullptr};
   if (hipMemcpy(d_remap, remap.data(), n0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_surv, survivors.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess)
+      hipMemcpy(d_surv, survivors.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_layer, &layer, sizeof(layer), hipMemcpyHostToDevice) != hipSuccess)
     return fail(ISL_ERR_DEVICE, "cannot upload the remap");
-  hipLaunchKernelGGL(touched_kernel, dim3((uint32_t)((n0 + 3) / 4)), dim3(256), 0, 0, old->d_off.get(), old->d_adj.get(),
-                     d_remap, n0, d_touched, d_flag + 1);
+  ISL_TRY(isl_build::list_touched(d_layer, 1, nullptr, d_remap, n0, d_touched, (uint32_t)n, d_flag + 1));
   uint32_t touched = 0;
-  if (hipGetLastError() != hipSuccess || hipMemcpy(&touched, d_flag + 1, 4, hipMemcpyDeviceToHost) != hipSuccess)
+  if (hipMemcpy(&touched, d_flag + 1, 4, hipMemcpyDeviceToHost) != hipSuccess)
     return fail(ISL_ERR_DEVICE, "listing the touched nodes failed");
   if (touched > n) return fail(ISL_ERR_DEVICE, "listing the touched nodes failed: %u of %llu survivors", touched,
                                (unsigned long long)n);
@@ -1026,15 +1076,18 @@ isl_status shrink_flat(const isl_build_options& opts, const isl_index* old, cons
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (debug && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
   if (touched) {
-    RepairParams p{};
+    isl_build::RepairParams p{};
     p.emb = rows.data(); p.norm2 = rows.norm2(); p.stride = rows.stride(); p.d = (uint32_t)rows.d();
     p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
-    p.off = old->d_off; p.adj = old->d_adj; p.remap = d_remap; p.touched = d_touched;
-    p.ell = t.ell; p.deg = t.deg; p.W = m0 + 1; p.m0 = m0; p.total = d_total;
+    p.layers = d_layer; p.levels = nullptr; p.remap = d_remap; p.touched = d_touched; p.total = d_total;
     if (ev0) (void)hipEventRecord(ev0, 0);
-    launch_repair(cfg.metric, opts.select_rule == ISL_SELECT_DIVERSE, rows, touched, p);
+    const isl_status launched = isl_build::launch_repair(cfg.metric, opts.select_rule == ISL_SELECT_DIVERSE, rows, touched,
+                                                         isl_build::repair_lds(rows, m0), p);
     if (ev1) (void)hipEventRecord(ev1, 0);
-    if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "repair launch failed");
+    if (launched != ISL_OK) {
+      if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
+      return launched;
+    }
   }
   // compaction: degrees of the survivors -> offsets (host scan, as table_to_csr), lists through the remap
   std::vector<uint32_t> hdeg(n0);
@@ -1055,29 +1108,19 @@ isl_status shrink_flat(const isl_build_options& opts, const isl_index* old, cons
   uint32_t* d_adj = nullptr;
   ISL_TRY(c.alloc(&d_off, n + 1));
   ISL_TRY(c.alloc(&d_adj, hoff[n]));
-  if (hipMemcpy(d_off, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
+  layer.new_off = d_off;
+  layer.new_adj = d_adj;
+  if (hipMemcpy(d_off, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_layer, &layer, sizeof(layer), hipMemcpyHostToDevice) != hipSuccess)
     return fail(ISL_ERR_DEVICE, "cannot upload the CSR offsets");
-  hipLaunchKernelGGL(table_to_csr_remap_kernel, dim3((uint32_t)((n0 + 3) / 4)), dim3(256), 0, 0, t.ell, t.deg, m0 + 1,
-                     d_remap, d_off, n0, d_adj, d_flag + 2);
-  if (hipGetLastError() != hipSuccess || hipMemcpy(&flag, d_flag + 2, 4, hipMemcpyDeviceToHost) != hipSuccess)
+  ISL_TRY(isl_build::compact_lists(d_layer, 1, nullptr, d_remap, n0, d_flag + 3));
+  if (hipMemcpy(&flag, d_flag + 3, 4, hipMemcpyDeviceToHost) != hipSuccess)
     return fail(ISL_ERR_DEVICE, "CSR compaction failed");
   if (flag) return fail(ISL_ERR_DEVICE, "isl_index_remove: a repaired list kept a removed id");
-  // rows and norms of the survivors, bit for bit, into a table of the same type (row_table.hpp has the layout)
+  // rows and norms of the survivors, bit for bit, into a table of the same type
   isl::RowTable shrunk;
-  if (shrunk.allocate(rows.dtype(), n, rows.d()) != ISL_OK)
-    return fail(ISL_ERR_DEVICE, "hipMalloc failed for the rows of the shrunk index");
-  const uint64_t es = isl_rows::elem_size(rows.dtype());
-  if (hipMemset(shrunk.as<unsigned char>() + n * shrunk.stride() * es, 0, (size_t)(isl_rows::slack(rows.dtype()) * es)) !=
-      hipSuccess)
-    return fail(ISL_ERR_DEVICE, "hipMemset failed");
-  rows.with_row_type([&](auto row) {
-    using T = decltype(row);
-    if constexpr (!std::is_same<T, isl::fp8_e4m3>::value)
-      hipLaunchKernelGGL(gather_survivor_rows_kernel<T>, dim3((uint32_t)n), dim3(256), 0, 0, rows.as<const T>(),
-                         rows.stride(), rows.norm2(), d_surv, shrunk.as<T>(), shrunk.norm2());
-  });
-  if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "row compaction failed");
+  ISL_TRY(isl_build::gather_survivors(rows, d_surv, n, shrunk));
+  if (hipDeviceSynchronize() != hipSuccess) return fail(ISL_ERR_DEVICE, "row compaction failed");
   const std::vector<uint64_t> old_levels = old->levels.size() == n0 ? old->levels : std::vector<uint64_t>();
   const isl_plan::Entry e = isl_plan::entry_after(old_levels, remap, survivors, old->has_entry, old->entry_point,
                                                   old->max_level);

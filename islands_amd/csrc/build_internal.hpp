@@ -109,4 +109,51 @@ struct Scaffold {
   isl_index* release();
 };
 
+// ---- what the two removals share (isl_index_remove in build.hip, isl_hnsw_remove in hnsw_build.hip; the kernels
+// are build.hip's).  A graph that shrinks is a set of layers -- one for a flat index -- each with its OLD CSR, the
+// table its lists return to and, once the repaired degrees are known, the CSR of the survivors.  The kernels read
+// an array of these in device memory and take the layer from blockIdx.y or from the touched pair.
+struct RemoveLayer {
+  const uint64_t* off;      // the OLD CSR over the old ids: every list is computed from the old lists only
+  const uint32_t* adj;
+  uint32_t* ell;            // [n0][M + 1] the table: a touched row is written by its wave alone, never read
+  uint32_t* deg;            // [n0]
+  uint32_t M;               // ids a row of this layer keeps
+  uint32_t reserved;
+  const uint64_t* new_off;  // [n + 1] the survivors' CSR over the new ids (compact_lists)
+  uint32_t* new_adj;
+};
+
+struct RepairParams {
+  const void* emb;            // the OLD rows, by old id
+  const float* norm2;
+  uint64_t stride;
+  uint32_t d;
+  float alpha;
+  uint32_t keep_pruned;
+  const RemoveLayer* layers;  // device array
+  const uint32_t* levels;     // [n0] HnswGraph: a node has layer L iff levels[node] >= L; NULL: every node has every layer
+  const uint32_t* remap;      // [n0] new id or isl_plan::kGone
+  const uint64_t* touched;    // [grid] isl_plan::touched_pair
+  unsigned long long* total;  // [1] sum of |C(p)| over the touched pairs
+};
+
+// LDS of a repair launch whose widest layer keeps `widest` ids, for the rows' stored type
+size_t repair_lds(const isl::RowTable& rows, uint32_t widest);
+// The launches below return once the kernel is enqueued on the default stream.
+// (layer, node) pairs of the survivors that lost a neighbour, all layers in one launch: d_counts [1 + layers],
+// zeroed by the caller, receives the number of pairs and the pairs per layer; at most `cap` pairs are written.
+isl_status list_touched(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
+                        uint64_t n0, uint64_t* d_pairs, uint32_t cap, uint32_t* d_counts);
+// one wave per pair rebuilds the pair's table row
+isl_status launch_repair(uint32_t metric, bool diverse, const isl::RowTable& rows, uint32_t grid, size_t lds,
+                         const RepairParams& p);
+// the tables of layers 0 .. layers-1 -> their new CSRs through the remap, one launch; *d_flag (zeroed by the caller)
+// is raised by a removed id left in a survivor's row
+isl_status compact_lists(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
+                         uint64_t n0, uint32_t* d_flag);
+// rows and norms of the n survivors d_surv[] (old ids, ascending), bit for bit, into `out`, a fresh table of the
+// same stored type (row_table.hpp has the layout)
+isl_status gather_survivors(const isl::RowTable& rows, const uint32_t* d_surv, uint64_t n, isl::RowTable& out);
+
 }  // namespace isl_build

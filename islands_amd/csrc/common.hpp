@@ -96,6 +96,8 @@ struct SearchWorkspace {
   PinnedBuffer<uint32_t> h_count;
   hipStream_t stream = nullptr;  // from the device's stream pool (search.hip): shared, never destroyed here
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_in = nullptr, ev_done = nullptr;
+  float launch_ms = 0.0f;        // ev0 .. ev1 of the launch last enqueued here, once a wait has read it (search_finish)
+  bool launch_ms_read = false;
   // call in flight on this lane (claim .. release)
   bool busy = false;           // under isl_index::mu
   bool waiting = false;        // a thread is inside isl_search_wait for this lane (under mu)

@@ -432,6 +432,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   if (!ws.ticket_clean) ISL_HIP(hipMemsetAsync(ws.ticket, 0, 64, st));
   ws.ticket_clean = false;
   ISL_HIP(hipEventRecord(ws.ev0, st));
+  ws.launch_ms_read = false;
   if (resume && !tl && plan.exact) {
     hipLaunchKernelGGL(seed_redo_kernel, dim3(1), dim3(256), 0, st, ws.h_xlist, plan.exact, ws.redo, ws.ticket);
     ISL_HIP(hipGetLastError());
@@ -573,14 +574,24 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
   const uint64_t nq = ws.nq_inflight;
   const bool use_fast = ws.fast_inflight;
   // a member of a group launch: that launch's events (the scatter kernel has filled this lane's mirrors)
-  const isl::SearchWorkspace& lw = ws.grp_launch ? *ws.grp_launch : ws;
+  isl::SearchWorkspace& lw = ws.grp_launch ? *ws.grp_launch : ws;
   ISL_HIP(hipEventSynchronize(lw.ev_done));
   const uint32_t* status = ws.h_status;
   const uint32_t* ctr = ws.h_ctr;
   const uint32_t* head = ws.h_head;
   isl::DeviceBuffer<uint64_t> d_prof = std::move(ws.d_prof);
+  // The launch's time is read from its events once and kept with the launch: every member of a group launch
+  // reports that one figure (two reads of the same event pair may differ in the last bit).
   float ms = 0.0f;
-  (void)hipEventElapsedTime(&ms, lw.ev0, lw.ev1);
+  {
+    static std::mutex ms_mu;
+    std::lock_guard<std::mutex> lock(ms_mu);
+    if (!lw.launch_ms_read) {
+      (void)hipEventElapsedTime(&lw.launch_ms, lw.ev0, lw.ev1);
+      lw.launch_ms_read = true;
+    }
+    ms = lw.launch_ms;
+  }
 
   isl_search_stats& ss = ws.stats;
   ss = isl_search_stats{};
