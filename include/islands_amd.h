@@ -451,6 +451,12 @@ isl_status isl_search_stream_wait(const isl_index* idx, uint64_t token, void* st
  * no such call has reached.  Any of the pointers may be NULL. */
 isl_status isl_index_group_counters(const isl_index* idx, uint64_t* launches, uint64_t* shared_launches,
                                     uint64_t* shared_calls);
+/* The calls the group path took so far, and those of them that found work pending on their caller's stream
+ * and put a marker (an event record) on it, for their launch to wait for.  A call whose caller's stream has
+ * nothing pending puts none: in a process of few hardware queues the caller's stream shares a queue with the
+ * library's launches, and a marker in it is reached only after the kernel in front of it has ended.
+ * ISL_GROUP_MARK=1 marks every call.  Either pointer may be NULL. */
+isl_status isl_index_group_markers(const isl_index* idx, uint64_t* calls, uint64_t* marked_calls);
 /* LeannIndex::search, leann.rs:858-865: one query, ef = config.ef_search. */
 isl_status isl_search(const isl_index* idx, const float* query, uint64_t d, uint64_t k,
                       uint64_t* out_ids, float* out_dist, uint32_t* out_count);

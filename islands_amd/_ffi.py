@@ -120,6 +120,7 @@ SIGNATURES = {
     "isl_search_wait": (i32, [C.c_void_p, u64]),
     "isl_search_stream_wait": (i32, [C.c_void_p, u64, C.c_void_p]),
     "isl_index_group_counters": (i32, [C.c_void_p, P(u64), P(u64), P(u64)]),
+    "isl_index_group_markers": (i32, [C.c_void_p, P(u64), P(u64)]),
     "isl_shard_record_bytes": (u64, [u64, u64]),
     "isl_merge_topk_packed_async": (i32, [u64, u64, u64, C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, i32, C.c_void_p]),

@@ -162,6 +162,7 @@ struct SearchWorkspace {
   SearchWorkspace* grp_launch = nullptr;   // the group workspace whose launch answers it (NULL: held, or alone on this lane)
   uint32_t grp_offset = 0;                 // its first query in that launch's union
   hipEvent_t grp_ready = nullptr;          // recorded behind the last kernel that writes the call's outputs
+  bool grp_marked = false;                 // ev_in is on the caller's stream: the call's launch waits for it
   uint64_t grp_allocs = 0;                 // what the launch's workspace had to set up (isl_search_stats::allocations)
   bool grp_failed = false;                 // the launch could not be enqueued: the wait returns grp_status / grp_error
   isl_status grp_status = ISL_OK;
@@ -186,8 +187,10 @@ constexpr int kGroupBelowQueues = 8;
 // ISL_NO_GROUP=1: no call waits for company (one launch per call, as before the group path existed), =0: calls do
 // whatever the queues are, unset: by the queues; ISL_GROUP_CAP=<queries>: the most one launch takes;
 // ISL_GROUP_ROOM=<queries>: stands in for the resident waves in "is there room on the chip" (small tests force
-// holding with it).  0 = not set.
-struct GroupSwitches { bool off; uint32_t cap, room; };
+// holding with it).  0 = not set.  ISL_GROUP_MARK=1: every call of the group path puts its marker on the caller's
+// stream, also where that stream has nothing pending (measurements: what the marker costs);
+// ISL_GROUP_TRACE=1: one stderr line per arrival, launch and observed completion, with host clocks.
+struct GroupSwitches { bool off; uint32_t cap, room; bool mark_always, trace; };
 inline GroupSwitches group_switches() {
   auto num = [](const char* name) -> uint32_t {
     const char* e = getenv(name);
@@ -196,7 +199,8 @@ inline GroupSwitches group_switches() {
   };
   const char* off = getenv("ISL_NO_GROUP");
   const bool is_off = (off && *off) ? strcmp(off, "0") != 0 : hw_queues_at_load() >= kGroupBelowQueues;
-  return GroupSwitches{is_off, num("ISL_GROUP_CAP"), num("ISL_GROUP_ROOM")};
+  return GroupSwitches{is_off, num("ISL_GROUP_CAP"), num("ISL_GROUP_ROOM"), num("ISL_GROUP_MARK") != 0,
+                       num("ISL_GROUP_TRACE") != 0};
 }
 struct GroupState;  // search_group.hip
 

@@ -3,8 +3,9 @@
 // The rules (who may share, when a call is held, how a held set is cut) are search_group_plan.hpp; this unit is
 // their host side and two small kernels.  Everything here is host-driven: nothing waits or spins on the device,
 // there is no host thread and no callback.  A group launch is
-//   1. group_gather_kernel: the members' query blocks -> the group workspace's contiguous buffer, behind every
-//      member's ev_in (recorded on the caller's stream when the call arrived, so the order after it is kept);
+//   1. group_gather_kernel: the members' query blocks -> the group workspace's contiguous buffer, behind the ev_in
+//      of every member that found work pending on its caller's stream (recorded there when the call arrived, so
+//      the order after it is kept; a call from an idle stream records nothing: group_arrive);
 //   2. search_enqueue, unchanged, over the union (queries, nq, staged outputs of the group workspace);
 //   3. group_scatter_kernel: each member's ids, distances and counts into that member's own output pointers,
 //      its statuses and counters into its lane's pinned mirrors, its share of the launch's exact-path and
@@ -12,6 +13,8 @@
 // A member keeps its lane and token; search_finish waits on the launch's event and reads the member's mirrors.
 // A launch of ONE call does not come here at all: it runs on the call's own lane through search_enqueue, as an
 // ungrouped call does.
+#include <cstdarg>
+#include <ctime>
 #include <memory>
 
 #include "search_geometry.hpp"
@@ -27,6 +30,8 @@ struct GroupState {
   std::vector<std::unique_ptr<SearchWorkspace>> slots;  // group workspaces (stable addresses)
   SearchCall calls[kSearchLanes];                       // the call of every lane the group path holds
   uint64_t launches = 0, shared_launches = 0, shared_calls = 0;  // isl_index_group_counters
+  uint64_t arrived_calls = 0, marked_calls = 0;                  // isl_index_group_markers
+  uint32_t launch_of[kSearchLanes] = {};                         // ISL_GROUP_TRACE: the launch a lane's call went out in
 };
 
 }  // namespace isl
@@ -167,6 +172,21 @@ __global__ void zero_u32_kernel(uint32_t* p, uint32_t n) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
 }
 
+// ISL_GROUP_TRACE: one stderr line with the host's clocks in front -- the boot-time clock is the one a kernel trace's
+// timestamps are on, the monotonic one is the interpreter's perf_counter
+void trace_line(const char* fmt, ...) {
+  timespec b{}, m{};
+  clock_gettime(CLOCK_BOOTTIME, &b);
+  clock_gettime(CLOCK_MONOTONIC, &m);
+  char text[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(text, sizeof text, fmt, ap);
+  va_end(ap);
+  fprintf(stderr, "isl group-trace boot_ns=%lld mono_ns=%lld %s\n", (long long)b.tv_sec * 1000000000ll + b.tv_nsec,
+          (long long)m.tv_sec * 1000000000ll + m.tv_nsec, text);
+}
+
 uint32_t group_cap(const isl_index* idx) { return idx->group_sw.cap ? idx->group_sw.cap : isl_group::kDefaultCap; }
 
 isl::GroupState& state_of(const isl_index* idx) {  // under idx->group_mu
@@ -217,7 +237,8 @@ isl_status enqueue_alone(const isl_index* idx, isl::GroupState& g, const isl_gro
   isl::SearchWorkspace& ws = idx->ws[lane_no];
   SearchCall c = g.calls[lane_no];
   c.user_stream = nullptr;
-  c.mode = StreamMode::OWN_AFTER_EVENT;  // behind ev_in, recorded on the caller's stream when the call arrived
+  // behind ev_in where the call put it on the caller's stream when it arrived
+  c.mode = ws.grp_marked ? StreamMode::OWN_AFTER_EVENT : StreamMode::OWN;
   ISL_TRY(search_enqueue(idx, ws, c));
   ws.grp_launch = nullptr;
   ws.grp_offset = 0;
@@ -245,7 +266,7 @@ isl_status enqueue_group_impl(const isl_index* idx, isl::GroupState& g, const is
     ISL_TRY(ws.h_status.reserve(std::max<uint64_t>(mb.nq, 1024), &ws.alloc_events));
     ISL_TRY(ws.h_ctr.reserve(std::max<uint64_t>(mb.nq, 1024) * 4, &ws.alloc_events));
     tab[i] = GroupMember{c.queries, c.ids, c.dist, c.count, ws.h_status, ws.h_ctr, ws.h_head, mb.offset, mb.nq};
-    ISL_HIP(hipStreamWaitEvent(gw.stream, ws.ev_in, 0));
+    if (ws.grp_marked) ISL_HIP(hipStreamWaitEvent(gw.stream, ws.ev_in, 0));
   }
   hipLaunchKernelGGL(group_gather_kernel, dim3(64, nm), dim3(256), 0, gw.stream, tab, gw.q_stage.get(), (uint32_t)d);
   ISL_HIP(hipGetLastError());
@@ -317,8 +338,18 @@ void poll(const isl_index* idx, isl::GroupState& g) {
   for (const isl_group::Planner::Live& l : g.plan.live()) {
     hipEvent_t ev = l.workspace >= 0 ? g.slots[l.workspace]->ev_done : idx->ws[l.first_call].ev_done;
     const hipError_t e = hipEventQuery(ev);
+    if (e != hipSuccess) (void)hipGetLastError();  // hipErrorNotReady
+    if (idx->group_sw.trace) {
+      uint32_t marks = 0, marks_pending = 0;  // the members' markers on their callers' streams, and those not yet reached
+      for (int i = 0; i < isl::kSearchLanes; ++i) {
+        const isl::SearchWorkspace& ws = idx->ws[i];
+        if (g.launch_of[i] != l.id || !ws.grp || !ws.grp_marked) continue;
+        marks += 1;
+        if (hipEventQuery(ws.ev_in) != hipSuccess) { (void)hipGetLastError(); marks_pending += 1; }
+      }
+      trace_line("poll launch=%u done=%d markers=%u markers_pending=%u", l.id, e == hipSuccess ? 1 : 0, marks, marks_pending);
+    }
     if (e == hipSuccess) g.plan.complete(l.id);
-    else (void)hipGetLastError();  // hipErrorNotReady
   }
 }
 
@@ -330,6 +361,20 @@ void submit(const isl_index* idx, isl::GroupState& g, uint32_t wanted) {
     if (wanted != isl_group::kNone && !g.plan.held(wanted)) wanted = isl_group::kNone;
     if (!g.plan.next(wanted, L)) break;
     const isl_status st = L.workspace < 0 ? enqueue_alone(idx, g, L) : enqueue_group(idx, g, L);
+    if (idx->group_sw.trace) {
+      char calls[256];
+      int at = 0;
+      uint32_t marks = 0;
+      for (const isl_group::Member& mb : L.members) {
+        g.launch_of[mb.call] = L.id;
+        marks += idx->ws[mb.call].grp_marked ? 1u : 0u;
+        if (at < (int)sizeof calls - 12) at += snprintf(calls + at, sizeof calls - at, "%s%u", at ? "," : "", mb.call);
+      }
+      hipStream_t on = L.workspace < 0 ? idx->ws[L.members[0].call].stream : g.slots[L.workspace]->stream;
+      trace_line("launch id=%u status=%d workspace=%d queries=%u lanes=%s markers=%u stream=%p wanted=%d inflight=%llu",
+                 L.id, (int)st, L.workspace, L.nq, calls, marks, (void*)on, wanted == isl_group::kNone ? -1 : (int)wanted,
+                 (unsigned long long)g.plan.inflight());
+    }
     if (st == ISL_OK) {
       g.launches += 1;
       if (L.workspace >= 0) { g.shared_launches += 1; g.shared_calls += L.members.size(); }
@@ -366,13 +411,26 @@ isl_status isl_lane::group_arrive(const isl_index* idx, isl::SearchWorkspace& ws
   CallGeometry cg;
   ISL_TRY(call_geometry(idx, c.d, c.k, c.ef, nullptr, cg));
   ISL_TRY(ensure_lane_stream(idx, ws));
-  ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));  // the call is ordered after the caller's stream as of now
+  // The call is ordered after the caller's stream as of now.  A stream with nothing pending orders nothing, and
+  // then no marker goes on it: the caller's stream shares its hardware queue with launch streams, and a marker in
+  // that queue is reached only when the traversal kernel in front of it has ended -- every launch that waits for
+  // it starts milliseconds late, on whichever queue it sits itself.
+  bool marked = idx->group_sw.mark_always;
+  if (!marked && hipStreamQuery(c.user_stream) != hipSuccess) {
+    (void)hipGetLastError();  // pending work (or a stream that cannot be asked): the marker, as for any other order
+    marked = true;
+  }
+  if (marked) ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));
   const uint32_t lane_no = (uint32_t)(&ws - idx->ws);
   std::lock_guard<std::mutex> lock(idx->group_mu);
   isl::GroupState& g = state_of(idx);
   if (g.slots.empty()) grow_slots(idx, g, isl::kSearchLanes / 2);  // not prepared: workspaces come as launches need them
   g.calls[lane_no] = c;
+  g.arrived_calls += 1;
+  g.marked_calls += marked ? 1 : 0;
+  if (idx->group_sw.trace) trace_line("arrive lane=%u queries=%llu marker=%d", lane_no, (unsigned long long)c.nq, marked ? 1 : 0);
   ws.grp = true;
+  ws.grp_marked = marked;
   ws.grp_failed = false;
   ws.grp_launch = nullptr;
   ws.grp_allocs = 0;
@@ -487,6 +545,15 @@ extern "C" isl_status isl_index_group_counters(const isl_index* idx, uint64_t* l
   if (launches) *launches = g ? g->launches : 0;
   if (shared_launches) *shared_launches = g ? g->shared_launches : 0;
   if (shared_calls) *shared_calls = g ? g->shared_calls : 0;
+  return ISL_OK;
+}
+
+extern "C" isl_status isl_index_group_markers(const isl_index* idx, uint64_t* calls, uint64_t* marked_calls) {
+  if (!idx) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "index is NULL");
+  std::lock_guard<std::mutex> lock(idx->group_mu);
+  const isl::GroupState* g = idx->group;
+  if (calls) *calls = g ? g->arrived_calls : 0;
+  if (marked_calls) *marked_calls = g ? g->marked_calls : 0;
   return ISL_OK;
 }
 
