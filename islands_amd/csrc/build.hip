@@ -24,13 +24,14 @@
 // rows, and the grown graph, built beside the old one, moves into the caller's handle at the end (adopt_grown).
 // Build and insert are argument checks around one function, grow_flat.
 //
-// isl_index_remove takes nodes out of a finished index, in place (shrink_flat): the lists return to the same table,
-// one wave per survivor that lost a neighbour rebuilds its row from the OLD CSR (repair_kernel: the removed
-// neighbours' own lists stand in for them; past m0 ids the builder's sort and selection decide), and the survivors'
-// lists, rows and norms are compacted into a graph built beside the old one, which moves in as a grown one does.
-// The remap, the entry-point rule and the LDS size are remove_plan.hpp's.  The removal kernels read their graph as
-// an array of layers (RemoveLayer, build_internal.hpp) -- one for a flat index -- and are launched through isl_build,
-// so that isl_hnsw_remove (hnsw_build.hip) runs the same kernels over every layer of an HnswGraph in one pass.
+// isl_index_remove takes nodes out of a finished index, in place: the lists return to the same table, one wave per
+// survivor that lost a neighbour rebuilds its row from the OLD CSR (repair_kernel: the removed neighbours' own lists
+// stand in for them; past m0 ids the builder's sort and selection decide), and the survivors' lists, rows and norms
+// are compacted into a graph built beside the old one, which moves in as a grown one does.  The remap, the
+// entry-point rule and the LDS size are remove_plan.hpp's.  The removal kernels read their graph as an array of
+// layers (RemoveLayer, build_internal.hpp) -- one for a flat index -- and one host routine drives them
+// (isl_build::shrink_import / shrink_finish, below the kernels): isl_index_remove calls it with its one layer,
+// isl_hnsw_remove (hnsw_build.hip) with every layer of an HnswGraph, and each makes its own handle from the result.
 //
 // The HnswGraph builder (hnsw_build.hip) runs the same selection kernels and link_kernel's HNSW mode
 // over one fixed-width table per layer.  Both go through one host path, isl_build::Scaffold
@@ -677,16 +678,17 @@ void launch_select_diverse(uint32_t metric, uint32_t grid, size_t lds, const Bui
       hipLaunchKernelGGL(select_diverse_kernel<decltype(mc)::value>, dim3(grid), dim3(64), lds, 0, p);
   });
 }
-}  // namespace
 
-namespace isl_build {
-
-// ---- what isl_index_remove and isl_hnsw_remove share
+// ---- the launches of a removal (shrink_finish below).  Each returns once the kernel is enqueued on the default
+// stream.
+// LDS of a repair launch whose widest layer keeps `widest` ids, for the rows' stored type
 size_t repair_lds(const isl::RowTable& rows, uint32_t widest) {
   return rows.is_bf16() ? isl_plan::repair_lds_bf16((uint32_t)rows.d(), widest)
                         : isl_plan::repair_lds(kTileBytes, (uint32_t)rows.d(), widest);
 }
 
+// (layer, node) pairs of the survivors that lost a neighbour, all layers in one launch: d_counts [1 + layers],
+// zeroed by the caller, receives the number of pairs and the pairs per layer; at most `cap` pairs are written.
 isl_status list_touched(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
                         uint64_t n0, uint64_t* d_pairs, uint32_t cap, uint32_t* d_counts) {
   hipLaunchKernelGGL(touched_kernel, dim3((uint32_t)((n0 + 3) / 4), layers), dim3(256), 0, 0, d_layers, d_levels, d_remap,
@@ -711,6 +713,8 @@ isl_status launch_repair(uint32_t metric, bool diverse, const isl::RowTable& row
   return ISL_OK;
 }
 
+// the tables of layers 0 .. layers-1 -> their new CSRs through the remap, one launch; *d_flag (zeroed by the caller)
+// is raised by a removed id left in a survivor's row
 isl_status compact_lists(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
                          uint64_t n0, uint32_t* d_flag) {
   hipLaunchKernelGGL(table_to_csr_remap_kernel, dim3((uint32_t)((n0 + 3) / 4), layers), dim3(256), 0, 0, d_layers,
@@ -719,6 +723,8 @@ isl_status compact_lists(const RemoveLayer* d_layers, uint32_t layers, const uin
   return ISL_OK;
 }
 
+// rows and norms of the n survivors d_surv[] (old ids, ascending), bit for bit, into `out`, a fresh table of the
+// same stored type (row_table.hpp has the layout)
 isl_status gather_survivors(const isl::RowTable& rows, const uint32_t* d_surv, uint64_t n, isl::RowTable& out) {
   if (out.allocate(rows.dtype(), n, rows.d()) != ISL_OK)
     return isl::fail(ISL_ERR_DEVICE, "hipMalloc failed for the rows of the shrunk graph");
@@ -735,7 +741,138 @@ isl_status gather_survivors(const isl::RowTable& rows, const uint32_t* d_surv, u
   if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "row compaction failed");
   return ISL_OK;
 }
+}  // namespace
 
+namespace isl_build {
+
+isl_status shrink_import(Scaffold& c, const std::vector<ShrinkLayer>& layers, uint64_t n0, ShrinkTables& t) {
+  t.ly.resize(layers.size());
+  ISL_TRY(c.alloc(&t.d_deg, layers.size() * n0, true));
+  ISL_TRY(c.alloc(&t.d_flag, 3 + layers.size(), true));
+  for (uint64_t L = 0; L < layers.size(); ++L) {
+    const ShrinkLayer& in = layers[L];
+    Table tab{nullptr, t.d_deg + L * n0, in.M};
+    ISL_TRY(c.alloc(&tab.ell, n0 * (tab.M + 1)));
+    t.ly[L] = RemoveLayer{in.off, in.adj, tab.ell, tab.deg, tab.M, 0u, nullptr, nullptr};
+    ISL_TRY(c.csr_to_table(tab, in.off, in.adj, in.nnz, n0, t.d_flag));
+  }
+  return ISL_OK;
+}
+
+isl_status shrink_finish(Scaffold& c, ShrinkTables& t, const isl::RowTable& old_rows, uint32_t metric,
+                         const isl_build_options& opts, const std::vector<uint32_t>& remap,
+                         const std::vector<uint32_t>& survivors, const std::vector<uint64_t>& levels, bool has_entry,
+                         uint64_t entry, uint64_t max_level, bool levels_name_layers, const char* call, Shrunk& out) {
+  using isl::fail;
+  const uint64_t n0 = remap.size(), n = survivors.size(), layers = t.ly.size();
+  std::vector<RemoveLayer>& ly = t.ly;
+  out.entry = isl_plan::entry_after(levels, remap, survivors, has_entry, entry, max_level);
+  // the layers above the new max_level cease to exist; layers that every node has all stay
+  const uint64_t kept_layers = levels_name_layers ? isl_plan::layers_after(out.entry) : layers;
+  // the rows that can hold a list bound the touched pairs
+  const uint64_t pair_cap =
+      levels_name_layers ? isl_plan::touched_capacity(isl_plan::layer_members(levels, survivors, layers)) : layers * n;
+  if (pair_cap > 0xFFFFFFFFull) return fail(ISL_ERR_UNSUPPORTED, "%s: more than 2^32 lists", call);
+  uint32_t widest = 0;
+  for (const RemoveLayer& l : ly) widest = std::max(widest, l.M);
+
+  uint32_t *d_counts = t.d_flag + 2, *d_remap = nullptr, *d_surv = nullptr, *d_lv = nullptr;
+  uint64_t* d_pairs = nullptr;
+  unsigned long long* d_total = nullptr;
+  RemoveLayer* d_ly = nullptr;
+  ISL_TRY(c.alloc(&d_total, 1, true));
+  ISL_TRY(c.alloc(&d_remap, n0));
+  ISL_TRY(c.alloc(&d_surv, n));
+  ISL_TRY(c.alloc(&d_pairs, pair_cap));
+  ISL_TRY(c.alloc(&d_ly, layers));
+  std::vector<uint32_t> lv;  // what the kernels read "node has layer L" from; none: d_lv stays NULL
+  if (levels_name_layers) {
+    lv.assign(levels.begin(), levels.end());
+    ISL_TRY(c.alloc(&d_lv, n0));
+  }
+  if (hipMemcpy(d_remap, remap.data(), n0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_surv, survivors.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      (d_lv && hipMemcpy(d_lv, lv.data(), n0 * 4, hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(d_ly, ly.data(), layers * sizeof(RemoveLayer), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "cannot upload the remap");
+  ISL_TRY(list_touched(d_ly, (uint32_t)layers, d_lv, d_remap, n0, d_pairs, (uint32_t)pair_cap, d_counts));
+  out.counts.assign(layers + 1, 0);
+  if (hipMemcpy(out.counts.data(), d_counts, (layers + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "listing the touched lists failed");
+  const uint32_t touched = out.counts[0];
+  if (touched > pair_cap)
+    return fail(ISL_ERR_DEVICE, "listing the touched lists failed: %u of %llu lists", touched, (unsigned long long)pair_cap);
+  const bool debug = getenv("ISL_DEBUG") != nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (debug && touched && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
+  isl_status launched = ISL_OK;
+  if (touched) {
+    RepairParams p{};
+    p.emb = old_rows.data(); p.norm2 = old_rows.norm2(); p.stride = old_rows.stride(); p.d = (uint32_t)old_rows.d();
+    p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
+    p.layers = d_ly; p.levels = d_lv; p.remap = d_remap; p.touched = d_pairs; p.total = d_total;
+    if (ev0) (void)hipEventRecord(ev0, 0);
+    launched = launch_repair(metric, opts.select_rule == ISL_SELECT_DIVERSE, old_rows, touched,
+                             repair_lds(old_rows, widest), p);
+    if (ev1) (void)hipEventRecord(ev1, 0);
+  }
+  // the repaired degrees of every layer -> the offsets of the layers that are left (host scan, as table_to_csr)
+  std::vector<uint32_t> hdeg(layers * n0);
+  const bool read =
+      launched == ISL_OK && hipMemcpy(hdeg.data(), t.d_deg, layers * n0 * 4, hipMemcpyDeviceToHost) == hipSuccess;
+  if (debug && read) {
+    (void)hipMemcpy(&out.candidates, d_total, 8, hipMemcpyDeviceToHost);
+    if (ev0) (void)hipEventElapsedTime(&out.repair_ms, ev0, ev1);
+  }
+  if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
+  ISL_TRY(launched);
+  if (!read) return fail(ISL_ERR_DEVICE, "repair kernel failed");
+  // layer 0: its own arrays (the core index copies them); the layers above: one block of offsets over ALL new
+  // ids (a node below a layer has an empty row there, isl_hnsw_from_layers' shape) and one of ids, kept
+  std::vector<uint64_t> hoff(kept_layers * (n + 1), 0);
+  for (uint64_t L = 0; L < kept_layers; ++L) {
+    uint64_t* o = hoff.data() + L * (n + 1);
+    for (uint64_t i = 0; i < n; ++i) {
+      const uint32_t s = survivors[i];
+      o[i + 1] = o[i] + ((!d_lv || lv[s] >= L) ? std::min(hdeg[L * n0 + s], ly[L].M) : 0u);
+    }
+  }
+  uint64_t upper_nnz = 0;
+  for (uint64_t L = 1; L < kept_layers; ++L) upper_nnz += hoff[L * (n + 1) + n];
+  uint64_t *d_off0 = nullptr, *d_off_up = nullptr;
+  uint32_t *d_adj0 = nullptr, *d_adj_up = nullptr;
+  ISL_TRY(c.alloc(&d_off0, n + 1));
+  ISL_TRY(c.alloc(&d_adj0, hoff[n]));
+  if (kept_layers > 1) {
+    ISL_TRY(c.alloc(&d_off_up, (kept_layers - 1) * (n + 1), false, true));
+    ISL_TRY(c.alloc(&d_adj_up, upper_nnz, false, true));
+  }
+  out.off.assign(kept_layers, nullptr);
+  out.adj.assign(kept_layers, nullptr);
+  out.off[0] = ly[0].new_off = d_off0;
+  out.adj[0] = ly[0].new_adj = d_adj0;
+  for (uint64_t L = 1, at = 0; L < kept_layers; ++L) {
+    out.off[L] = ly[L].new_off = d_off_up + (L - 1) * (n + 1);
+    out.adj[L] = ly[L].new_adj = d_adj_up + at;
+    at += hoff[L * (n + 1) + n];
+  }
+  if (hipMemcpy(d_off0, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
+      (kept_layers > 1 && hipMemcpy(d_off_up, hoff.data() + (n + 1), (kept_layers - 1) * (n + 1) * 8,
+                                    hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(d_ly, ly.data(), layers * sizeof(RemoveLayer), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "cannot upload the CSR offsets");
+  ISL_TRY(compact_lists(d_ly, (uint32_t)kept_layers, d_lv, d_remap, n0, t.d_flag + 1));
+  ISL_TRY(gather_survivors(old_rows, d_surv, n, out.rows));
+  uint32_t flag = 0;
+  if (hipMemcpy(&flag, t.d_flag + 1, 4, hipMemcpyDeviceToHost) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "compaction failed");
+  if (flag) return fail(ISL_ERR_DEVICE, "%s: a repaired list kept a removed id", call);
+  out.levels = isl_plan::levels_after(levels, survivors);
+  return ISL_OK;
+}
+
+namespace {
+// struct_size, rule and alpha of caller-supplied options
 isl_status check_build_options(const isl_build_options* o, bool need_rule) {
   using isl::fail;
   if (o->struct_size < sizeof(isl_build_options))
@@ -746,6 +883,27 @@ isl_status check_build_options(const isl_build_options* o, bool need_rule) {
   if ((!need_rule || o->select_rule == ISL_SELECT_DIVERSE) && !(std::isfinite(o->alpha) && o->alpha >= 1.0f))
     return fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: alpha must be finite and >= 1");
   return ISL_OK;
+}
+}  // namespace
+
+isl_status resolve_build_options(const isl_build_options* in, bool need_rule, isl_build_options& out) {
+  isl_build_options_default(&out);
+  if (in) {
+    ISL_TRY(check_build_options(in, need_rule));
+    out = *in;
+  }
+  return ISL_OK;
+}
+
+bool device_lists_differ(const isl_index* idx) {
+  return idx->host_csr_valid && idx->node_offsets.size() == idx->num_nodes + 1 &&
+         idx->node_offsets[idx->num_nodes] != idx->nnz;
+}
+
+void write_remap(const std::vector<uint32_t>* remap, uint64_t n0, uint64_t* out_remap) {
+  if (!out_remap) return;
+  for (uint64_t i = 0; i < n0; ++i)
+    out_remap[i] = !remap ? i : (*remap)[i] == isl_plan::kGone ? ISL_REMOVED : (uint64_t)(*remap)[i];
 }
 
 size_t link_lds(uint64_t d) { return isl_plan::link_lds(kTileBytes, (uint32_t)d); }
@@ -904,6 +1062,24 @@ extern "C" isl_status isl_index_build_ex(const isl_leann_config* cfg, const isl_
 
 namespace {
 
+// What `call` (isl_index_insert, isl_index_remove) refuses once the lists of `old` have returned to a table:
+// *d_flag holds Scaffold::csr_to_table's bits, read here once.  Past this the CSR is in range.
+isl_status check_import(const char* call, const uint32_t* d_flag, const isl_index* old) {
+  using isl::fail;
+  uint32_t flag = 0;
+  if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "importing the index's lists failed");
+  if (flag & 1u)
+    return fail(ISL_ERR_UNSUPPORTED, "%s: the index has a list longer than m0 = %u", call, (uint32_t)old->cfg.m0);
+  if (isl_build::device_lists_differ(old))
+    return fail(ISL_ERR_UNSUPPORTED, "%s: the device copy of the graph is not the lists verbatim (ids repeated inside a "
+                "list were removed at upload)", call);
+  if (flag & 4u) return fail(ISL_ERR_UNSUPPORTED, "%s: a list names an id that is not below len = %llu", call,
+                             (unsigned long long)old->num_nodes);
+  if (flag) return fail(ISL_ERR_UNSUPPORTED, "%s: the index's offsets do not fit its lists", call);
+  return ISL_OK;
+}
+
 // LeannIndex::build (leann.rs:578-615) for nodes n0 .. n-1 of a graph that holds n0 (`old`: a finished index
 // with resident rows of `dtype`, whose CSR returns to the builder's table in its stored order and whose
 // entry_point / max_level the loop continues from; NULL: nothing, node 0 starts the graph).  One loop over the
@@ -938,17 +1114,7 @@ isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts,
     uint32_t* d_flag = nullptr;
     ISL_TRY(c.alloc(&d_flag, 1, true));
     ISL_TRY(c.csr_to_table(t, old->d_off, old->d_adj, old->nnz, n0, d_flag));
-    uint32_t flag = 0;
-    if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
-      return fail(ISL_ERR_DEVICE, "importing the index's lists failed");
-    if (flag & 1u)
-      return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index has a list longer than m0 = %u", m0);
-    if (old->host_csr_valid && old->node_offsets.size() == n0 + 1 && old->node_offsets[n0] != old->nnz)
-      return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the device copy of the graph is not the lists verbatim (ids "
-                  "repeated inside a list were removed at upload)");
-    if (flag & 4u) return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: a list names an id that is not below len = %llu",
-                               (unsigned long long)n0);
-    if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index's offsets do not fit its lists");
+    ISL_TRY(check_import("isl_index_insert", d_flag, old));
   }
   auto note_level = [&](uint64_t id) {  // :610-613
     const uint64_t lv = levels.empty() ? 0 : levels[id];
@@ -1023,118 +1189,6 @@ void adopt_grown(isl_index* idx, isl_index* grown) {
   // buffers follow nq, k, ef, d and the wave count of a call, never the node count)
 }
 
-// The graph of `old` without the nodes `remap` marks kGone (include/islands_amd.h, isl_index_remove): repair over
-// the old ids on the builder's table, then compaction of lists and rows.  `old` (non-empty, resident rows, at
-// least one survivor) is only read; the shrunk graph leaves in `out`, built beside it, with the survivors' rows.
-isl_status shrink_flat(const isl_build_options& opts, const isl_index* old, const std::vector<uint32_t>& remap,
-                       const std::vector<uint32_t>& survivors, isl_index** out) {
-  using isl::fail;
-  const isl_leann_config cfg = old->cfg;
-  const uint64_t n0 = old->num_nodes, n = survivors.size();
-  const uint32_t m0 = (uint32_t)cfg.m0;
-  const isl::RowTable& rows = old->rows;
-  ISL_TRY(isl::use_device(old->device));
-  Scaffold c;  // the staging buffers alone: no construction graph
-  Table t{nullptr, nullptr, m0};
-  ISL_TRY(c.alloc(&t.ell, n0 * (m0 + 1), true));
-  ISL_TRY(c.alloc(&t.deg, n0, true));
-  uint32_t *d_flag = nullptr, *d_remap = nullptr, *d_surv = nullptr;
-  uint64_t* d_touched = nullptr;
-  unsigned long long* d_total = nullptr;
-  isl_build::RemoveLayer* d_layer = nullptr;  // the one layer of a flat index
-  ISL_TRY(c.alloc(&d_flag, 4, true));  // [0] import, [1] touched nodes, [2] those of layer 0, [3] compaction
-  ISL_TRY(c.alloc(&d_total, 1, true));
-  ISL_TRY(c.alloc(&d_remap, n0));
-  ISL_TRY(c.alloc(&d_surv, n));
-  ISL_TRY(c.alloc(&d_touched, n));
-  ISL_TRY(c.alloc(&d_layer, 1));
-  // every list returns to the table in its stored order: an untouched row is finished with that copy
-  ISL_TRY(c.csr_to_table(t, old->d_off, old->d_adj, old->nnz, n0, d_flag));
-  uint32_t flag = 0;
-  if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "importing the index's lists failed");
-  if (flag & 1u) return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the index has a list longer than m0 = %u", m0);
-  if (old->host_csr_valid && old->node_offsets.size() == n0 + 1 && old->node_offsets[n0] != old->nnz)
-    return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the device copy of the graph is not the lists verbatim (ids "
-                "repeated inside a list were removed at upload)");
-  if (flag & 4u) return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: a list names an id that is not below len = %llu",
-                             (unsigned long long)n0);
-  if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_index_remove: the index's offsets do not fit its lists");
-  // the CSR is in range from here on: the kernels below index by its ids
-  isl_build::RemoveLayer layer{old->d_off.get(), old->d_adj.get(), t.ell, t.deg, m0, 0u, nullptr, nullptr};
-  if (hipMemcpy(d_remap, remap.data(), n0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_surv, survivors.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_layer, &layer, sizeof(layer), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "cannot upload the remap");
-  ISL_TRY(isl_build::list_touched(d_layer, 1, nullptr, d_remap, n0, d_touched, (uint32_t)n, d_flag + 1));
-  uint32_t touched = 0;
-  if (hipMemcpy(&touched, d_flag + 1, 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "listing the touched nodes failed");
-  if (touched > n) return fail(ISL_ERR_DEVICE, "listing the touched nodes failed: %u of %llu survivors", touched,
-                               (unsigned long long)n);
-  const bool debug = getenv("ISL_DEBUG") != nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (debug && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
-  if (touched) {
-    isl_build::RepairParams p{};
-    p.emb = rows.data(); p.norm2 = rows.norm2(); p.stride = rows.stride(); p.d = (uint32_t)rows.d();
-    p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
-    p.layers = d_layer; p.levels = nullptr; p.remap = d_remap; p.touched = d_touched; p.total = d_total;
-    if (ev0) (void)hipEventRecord(ev0, 0);
-    const isl_status launched = isl_build::launch_repair(cfg.metric, opts.select_rule == ISL_SELECT_DIVERSE, rows, touched,
-                                                         isl_build::repair_lds(rows, m0), p);
-    if (ev1) (void)hipEventRecord(ev1, 0);
-    if (launched != ISL_OK) {
-      if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
-      return launched;
-    }
-  }
-  // compaction: degrees of the survivors -> offsets (host scan, as table_to_csr), lists through the remap
-  std::vector<uint32_t> hdeg(n0);
-  if (hipMemcpy(hdeg.data(), t.deg, n0 * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "repair kernel failed");
-  if (debug) {
-    unsigned long long total = 0;
-    float ms = 0.0f;
-    (void)hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost);
-    if (touched && ev0) (void)hipEventElapsedTime(&ms, ev0, ev1);
-    fprintf(stderr, "[isl] isl_index_remove: %llu of %llu nodes removed, touched %u, candidates %llu, repair kernel "
-            "%.3f ms\n", (unsigned long long)(n0 - n), (unsigned long long)n0, touched, total, ms);
-  }
-  if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
-  std::vector<uint64_t> hoff(n + 1, 0);
-  for (uint64_t i = 0; i < n; ++i) hoff[i + 1] = hoff[i] + std::min(hdeg[survivors[i]], m0);
-  uint64_t* d_off = nullptr;
-  uint32_t* d_adj = nullptr;
-  ISL_TRY(c.alloc(&d_off, n + 1));
-  ISL_TRY(c.alloc(&d_adj, hoff[n]));
-  layer.new_off = d_off;
-  layer.new_adj = d_adj;
-  if (hipMemcpy(d_off, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_layer, &layer, sizeof(layer), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "cannot upload the CSR offsets");
-  ISL_TRY(isl_build::compact_lists(d_layer, 1, nullptr, d_remap, n0, d_flag + 3));
-  if (hipMemcpy(&flag, d_flag + 3, 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "CSR compaction failed");
-  if (flag) return fail(ISL_ERR_DEVICE, "isl_index_remove: a repaired list kept a removed id");
-  // rows and norms of the survivors, bit for bit, into a table of the same type
-  isl::RowTable shrunk;
-  ISL_TRY(isl_build::gather_survivors(rows, d_surv, n, shrunk));
-  if (hipDeviceSynchronize() != hipSuccess) return fail(ISL_ERR_DEVICE, "row compaction failed");
-  const std::vector<uint64_t> old_levels = old->levels.size() == n0 ? old->levels : std::vector<uint64_t>();
-  const isl_plan::Entry e = isl_plan::entry_after(old_levels, remap, survivors, old->has_entry, old->entry_point,
-                                                  old->max_level);
-  ISL_TRY(isl_index_from_device_csr(&cfg, old->device, n, d_off, d_adj, e.has ? 1 : 0, e.id, old->has_dimension ? 1 : 0,
-                                    old->dimension, &c.res));
-  c.res->max_level = e.max_level;
-  c.res->levels = isl_plan::levels_after(old_levels, survivors);
-  c.res->rows = std::move(shrunk);
-  c.res->nvec = n;
-  *out = c.res;
-  c.res = nullptr;
-  return ISL_OK;
-}
-
 }  // namespace
 
 extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* opts_in, const uint64_t* ids,
@@ -1142,15 +1196,10 @@ extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* 
   using isl::fail;
   if (!idx || (!ids && n_ids)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
+  ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
   const uint64_t n0 = idx->num_nodes;
   if (n_ids == 0) {
-    if (out_remap)
-      for (uint64_t i = 0; i < n0; ++i) out_remap[i] = i;
+    isl_build::write_remap(nullptr, n0, out_remap);
     if (out_len) *out_len = n0;
     return ISL_OK;
   }
@@ -1176,8 +1225,33 @@ extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* 
   const uint64_t n = isl_plan::build_remap(n0, ids, n_ids, remap, survivors);
   isl_index* shrunk = nullptr;
   // every node gone: what isl_index_build_rows gives for n == 0 under the handle's config
-  if (n == 0) ISL_TRY(isl_index_new(&idx->cfg, &shrunk));
-  else ISL_TRY(shrink_flat(opts, idx, remap, survivors, &shrunk));
+  if (n == 0) {
+    ISL_TRY(isl_index_new(&idx->cfg, &shrunk));
+  } else {
+    // one layer that every node has: the levels only name the entry point.  `idx` is only read; the shrunk graph is
+    // built beside it, with the survivors' rows.
+    const uint32_t m0 = (uint32_t)idx->cfg.m0;
+    ISL_TRY(isl::use_device(idx->device));
+    Scaffold c;  // the staging buffers alone: no construction graph
+    isl_build::ShrinkTables t;
+    ISL_TRY(isl_build::shrink_import(c, {{idx->d_off.get(), idx->d_adj.get(), idx->nnz, m0}}, n0, t));
+    ISL_TRY(check_import("isl_index_remove", t.d_flag, idx));
+    isl_build::Shrunk r;
+    ISL_TRY(isl_build::shrink_finish(c, t, old_rows, idx->cfg.metric, opts, remap, survivors,
+                                     idx->levels.size() == n0 ? idx->levels : std::vector<uint64_t>(), idx->has_entry,
+                                     idx->entry_point, idx->max_level, false, "isl_index_remove", r));
+    if (getenv("ISL_DEBUG"))
+      fprintf(stderr, "[isl] isl_index_remove: %llu of %llu nodes removed, touched %u, candidates %llu, repair kernel "
+              "%.3f ms\n", (unsigned long long)(n0 - n), (unsigned long long)n0, r.counts[0], r.candidates, r.repair_ms);
+    ISL_TRY(isl_index_from_device_csr(&idx->cfg, idx->device, n, r.off[0], r.adj[0], r.entry.has ? 1 : 0, r.entry.id,
+                                      idx->has_dimension ? 1 : 0, idx->dimension, &c.res));
+    c.res->max_level = r.entry.max_level;
+    c.res->levels = std::move(r.levels);
+    c.res->rows = std::move(r.rows);
+    c.res->nvec = n;
+    shrunk = c.res;
+    c.res = nullptr;
+  }
   // the entry seeds that survive, under their new ids
   std::vector<uint64_t> seeds;
   for (uint64_t s : idx->seeds.ids)
@@ -1196,8 +1270,7 @@ extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* 
   // their rows are gathered again from the shrunk table; a table that cannot be made stays dropped, and a plain
   // search then starts at the entry point: the graph, the rows and the remap stand either way
   if (!seeds.empty() && isl_index_set_entry_seeds(idx, seeds.data(), seeds.size()) != ISL_OK) isl::last_error() = {};
-  if (out_remap)
-    for (uint64_t i = 0; i < n0; ++i) out_remap[i] = remap[i] == isl_plan::kGone ? ISL_REMOVED : (uint64_t)remap[i];
+  isl_build::write_remap(&remap, n0, out_remap);
   if (out_len) *out_len = n;
   return ISL_OK;
 }
@@ -1208,11 +1281,7 @@ extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const
   using isl::fail;
   if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
+  ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
   ISL_TRY(isl_build::check_row_dtype(dtype));
   isl_leann_config cfg;
   if (cfg_in) cfg = *cfg_in;
@@ -1243,11 +1312,7 @@ extern "C" isl_status isl_index_insert(isl_index* idx, const isl_build_options* 
   using isl::fail;
   if (!idx || (!rows && n_new)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
+  ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
   ISL_TRY(isl_build::check_row_dtype(dtype));
   const uint64_t n0 = idx->num_nodes;
   if (n_new == 0) {
@@ -1314,11 +1379,7 @@ extern "C" isl_status isl_select_neighbors(const isl_index* idx, const isl_build
   if (!idx || (nb && (!base_ids || !cand_cnt || !out_ids || !out_cnt || (!cand_ids && pitch))))
     return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, false));
-    opts = *opts_in;
-  }
+  ISL_TRY(isl_build::resolve_build_options(opts_in, false, opts));
   if (cap == 0 || cap > isl_plan::kMaxM0) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: 1 <= cap <= 128");
   if (nb == 0) return ISL_OK;
   if (nb > 0x7FFFFFFFull) return fail(ISL_ERR_UNSUPPORTED, "isl_select_neighbors: too many base nodes");

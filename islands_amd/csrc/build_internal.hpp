@@ -5,6 +5,7 @@
 
 #include "build_plan.hpp"
 #include "common.hpp"
+#include "remove_plan.hpp"
 
 namespace isl_build {
 
@@ -40,8 +41,15 @@ struct BuildParams {
   const uint16_t* emb16;
 };
 
-// struct_size, rule and alpha of caller-supplied options, before any device call
-isl_status check_build_options(const isl_build_options* o, bool need_rule);
+// The options of a call: the defaults, or the caller's once struct_size, rule and alpha are checked (before any
+// device call)
+isl_status resolve_build_options(const isl_build_options* in, bool need_rule, isl_build_options& out);
+// "the device copy of layer 0 is not the lists verbatim": the host lists are longer than what was uploaded, because
+// ids repeated inside a list were removed at upload.  A builder that reads the device CSR back into its table
+// would quietly build on another graph.
+bool device_lists_differ(const isl_index* idx);
+// old -> new ids of a removal for the caller, ISL_REMOVED for a removed one; `remap` NULL: nothing was removed
+void write_remap(const std::vector<uint32_t>* remap, uint64_t n0, uint64_t* out_remap);
 // bytes of LDS of the reference-rule link kernel and of the insertion descent (tile + query)
 size_t link_lds(uint64_t d);
 // ISL_DTYPE_F32 / ISL_DTYPE_BF16, before any device call
@@ -109,10 +117,11 @@ struct Scaffold {
   isl_index* release();
 };
 
-// ---- what the two removals share (isl_index_remove in build.hip, isl_hnsw_remove in hnsw_build.hip; the kernels
-// are build.hip's).  A graph that shrinks is a set of layers -- one for a flat index -- each with its OLD CSR, the
-// table its lists return to and, once the repaired degrees are known, the CSR of the survivors.  The kernels read
-// an array of these in device memory and take the layer from blockIdx.y or from the touched pair.
+// ---- what the two removals share: the kernels and the one routine that drives them are build.hip's;
+// isl_index_remove (build.hip) and isl_hnsw_remove (hnsw_build.hip) call it and make their own handle from what it
+// returns.  A graph that shrinks is a set of layers -- one for a flat index -- each with its OLD CSR, the table its
+// lists return to and, once the repaired degrees are known, the CSR of the survivors.  The kernels read an array of
+// these in device memory and take the layer from blockIdx.y or from the touched pair.
 struct RemoveLayer {
   const uint64_t* off;      // the OLD CSR over the old ids: every list is computed from the old lists only
   const uint32_t* adj;
@@ -120,7 +129,7 @@ struct RemoveLayer {
   uint32_t* deg;            // [n0]
   uint32_t M;               // ids a row of this layer keeps
   uint32_t reserved;
-  const uint64_t* new_off;  // [n + 1] the survivors' CSR over the new ids (compact_lists)
+  const uint64_t* new_off;  // [n + 1] the survivors' CSR over the new ids (table_to_csr_remap_kernel)
   uint32_t* new_adj;
 };
 
@@ -138,22 +147,53 @@ struct RepairParams {
   unsigned long long* total;  // [1] sum of |C(p)| over the touched pairs
 };
 
-// LDS of a repair launch whose widest layer keeps `widest` ids, for the rows' stored type
-size_t repair_lds(const isl::RowTable& rows, uint32_t widest);
-// The launches below return once the kernel is enqueued on the default stream.
-// (layer, node) pairs of the survivors that lost a neighbour, all layers in one launch: d_counts [1 + layers],
-// zeroed by the caller, receives the number of pairs and the pairs per layer; at most `cap` pairs are written.
-isl_status list_touched(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
-                        uint64_t n0, uint64_t* d_pairs, uint32_t cap, uint32_t* d_counts);
-// one wave per pair rebuilds the pair's table row
-isl_status launch_repair(uint32_t metric, bool diverse, const isl::RowTable& rows, uint32_t grid, size_t lds,
-                         const RepairParams& p);
-// the tables of layers 0 .. layers-1 -> their new CSRs through the remap, one launch; *d_flag (zeroed by the caller)
-// is raised by a removed id left in a survivor's row
-isl_status compact_lists(const RemoveLayer* d_layers, uint32_t layers, const uint32_t* d_levels, const uint32_t* d_remap,
-                         uint64_t n0, uint32_t* d_flag);
-// rows and norms of the n survivors d_surv[] (old ids, ascending), bit for bit, into `out`, a fresh table of the
-// same stored type (row_table.hpp has the layout)
-isl_status gather_survivors(const isl::RowTable& rows, const uint32_t* d_surv, uint64_t n, isl::RowTable& out);
+// One layer as its caller hands it in: the old CSR on the device and the ids a list of the layer keeps.
+struct ShrinkLayer {
+  const uint64_t* off;
+  const uint32_t* adj;
+  uint64_t nnz;
+  uint32_t M;
+};
+
+// What shrink_import leaves for shrink_finish, all of it owned by the caller's Scaffold.
+struct ShrinkTables {
+  std::vector<RemoveLayer> ly;  // per layer: old CSR and table
+  uint32_t* d_deg = nullptr;    // [layers][n0] the tables' degrees: one block, read back in one copy
+  uint32_t* d_flag = nullptr;   // [0] what the import could not take (Scaffold::csr_to_table's bits), [1] compaction,
+                                // [2 ..] the touched pairs: all, then per layer
+};
+
+// What shrink_finish returns.
+struct Shrunk {
+  std::vector<const uint64_t*> off;  // per kept layer, the survivors' CSR over the new ids: layer 0 from the
+  std::vector<const uint32_t*> adj;  // Scaffold's tmp; the layers above from keep, one block of offsets over ALL new
+                                     // ids (a node below a layer has an empty row there) and one of ids
+  isl::RowTable rows;                // the survivors' rows and norms, bit for bit, in the stored type
+  isl_plan::Entry entry;             // remove_plan.hpp's entry rule
+  std::vector<uint64_t> levels;      // of the survivors
+  // for the caller's ISL_DEBUG line
+  std::vector<uint32_t> counts;      // [1 + layers] touched (layer, node) pairs: all, then per layer
+  unsigned long long candidates = 0; // sum of |C(p)| over them
+  float repair_ms = 0.0f;            // the repair kernel, timed under ISL_DEBUG alone
+};
+
+// The removal in two halves, so that each caller words its own refusals in between.
+// shrink_import: every layer's list returns to a table of n0 rows in its stored order (an untouched row is finished
+// with that copy), all launches enqueued; the caller reads t.d_flag[0] once and refuses what it must.
+isl_status shrink_import(Scaffold& c, const std::vector<ShrinkLayer>& layers, uint64_t n0, ShrinkTables& t);
+// shrink_finish, once the CSRs are known to be in range: one kernel lists the (layer, node) pairs that lost a
+// neighbour, one repair launch rebuilds those rows from the layer's OLD CSR under M_L, one launch compacts the kept
+// layers through the remap and one gathers the survivors' rows.  Two read-backs in between: the pair counts and the
+// repaired degrees.  `old_rows`: resident f32 or bf16 rows of all n0 nodes; `remap` / `survivors`:
+// isl_plan::build_remap's, at least one survivor.  The levels play two roles.  `levels` (of all old nodes, or empty
+// = all 0) and has_entry / entry / max_level always feed the entry rule.  With `levels_name_layers` they also say
+// which node has which layer (a node has layer L iff levels[node] >= L): the kernels then read them from a device
+// copy, and the layers above the new max_level cease to exist.  Without it the kernels get no level array: every
+// node has every layer and every layer is kept -- a flat index, whose levels only name the entry point.
+// `call` names the entry point in messages.
+isl_status shrink_finish(Scaffold& c, ShrinkTables& t, const isl::RowTable& old_rows, uint32_t metric,
+                         const isl_build_options& opts, const std::vector<uint32_t>& remap,
+                         const std::vector<uint32_t>& survivors, const std::vector<uint64_t>& levels, bool has_entry,
+                         uint64_t entry, uint64_t max_level, bool levels_name_layers, const char* call, Shrunk& out);
 
 }  // namespace isl_build

@@ -20,9 +20,10 @@
 // A graph that grows returns to this layout first: its CSR layers are written back into tables of len + n_new
 // rows (Scaffold::csr_to_table), its rows are copied beside the new ones, and the plan starts at node len.  The
 // grown graph is built beside the old one and swapped into the handle at the end.
-// A graph that shrinks (isl_hnsw_remove, shrink()) returns to tables over its OLD nodes in the same way; the flat
-// removal's kernels (build.hip, through isl_build) then repair and compact every layer in one pass, and the shrunk
-// graph is swapped in as a grown one is.  Its host-only arithmetic is hnsw_remove_plan.hpp's.
+// A graph that shrinks (isl_hnsw_remove, shrink()) hands its layers to the removal routine of build.hip
+// (isl_build::shrink_import / shrink_finish, the one isl_index_remove calls with its single layer), which repairs
+// and compacts every layer in one pass; the shrunk graph is swapped in as a grown one is (install_core).  The
+// host-only arithmetic is hnsw_remove_plan.hpp's.
 #include "device_common.hip.h"
 #include "build_internal.hpp"
 #include "hnsw_remove_plan.hpp"
@@ -176,6 +177,24 @@ isl_status all_levels(const isl_index* old, const isl_hnsw_config& cfg, uint64_t
   return ISL_OK;
 }
 
+// What `call` (isl_hnsw_insert, isl_hnsw_remove) refuses once the layers of `from` have returned to their tables:
+// *d_flag holds Scaffold::csr_to_table's bits over all layers, read here once.  Past this the CSRs are in range.
+// (isl_hnsw_insert has refused a layer 0 that is not verbatim before it came here.)
+isl_status check_import(const char* call, const uint32_t* d_flag, const isl_hnsw* from) {
+  using isl::fail;
+  uint32_t flag = 0;
+  if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return fail(ISL_ERR_DEVICE, "importing the graph's layers failed");
+  if (flag & 1u)
+    return fail(ISL_ERR_UNSUPPORTED, "%s: the graph has a list longer than its layer keeps (m0 = %u on layer 0, m = %u "
+                "above)", call, (uint32_t)from->m0, (uint32_t)from->m);
+  if (isl_build::device_lists_differ(from->core))
+    return fail(ISL_ERR_UNSUPPORTED, "%s: the device copy of layer 0 is not the lists verbatim (ids repeated inside a "
+                "list were removed at upload)", call);
+  if (flag) return fail(ISL_ERR_UNSUPPORTED, "%s: the graph's layers name ids or offsets outside it", call);
+  return ISL_OK;
+}
+
 // HnswGraph::insert for nodes n0 .. n-1 of a graph that holds n0 (`from`: a finished graph with at least one
 // node, whose CSR layers return to the builder's tables; NULL: nothing, node 0 starts the graph).  One loop
 // over the plan's steps -- descent, per-layer gather, Scaffold::insert -- then compaction and
@@ -227,13 +246,7 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
         return fail(ISL_ERR_DEVICE, "cannot read the offsets of layer %llu", (unsigned long long)L);
       ISL_TRY(c.csr_to_table(tab[L], from->layer_off[L], from->layer_adj[L], nnz, n0, d_flag));
     }
-    uint32_t flag = 0;
-    if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
-      return fail(ISL_ERR_DEVICE, "importing the graph's layers failed");
-    if (flag & 1u)
-      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the graph has a list longer than its layer keeps (m0 = %u on "
-                  "layer 0, m = %u above)", m0, m);
-    if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the graph's layers name ids or offsets outside it");
+    ISL_TRY(check_import("isl_hnsw_insert", d_flag, from));
   }
   uint32_t **d_tab = nullptr, **d_deg = nullptr;
   uint32_t *d_lv = nullptr, *d_order = nullptr, *cur_of = nullptr, *evals_of = nullptr;
@@ -327,178 +340,92 @@ isl_status check_entry_and_levels(const char* call, const isl_index* core) {
 }
 
 // The graph of `from` without the nodes `remap` marks kGone (include/islands_amd.h, isl_hnsw_remove), every layer
-// in one pass: the layers' CSRs return to per-layer tables, one kernel lists the (layer, node) pairs that lost a
-// neighbour, one repair launch rebuilds those rows from the layer's OLD CSR under M_L, one launch compacts the
-// layers that are left through the remap and one gathers the survivors' rows.  Two read-backs in between: the
-// pair counts and the repaired degrees.  `from` (non-empty, resident f32 rows, levels that match its layers, at
-// least one survivor) is only read; the shrunk graph leaves in `out`, built beside it.
+// in one pass of the removal routine (isl_build::shrink_import / shrink_finish): layer 0 is the core index's CSR,
+// the layers above are the descent's arrays, and the levels say which node has which layer.  `from` (non-empty,
+// resident f32 rows, levels that match its layers, at least one survivor) is only read; the shrunk graph leaves in
+// `out`, built beside it.
 isl_status shrink(const isl_build_options& opts, const isl_hnsw* from, const std::vector<uint32_t>& remap,
                   const std::vector<uint32_t>& survivors, std::unique_ptr<isl_hnsw>& out) {
   using isl::fail;
-  using isl_build::RemoveLayer;
   const isl_index* old = from->core;
   const uint64_t n0 = old->num_nodes, n = survivors.size(), layers = old->max_level + 1;
   const uint32_t m = (uint32_t)from->m, m0 = (uint32_t)from->m0;
-  const isl::RowTable& rows = old->rows;
   if (from->layer_off.size() < layers || from->layer_adj.size() < layers)
     return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove: the graph holds %llu layers and max_level is %llu",
                 (unsigned long long)from->layer_off.size(), (unsigned long long)old->max_level);
   ISL_TRY(isl::use_device(old->device));
-  const isl_plan::Entry e = isl_plan::entry_after(old->levels, remap, survivors, old->has_entry, old->entry_point,
-                                                  old->max_level);
-  const uint64_t kept_layers = isl_plan::layers_after(e);  // <= layers: the layers above cease to exist
-  const std::vector<uint64_t> members = isl_plan::layer_members(old->levels, survivors, layers);
-  const uint64_t pair_cap = isl_plan::touched_capacity(members);
-  if (pair_cap > 0xFFFFFFFFull) return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove: more than 2^32 lists");
-
-  isl_build::Scaffold c;  // the staging buffers alone: no construction graph
-  std::vector<RemoveLayer> ly(layers);
-  std::vector<isl_build::Table> tab(layers);
-  uint32_t* d_deg = nullptr;  // [layers][n0]: one block, read back in one copy
-  ISL_TRY(c.alloc(&d_deg, layers * n0, true));
-  for (uint64_t L = 0; L < layers; ++L) {
-    tab[L].M = isl_plan::layer_cap((uint32_t)L, m, m0);
-    tab[L].deg = d_deg + L * n0;
-    ISL_TRY(c.alloc(&tab[L].ell, n0 * (tab[L].M + 1)));
-    ly[L] = RemoveLayer{L ? from->layer_off[L] : old->d_off.get(), L ? from->layer_adj[L] : old->d_adj.get(), tab[L].ell,
-                        tab[L].deg, tab[L].M, 0u, nullptr, nullptr};
+  std::vector<isl_build::ShrinkLayer> ly(layers);
+  ly[0] = {old->d_off.get(), old->d_adj.get(), old->nnz, m0};
+  for (uint64_t L = 1; L < layers; ++L) {
+    ly[L] = {from->layer_off[L], from->layer_adj[L], 0, isl_plan::layer_cap((uint32_t)L, m, m0)};
     if (!ly[L].off || !ly[L].adj) return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove: layer %llu is not on the device",
                                                (unsigned long long)L);
-  }
-  uint32_t *d_flag = nullptr, *d_counts = nullptr, *d_remap = nullptr, *d_surv = nullptr, *d_lv = nullptr;
-  uint64_t* d_pairs = nullptr;
-  unsigned long long* d_total = nullptr;
-  RemoveLayer* d_ly = nullptr;
-  ISL_TRY(c.alloc(&d_flag, 2, true));  // [0] import, [1] compaction
-  ISL_TRY(c.alloc(&d_counts, layers + 1, true));
-  ISL_TRY(c.alloc(&d_total, 1, true));
-  ISL_TRY(c.alloc(&d_remap, n0));
-  ISL_TRY(c.alloc(&d_surv, n));
-  ISL_TRY(c.alloc(&d_lv, n0));
-  ISL_TRY(c.alloc(&d_pairs, pair_cap));
-  ISL_TRY(c.alloc(&d_ly, layers));
-  // every list returns to its layer's table in its stored order: an untouched row is finished with that copy
-  ISL_TRY(c.csr_to_table(tab[0], old->d_off, old->d_adj, old->nnz, n0, d_flag));
-  for (uint64_t L = 1; L < layers; ++L) {
-    uint64_t nnz = 0;
-    if (hipMemcpy(&nnz, from->layer_off[L] + n0, 8, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&ly[L].nnz, ly[L].off + n0, 8, hipMemcpyDeviceToHost) != hipSuccess)
       return fail(ISL_ERR_DEVICE, "cannot read the offsets of layer %llu", (unsigned long long)L);
-    ISL_TRY(c.csr_to_table(tab[L], from->layer_off[L], from->layer_adj[L], nnz, n0, d_flag));
   }
-  uint32_t flag = 0;
-  if (hipMemcpy(&flag, d_flag, 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "importing the graph's layers failed");
-  if (flag & 1u)
-    return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove: the graph has a list longer than its layer keeps (m0 = %u on "
-                "layer 0, m = %u above)", m0, m);
-  if (old->host_csr_valid && old->node_offsets.size() == n0 + 1 && old->node_offsets[n0] != old->nnz)
-    return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove: the device copy of layer 0 is not the lists verbatim (ids repeated "
-                "inside a list were removed at upload)");
-  if (flag) return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove: the graph's layers name ids or offsets outside it");
-  // the CSRs are in range from here on: the kernels below index by their ids
-  const std::vector<uint32_t> lv(old->levels.begin(), old->levels.end());
-  if (hipMemcpy(d_remap, remap.data(), n0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_surv, survivors.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_lv, lv.data(), n0 * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d_ly, ly.data(), layers * sizeof(RemoveLayer), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "cannot upload the remap");
-  ISL_TRY(isl_build::list_touched(d_ly, (uint32_t)layers, d_lv, d_remap, n0, d_pairs, (uint32_t)pair_cap, d_counts));
-  std::vector<uint32_t> counts(layers + 1, 0);
-  if (hipMemcpy(counts.data(), d_counts, (layers + 1) * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "listing the touched lists failed");
-  const uint32_t touched = counts[0];
-  if (touched > pair_cap)
-    return fail(ISL_ERR_DEVICE, "listing the touched lists failed: %u of %llu lists", touched, (unsigned long long)pair_cap);
-  const bool debug = getenv("ISL_DEBUG") != nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (debug && touched && (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess)) ev0 = ev1 = nullptr;
-  isl_status launched = ISL_OK;
-  if (touched) {
-    isl_build::RepairParams p{};
-    p.emb = rows.data(); p.norm2 = rows.norm2(); p.stride = rows.stride(); p.d = (uint32_t)rows.d();
-    p.alpha = opts.alpha; p.keep_pruned = opts.keep_pruned ? 1u : 0u;
-    p.layers = d_ly; p.levels = d_lv; p.remap = d_remap; p.touched = d_pairs; p.total = d_total;
-    if (ev0) (void)hipEventRecord(ev0, 0);
-    launched = isl_build::launch_repair(old->cfg.metric, opts.select_rule == ISL_SELECT_DIVERSE, rows, touched,
-                                        isl_plan::hnsw_repair_lds((size_t)TILE_ROWS * TILE_LD * 4, p.d, m, m0), p);
-    if (ev1) (void)hipEventRecord(ev1, 0);
-  }
-  // the repaired degrees of every layer -> the offsets of the layers that are left (host scan, as table_to_csr)
-  std::vector<uint32_t> hdeg(layers * n0);
-  const bool read = launched == ISL_OK && hipMemcpy(hdeg.data(), d_deg, layers * n0 * 4, hipMemcpyDeviceToHost) == hipSuccess;
-  if (debug && read) {
-    unsigned long long total = 0;
-    float ms = 0.0f;
-    (void)hipMemcpy(&total, d_total, 8, hipMemcpyDeviceToHost);
-    if (ev0) (void)hipEventElapsedTime(&ms, ev0, ev1);
+  isl_build::Scaffold c;  // the staging buffers alone: no construction graph
+  isl_build::ShrinkTables t;
+  ISL_TRY(isl_build::shrink_import(c, ly, n0, t));
+  ISL_TRY(check_import("isl_hnsw_remove", t.d_flag, from));
+  isl_build::Shrunk r;
+  ISL_TRY(isl_build::shrink_finish(c, t, old->rows, old->cfg.metric, opts, remap, survivors, old->levels, old->has_entry,
+                                   old->entry_point, old->max_level, true, "isl_hnsw_remove", r));
+  if (getenv("ISL_DEBUG")) {
     std::string per;
-    for (uint64_t L = 0; L < layers; ++L) per += (L ? " " : "") + std::to_string(counts[1 + L]);
+    for (uint64_t L = 0; L < layers; ++L) per += (L ? " " : "") + std::to_string(r.counts[1 + L]);
     fprintf(stderr, "[isl] isl_hnsw_remove: %llu of %llu nodes removed, layers %llu -> %llu, touched %u (per layer: %s), "
             "candidates %llu, repair kernel %.3f ms\n", (unsigned long long)(n0 - n), (unsigned long long)n0,
-            (unsigned long long)layers, (unsigned long long)kept_layers, touched, per.c_str(), total, ms);
+            (unsigned long long)layers, (unsigned long long)r.off.size(), r.counts[0], per.c_str(), r.candidates,
+            r.repair_ms);
   }
-  if (ev0) { (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1); }
-  ISL_TRY(launched);
-  if (!read) return fail(ISL_ERR_DEVICE, "repair kernel failed");
-  // layer 0: its own arrays (the core index copies them); the layers above: one block of offsets over ALL new
-  // ids (a node below a layer has an empty row there, isl_hnsw_from_layers' shape) and one of ids, kept
-  std::vector<uint64_t> hoff(kept_layers * (n + 1), 0);
-  for (uint64_t L = 0; L < kept_layers; ++L) {
-    uint64_t* o = hoff.data() + L * (n + 1);
-    for (uint64_t i = 0; i < n; ++i) {
-      const uint32_t s = survivors[i];
-      o[i + 1] = o[i] + (lv[s] >= L ? std::min(hdeg[L * n0 + s], tab[L].M) : 0u);
-    }
-  }
-  uint64_t upper_nnz = 0;
-  for (uint64_t L = 1; L < kept_layers; ++L) upper_nnz += hoff[L * (n + 1) + n];
-  uint64_t *d_off0 = nullptr, *d_off_up = nullptr;
-  uint32_t *d_adj0 = nullptr, *d_adj_up = nullptr;
-  ISL_TRY(c.alloc(&d_off0, n + 1));
-  ISL_TRY(c.alloc(&d_adj0, hoff[n]));
-  if (kept_layers > 1) {
-    ISL_TRY(c.alloc(&d_off_up, (kept_layers - 1) * (n + 1), false, true));
-    ISL_TRY(c.alloc(&d_adj_up, upper_nnz, false, true));
-  }
-  std::vector<const uint64_t*> offs(kept_layers, nullptr);
-  std::vector<const uint32_t*> adjs(kept_layers, nullptr);
-  ly[0].new_off = d_off0;
-  ly[0].new_adj = d_adj0;
-  for (uint64_t L = 1, at = 0; L < kept_layers; ++L) {
-    offs[L] = ly[L].new_off = d_off_up + (L - 1) * (n + 1);
-    adjs[L] = ly[L].new_adj = d_adj_up + at;
-    at += hoff[L * (n + 1) + n];
-  }
-  if (hipMemcpy(d_off0, hoff.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      (kept_layers > 1 && hipMemcpy(d_off_up, hoff.data() + (n + 1), (kept_layers - 1) * (n + 1) * 8,
-                                    hipMemcpyHostToDevice) != hipSuccess) ||
-      hipMemcpy(d_ly, ly.data(), layers * sizeof(RemoveLayer), hipMemcpyHostToDevice) != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "cannot upload the CSR offsets");
-  ISL_TRY(isl_build::compact_lists(d_ly, (uint32_t)kept_layers, d_lv, d_remap, n0, d_flag + 1));
-  // rows and norms of the survivors, bit for bit
-  isl::RowTable shrunk;
-  ISL_TRY(isl_build::gather_survivors(rows, d_surv, n, shrunk));
-  if (hipMemcpy(&flag, d_flag + 1, 4, hipMemcpyDeviceToHost) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-    return fail(ISL_ERR_DEVICE, "compaction failed");
-  if (flag) return fail(ISL_ERR_DEVICE, "isl_hnsw_remove: a repaired list kept a removed id");
-  // layer 0 becomes the new core as grow() makes it; the layers above are attached as the builder's are
+  // layer 0 becomes the new core as grow() makes it (its own copy); the layers above are attached as the builder's
+  // are: the pointer tables carry nothing for layer 0
   const isl_leann_config lcfg = old->cfg;
-  ISL_TRY(isl_index_from_device_csr(&lcfg, old->device, n, d_off0, d_adj0, e.has ? 1 : 0, e.id, 1, rows.d(), &c.res));
+  ISL_TRY(isl_index_from_device_csr(&lcfg, old->device, n, r.off[0], r.adj[0], r.entry.has ? 1 : 0, r.entry.id, 1,
+                                    old->rows.d(), &c.res));
+  r.off[0] = nullptr;
+  r.adj[0] = nullptr;
   c.res->is_hnsw = true;
-  c.res->max_level = e.max_level;
-  c.res->levels = isl_plan::levels_after(old->levels, survivors);
-  c.res->rows = std::move(shrunk);
+  c.res->max_level = r.entry.max_level;
+  c.res->levels = std::move(r.levels);
+  c.res->rows = std::move(r.rows);
   c.res->nvec = n;
   std::unique_ptr<isl_hnsw> h(new isl_hnsw());
   h->core = c.res;
   h->m = from->m; h->m0 = from->m0; h->ef_construction = from->ef_construction; h->dim = from->dim;
   h->ml = from->ml; h->max_layers = from->max_layers;
   h->device = old->device;
-  ISL_TRY(isl::attach_upper_layers(h.get(), offs, adjs));
+  ISL_TRY(isl::attach_upper_layers(h.get(), r.off, r.adj));
   for (auto& b : c.keep) c.res->hnsw_owned.push_back(std::move(b));
   c.keep.clear();
   c.res = nullptr;
   out = std::move(h);
+  return ISL_OK;
+}
+
+// What isl_hnsw_insert and isl_hnsw_remove do to the handle once the new graph stands beside the old one, which
+// nothing has touched so far: the core and the layer tables are swapped, the host mirrors reset and the old core
+// freed.  `verb` words the refusal beside a search ("grow", "shrink"), which frees the new core instead.  Either way
+// `fresh` is left for its owner to delete, without a core of its own.
+isl_status install_core(isl_hnsw* h, isl_hnsw* fresh, uint64_t dim, int32_t device, const char* verb) {
+  std::lock_guard<std::mutex> host_lock(h->host_mu);
+  isl_index* old = h->core;
+  {
+    std::lock_guard<std::mutex> lock(old->mu);
+    if (isl::any_lane_busy(old)) {
+      isl_index_free(fresh->core);
+      return isl::fail(ISL_ERR_SEARCH, "Search error: the graph cannot %s while searches are in flight", verb);
+    }
+  }
+  h->core = fresh->core;
+  h->layer_off.swap(fresh->layer_off);
+  h->layer_adj.swap(fresh->layer_adj);
+  h->dim = dim;
+  h->device = device;
+  h->host_valid = false;
+  h->h_off.clear();
+  h->h_adj.clear();
+  isl_index_free(old);  // with its lanes and padded adjacency; the new core sets its own up at the first search
   return ISL_OK;
 }
 
@@ -516,11 +443,7 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options
   using isl::fail;
   if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
+  ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
   isl_hnsw_config cfg;
   if (cfg_in) cfg = *cfg_in;
   else isl_hnsw_config_default(&cfg);
@@ -548,11 +471,7 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const 
   using isl::fail;
   if (!h || !h->core || (!vectors && n_new)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
+  ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
   const isl_index* core = h->core;
   const uint64_t n0 = core->num_nodes;
   if (n_new == 0) {
@@ -575,7 +494,7 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const 
     if (core->max_degree > h->m0)
       return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: a layer-0 list of %u ids is longer than m0 = %llu",
                   core->max_degree, (unsigned long long)h->m0);
-    if (core->host_csr_valid && core->node_offsets.size() == n0 + 1 && core->node_offsets[n0] != core->nnz)
+    if (isl_build::device_lists_differ(core))
       return fail(ISL_ERR_UNSUPPORTED,
                   "isl_hnsw_insert: the device copy of layer 0 is not the lists verbatim (ids repeated inside a list "
                   "were removed at upload)");
@@ -588,25 +507,7 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const 
   std::unique_ptr<isl_hnsw> grown;
   ISL_TRY(grow(cfg, opts, n0 ? h : nullptr, vectors, n_new, d, levels, top, mem, n0 ? core->device : h->device,
                grown));
-  // the swap: the grown graph was built beside the old one, which nothing has touched so far
-  std::lock_guard<std::mutex> host_lock(h->host_mu);
-  isl_index* old = h->core;
-  {
-    std::lock_guard<std::mutex> lock(old->mu);
-    if (isl::any_lane_busy(old)) {
-      isl_index_free(grown->core);
-      return fail(ISL_ERR_SEARCH, "Search error: the graph cannot grow while searches are in flight");
-    }
-  }
-  h->core = grown->core;
-  h->layer_off.swap(grown->layer_off);
-  h->layer_adj.swap(grown->layer_adj);
-  h->dim = d;
-  h->device = h->core->device;
-  h->host_valid = false;
-  h->h_off.clear();
-  h->h_adj.clear();
-  isl_index_free(old);  // with its lanes and padded adjacency; the new core sets its own up at the first search
+  ISL_TRY(install_core(h, grown.get(), d, grown->core->device, "grow"));
   if (first_id) *first_id = n0;
   return ISL_OK;
 }
@@ -616,16 +517,11 @@ isl_status isl_hnsw_remove(isl_hnsw* h, const isl_build_options* opts_in, const 
   using isl::fail;
   if (!h || !h->core || (!ids && n_ids)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
-  isl_build_options_default(&opts);
-  if (opts_in) {
-    ISL_TRY(isl_build::check_build_options(opts_in, true));
-    opts = *opts_in;
-  }
+  ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
   const isl_index* core = h->core;
   const uint64_t n0 = core->num_nodes;
   if (n_ids == 0) {
-    if (out_remap)
-      for (uint64_t i = 0; i < n0; ++i) out_remap[i] = i;
+    isl_build::write_remap(nullptr, n0, out_remap);
     if (out_len) *out_len = n0;
     return ISL_OK;
   }
@@ -655,27 +551,8 @@ isl_status isl_hnsw_remove(isl_hnsw* h, const isl_build_options* opts_in, const 
   } else {
     ISL_TRY(shrink(opts, h, remap, survivors, shrunk));
   }
-  // the swap: the shrunk graph was built beside the old one, which nothing has touched so far
-  std::lock_guard<std::mutex> host_lock(h->host_mu);
-  isl_index* old = h->core;
-  {
-    std::lock_guard<std::mutex> lock(old->mu);
-    if (isl::any_lane_busy(old)) {
-      isl_index_free(shrunk->core);
-      return fail(ISL_ERR_SEARCH, "Search error: the graph cannot shrink while searches are in flight");
-    }
-  }
-  h->core = shrunk->core;
-  h->layer_off.swap(shrunk->layer_off);
-  h->layer_adj.swap(shrunk->layer_adj);
-  h->dim = n ? h->dim : 0;
-  h->device = n ? h->core->device : h->device;
-  h->host_valid = false;
-  h->h_off.clear();
-  h->h_adj.clear();
-  isl_index_free(old);  // with its lanes and padded adjacency; the new core sets its own up at the first search
-  if (out_remap)
-    for (uint64_t i = 0; i < n0; ++i) out_remap[i] = remap[i] == isl_plan::kGone ? ISL_REMOVED : (uint64_t)remap[i];
+  ISL_TRY(install_core(h, shrunk.get(), n ? h->dim : 0, n ? shrunk->core->device : h->device, "shrink"));
+  isl_build::write_remap(&remap, n0, out_remap);
   if (out_len) *out_len = n;
   return ISL_OK;
 }

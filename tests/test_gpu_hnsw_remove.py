@@ -14,6 +14,7 @@ import _hnsw_remove_ref as href
 from _data import random_levels, uniform_vectors
 from test_gpu_hnsw import METRICS, bits
 from test_gpu_hnsw_insert import small_image
+from test_gpu_index_remove import index_from_lists
 from test_hnsw_bytes import hnsw_to_bincode
 
 pytestmark = pytest.mark.gpu
@@ -193,6 +194,23 @@ def test_d768(orc):
     stats = []
     remove_and_check(orc, g, layers, lv, v, pick_ids(layers, 400, 200), ia.DistanceMetric.Cosine, stats=stats, **cfg)
     assert max(c for L, _, c in stats if L == 0) > 16
+
+
+@pytest.mark.parametrize("count", [1, 20, 120])
+@pytest.mark.parametrize("rule", ["reference", "diverse"])
+def test_a_single_layer_graph_shrinks_as_the_flat_index_does(orc, rule, count):
+    """every level 0 from the start: max_level 0 and a device level array of zeros.  The graph is the definition's,
+    and a LeannIndex over the same layer-0 lists and m0 loses the same ids into the same remap and lists."""
+    v, lv = uniform_vectors(200, 24, 21), np.zeros(200, np.uint64)
+    g, layers = fresh("single", v, lv)
+    assert g.max_level == 0 and len(layers) == 1
+    flat = index_from_lists(layers[0], v, ia.LeannConfig(metric=ia.DistanceMetric.Euclidean, **BASE), entry=g.entry_point)
+    ids = pick_ids(layers, 200, count)
+    want, _ = remove_and_check(orc, g, layers, lv, v, ids, rule=rule)  # (the handle's remap is want.remap)
+    assert flat.remove(ids, select=rule).tolist() == want.remap.tolist()
+    assert len(flat) == len(g) == 200 - count
+    for i in range(len(g)):
+        assert flat.get_neighbors(i).tolist() == g.neighbors(i, 0), i
 
 
 def test_repeated_ids_and_their_order(orc):
