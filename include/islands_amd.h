@@ -315,8 +315,10 @@ isl_status isl_index_upload(isl_index* idx, int32_t device);
  * dtype ISL_DTYPE_BF16: `rows` holds bf16 bit patterns (u16) and is stored as such -- half the
  * HBM bytes per visited node; the provider's vectors are their exact f32 images and the
  * arithmetic stays the reference's f32 chain, so results equal the reference's on those f32
- * rows.  (The LeannIndex builder takes either type through isl_index_build_rows; the HnswGraph facade and its
- * builder, isl_select_neighbors and the distance / PQ entry points take f32.) */
+ * rows.  (The LeannIndex builder takes either type through isl_index_build_rows, the HnswGraph facade and its
+ * builder through isl_hnsw_build_rows / isl_hnsw_insert_rows / isl_hnsw_from_layers_rows -- on the core index of a
+ * facade this call itself keeps refusing anything but f32; isl_select_neighbors and the distance / PQ entry points
+ * take f32.) */
 isl_status isl_set_embeddings(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
                               int32_t dtype, int32_t mem);
 
@@ -766,6 +768,18 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
                                 const uint64_t* const* layer_neighbors, const uint64_t* levels,
                                 int32_t has_entry, uint64_t entry_point, uint64_t max_level,
                                 const float* vectors, int32_t device, isl_hnsw** out);
+/* isl_hnsw_from_layers over rows of either stored type: a finished graph handed over with its rows.  dtype
+ * ISL_DTYPE_F32: rows = num_nodes x d float, the call IS isl_hnsw_from_layers.  dtype ISL_DTYPE_BF16: rows =
+ * num_nodes x d bf16 bit patterns (u16) in host memory; the graph's vectors are their exact float32 images and the
+ * rows stay bf16 on the device (one table of 2-byte elements, isl_hnsw_row_storage).  Checked first, in this order:
+ * NULL out -> ISL_ERR_INVALID_ARGUMENT; an unknown dtype -> ISL_ERR_INVALID_ARGUMENT, ISL_DTYPE_FP8_E4M3 ->
+ * ISL_ERR_UNSUPPORTED; then everything isl_hnsw_from_layers checks. */
+isl_status isl_hnsw_from_layers_rows(uint64_t m, uint64_t m0, uint64_t ef_construction, int32_t metric,
+                                     uint64_t num_nodes, uint64_t d, uint64_t num_layers,
+                                     const uint64_t* const* layer_offsets,
+                                     const uint64_t* const* layer_neighbors, const uint64_t* levels,
+                                     int32_t has_entry, uint64_t entry_point, uint64_t max_level,
+                                     const void* rows, int32_t dtype, int32_t device, isl_hnsw** out);
 /* HnswGraph::from_bytes, hnsw.rs:511-514: reads the bincode image of a HnswGraph (1.x default
  * layout; HashMap entries in any order, node ids 0..n-1) and makes it resident on `device`.
  * Truncated or inconsistent input -> ISL_ERR_DESERIALIZATION.  (isl_hnsw_to_bytes writes ascending ids;
@@ -775,7 +789,8 @@ void isl_hnsw_free(isl_hnsw* h);
 uint64_t isl_hnsw_len(const isl_hnsw* h);
 /* HnswGraph::search (hnsw.rs:458-504) for a batch of queries: greedy descent through layers
  * max_level..1, then search_layer on layer 0 with ef = max(ef, k); heap order on distance only
- * (hnsw.rs:136-141), reproduced with an exact BinaryHeap emulation. */
+ * (hnsw.rs:136-141), reproduced with an exact BinaryHeap emulation.  A graph over bf16 rows is searched with
+ * float32 queries all the same: ids and distances are those of the graph over the rows' float32 images. */
 isl_status isl_hnsw_search_batch(const isl_hnsw* h, const float* queries, uint64_t nq, uint64_t d,
                                  uint64_t k, uint64_t ef, uint64_t* out_ids, float* out_dist,
                                  uint32_t* out_count);
@@ -823,6 +838,22 @@ isl_status isl_hnsw_random_levels(uint64_t seed, uint64_t n, double ml, uint64_t
 isl_status isl_hnsw_build(const isl_hnsw_config* cfg, const isl_build_options* opts, const float* vectors,
                           uint64_t n, uint64_t d, const uint64_t* levels, uint64_t level_seed, int32_t mem,
                           int32_t device, isl_hnsw** out);
+/* isl_hnsw_build over rows of either stored type.  dtype ISL_DTYPE_F32: rows = n x d float, the call IS
+ * isl_hnsw_build.  dtype ISL_DTYPE_BF16: rows = n x d bf16 bit patterns (u16), on the host or on `device`; the
+ * graph's vectors are their exact float32 images, so the graph is -- list for list on every layer, under both rules
+ * and any batch -- the one isl_hnsw_build makes of the widened rows, and every search answers as that graph does.
+ * The rows stay bf16: one table of 2-byte elements (isl_hnsw_row_storage) and no float32 copy of them on the device
+ * once the call has returned.  The descent, the selections and the re-selections measure the bf16 rows with the
+ * library's exact-order float32 chain over the images.
+ * Checked in this order before any device call: NULL out, or NULL rows with n > 0 -> ISL_ERR_INVALID_ARGUMENT; opts
+ * as in isl_index_build_ex; an unknown dtype -> ISL_ERR_INVALID_ARGUMENT, ISL_DTYPE_FP8_E4M3 -> ISL_ERR_UNSUPPORTED
+ * (the builders do not take fp8 rows for a LeannIndex either); then as isl_hnsw_build: HnswConfig::validate; n == 0
+ * -> the empty graph (it stores nothing: isl_hnsw_row_storage reports ISL_DTYPE_F32 and 0 bytes); d == 0 ->
+ * ISL_ERR_EMPTY_COLLECTION; levels[i] >= max_layers -> ISL_ERR_INVALID_ARGUMENT; the shape limits ->
+ * ISL_ERR_UNSUPPORTED.  *out is written only on ISL_OK. */
+isl_status isl_hnsw_build_rows(const isl_hnsw_config* cfg, const isl_build_options* opts, const void* rows,
+                               int32_t dtype, uint64_t n, uint64_t d, const uint64_t* levels, uint64_t level_seed,
+                               int32_t mem, int32_t device, isl_hnsw** out);
 /* HnswGraph::insert (hnsw.rs:214-251) for n_new more rows: nodes len .. len + n_new - 1 enter `h` in id order,
  * in place, under the config the handle carries (m, m0, ef_construction, metric, ml, max_layers).  `h` may
  * have been built here, read by isl_hnsw_from_bytes or handed over with isl_hnsw_from_layers.  *first_id
@@ -851,7 +882,8 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg, const isl_build_options* o
  * d == 0 -> ISL_ERR_EMPTY_COLLECTION; levels[i] >= max_layers -> ISL_ERR_INVALID_ARGUMENT; m0 > 128,
  * ef_construction > 512, len + n_new beyond the device id range or more than 64 layers ->
  * ISL_ERR_UNSUPPORTED; and ISL_ERR_UNSUPPORTED, with a message that says which, for a handle whose rows are
- * not resident f32 rows, a handle with a list longer than its layer's M_L (isl_hnsw_from_bytes accepts such
+ * not resident f32 or bf16 rows, a handle whose rows are bf16 (isl_hnsw_insert_rows takes those), a handle
+ * with a list longer than its layer's M_L (isl_hnsw_from_bytes accepts such
  * images; the tables hold M_L + 1 ids -- lists above layer 0 are measured while they are imported), a
  * handle whose layer-0 device copy is not the list verbatim because ids repeated inside a list were removed
  * at upload, and a handle whose levels do not match its layers (the entry point's level is not max_level,
@@ -859,6 +891,20 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg, const isl_build_options* o
 isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts, const float* vectors, uint64_t n_new,
                            uint64_t d, const uint64_t* levels, uint64_t level_seed, int32_t mem,
                            uint64_t* first_id);
+/* isl_hnsw_insert over rows of either stored type; isl_hnsw_insert IS this call with ISL_DTYPE_F32.  rows = n_new x d
+ * elements of `dtype` (float, or bf16 bit patterns as u16), on the host or on the graph's device.  On a non-empty
+ * graph `dtype` must be the stored type of its rows (isl_hnsw_row_storage): the grown graph keeps one table of that
+ * type, the old rows and norms copied beside the new ones on the device.  An empty handle takes the type of the rows
+ * it is given.  The strong guarantee, the `&mut self` rule and the batch == 1 identity are isl_hnsw_insert's: over
+ * bf16 rows the graph after the call is the graph isl_hnsw_build_rows makes of all len + n_new rows.
+ * Checked in this order before any device call: NULL h, or NULL rows with n_new > 0 -> ISL_ERR_INVALID_ARGUMENT;
+ * opts as in isl_hnsw_build; an unknown dtype -> ISL_ERR_INVALID_ARGUMENT, ISL_DTYPE_FP8_E4M3 ->
+ * ISL_ERR_UNSUPPORTED; then as isl_hnsw_insert from n_new == 0 on, with one refusal more behind the residency of
+ * the rows: a non-empty graph that stores another type than `dtype` -> ISL_ERR_UNSUPPORTED (isl_index_insert's
+ * rule).  *first_id is written only on ISL_OK. */
+isl_status isl_hnsw_insert_rows(isl_hnsw* h, const isl_build_options* opts, const void* rows, int32_t dtype,
+                                uint64_t n_new, uint64_t d, const uint64_t* levels, uint64_t level_seed, int32_t mem,
+                                uint64_t* first_id);
 /* Rows out of a built HnswGraph, in place (extension: the reference has no removal).  `h` may have been built
  * here, grown by isl_hnsw_insert, read by isl_hnsw_from_bytes or handed over with isl_hnsw_from_layers.  ids =
  * n_ids node ids in host memory, repeated ids counting once: the set D.  opts = the selection rule of this call
@@ -866,7 +912,8 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts, const flo
  * as with isl_hnsw_insert.  out_remap [old len] (may be NULL) receives the new id of every old node or ISL_REMOVED,
  * *out_len (may be NULL) the new len; both are written only on ISL_OK.
  * Definition, over a graph with layers 0 .. max_level, L_L[p] = neighbors_at(L) of node p in stored order,
- * M_L = m0 on layer 0 and m above, and resident f32 rows:
+ * M_L = m0 on layer 0 and m above, and resident f32 or bf16 rows (the vectors of bf16 rows are their exact float32
+ * images; the shrunk graph keeps the stored type, fp8 rows stay refused):
  * 1. Repair, per layer.  Every layer is repaired independently and every list comes from the OLD lists of that
  *    layer only.  For every layer L and every survivor p with level[p] >= L: if no id of L_L[p] is in D,
  *    L'_L[p] = L_L[p].  Otherwise the candidate list C_L(p), built as isl_index_remove builds C(p) but on layer L:
@@ -896,7 +943,7 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts, const flo
  * The call is the reference's &mut self: not beside searches on the same handle.  Checked in this order before any
  * device call: NULL h, or NULL ids with n_ids > 0 -> ISL_ERR_INVALID_ARGUMENT; opts as in isl_hnsw_build;
  * n_ids == 0 -> ISL_OK, nothing changed, out_remap the identity; an id >= len -> ISL_ERR_NODE_NOT_FOUND (node); a
- * non-empty graph whose rows are not resident f32 rows -> ISL_ERR_UNSUPPORTED; nodes but no entry point, or levels
+ * non-empty graph whose rows are not resident f32 or bf16 rows -> ISL_ERR_UNSUPPORTED; nodes but no entry point, or levels
  * that do not match the layers (as isl_hnsw_insert refuses them) -> ISL_ERR_UNSUPPORTED; m0 > 128 or more than 64
  * layers -> ISL_ERR_UNSUPPORTED; a busy lane -> ISL_ERR_SEARCH.  Refused once the import kernel has looked, each
  * with ISL_ERR_UNSUPPORTED and a message that says which: a list longer than its layer's M_L; a layer-0 device
@@ -913,10 +960,18 @@ isl_status isl_hnsw_levels(const isl_hnsw* h, uint64_t* out /* [len] */);
  * (None; *count = 0).  node >= len -> ISL_ERR_NODE_NOT_FOUND. */
 isl_status isl_hnsw_get_neighbors(const isl_hnsw* h, uint64_t node, uint64_t layer, uint64_t* out,
                                   uint64_t cap, uint64_t* count, int32_t* has_layer);
+/* HnswNode::vector as float32.  Over bf16 rows: the exact float32 images of the stored bits. */
 isl_status isl_hnsw_get_vector(const isl_hnsw* h, uint64_t node, float* out /* [dim] */);
+/* What the graph's rows cost on the device (isl_index_row_storage of the facade): their stored type (ISL_DTYPE_F32
+ * or ISL_DTYPE_BF16) and the bytes of the row table.  Either out pointer may be NULL.  An empty graph stores
+ * nothing: ISL_DTYPE_F32 and 0 bytes.  NULL h -> ISL_ERR_INVALID_ARGUMENT. */
+isl_status isl_hnsw_row_storage(const isl_hnsw* h, int32_t* dtype, uint64_t* block_bytes);
 /* HnswGraph::to_bytes, hnsw.rs:507-509: the bincode image isl_hnsw_from_bytes reads, nodes in ascending
  * id (the reference's HashMap order is arbitrary), next_id = len; ml / max_layers as built or parsed
- * (isl_hnsw_from_layers: the default config's).  Free with isl_free_bytes. */
+ * (isl_hnsw_from_layers: the default config's).  Free with isl_free_bytes.
+ * The format has one vector field, Vec<f32>: over bf16 rows the widened values are written, so the image of a bf16
+ * graph is byte for byte the image of the float32 graph over the widened rows, and isl_hnsw_from_bytes of it gives a
+ * graph that stores float32 rows. */
 isl_status isl_hnsw_to_bytes(const isl_hnsw* h, uint8_t** out, size_t* len);
 
 /* isl_distance_matrix for bf16 queries and rows (bit patterns; BASELINE config 5: d = 4096 bf16): the

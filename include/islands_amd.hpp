@@ -372,6 +372,39 @@ class HnswGraph {
                          level_seed, ISL_MEM_HOST, device, &g.h_));
     return g;
   }
+  // build() from bf16 rows (isl_hnsw_build_rows): rows_bits = n x dim bf16 bit patterns.  The graph is the one
+  // build() makes of their exact float32 images; the rows stay bf16 on the device (row_storage()).
+  static HnswGraph build_bf16(const std::vector<uint16_t>& rows_bits, uint64_t dim, const isl_hnsw_config* cfg = nullptr,
+                              const std::vector<uint64_t>& levels = {}, uint64_t level_seed = 0,
+                              const isl_build_options* opts = nullptr, int32_t device = 0) {
+    HnswGraph g;
+    const uint64_t n = dim ? rows_bits.size() / dim : 0;
+    check(isl_hnsw_build_rows(cfg, opts, n ? rows_bits.data() : nullptr, ISL_DTYPE_BF16, n, dim,
+                              levels.empty() ? nullptr : levels.data(), level_seed, ISL_MEM_HOST, device, &g.h_));
+    return g;
+  }
+  // insert() for a graph that stores bf16 rows (isl_hnsw_insert_rows); an empty graph becomes a bf16 graph.  Rows
+  // of the other type than the graph stores are refused (Unsupported) and leave the graph unchanged.
+  uint64_t insert_bf16(const std::vector<uint16_t>& rows_bits, uint64_t dim, const std::vector<uint64_t>& levels = {},
+                       uint64_t level_seed = 0, const isl_build_options* opts = nullptr) {
+    const uint64_t n = dim ? rows_bits.size() / dim : 0;
+    uint64_t first = 0;
+    check(isl_hnsw_insert_rows(h_, opts, n ? rows_bits.data() : nullptr, ISL_DTYPE_BF16, n, dim,
+                               levels.empty() ? nullptr : levels.data(), level_seed, ISL_MEM_HOST, &first));
+    if (n) vectors_.clear();
+    return first;
+  }
+  // What the rows cost on the device (isl_hnsw_row_storage): the stored type (ISL_DTYPE_F32 / ISL_DTYPE_BF16) and
+  // the bytes of the row table; an empty graph: ISL_DTYPE_F32 and 0.
+  struct RowStorage {
+    int32_t dtype;
+    uint64_t block_bytes;
+  };
+  RowStorage row_storage() const {
+    RowStorage s{ISL_DTYPE_F32, 0};
+    check(isl_hnsw_row_storage(h_, &s.dtype, &s.block_bytes));
+    return s;
+  }
   // HnswGraph::insert (hnsw.rs:214-251) for more rows, in place (isl_hnsw_insert): nodes len .. len + n - 1 under
   // the config the graph carries; returns the first new id.  `levels` empty = the level_seed stream continued at
   // position len; opts NULL = the reference rule, one node per step.  On an error the graph is unchanged.

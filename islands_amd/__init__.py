@@ -1041,16 +1041,19 @@ class HnswGraph:
     """HnswGraph (hnsw.rs:149-515) on the device.  `build` constructs one from its vectors
     (HnswGraph::insert, hnsw.rs:214-329, as isl_hnsw_build); the constructor takes a graph made
     elsewhere as per-layer adjacency (`layers[L][node]` = neighbour ids of `node` on layer L, empty
-    above the node's level); `from_bytes` / `to_bytes` carry the bincode image."""
+    above the node's level); `from_bytes` / `to_bytes` carry the bincode image.  The `_bf16` forms (`build_bf16`,
+    `insert_bf16`, `from_layers_bf16`) take bf16 bit patterns and keep them as such on the device: the graph is the
+    one over their exact f32 images, at half the row bytes (`row_storage`)."""
 
     def __init__(self, vectors, layers, levels, entry_point: int | None, max_level: int,
                  m: int = 16, m0: int = 32, ef_construction: int = 200,
-                 metric: DistanceMetric = DistanceMetric.Cosine, device: int = 0):
-        v = _f32(vectors)
+                 metric: DistanceMetric = DistanceMetric.Cosine, device: int = 0, _dtype: int = 0):
+        v = _f32(vectors) if _dtype == 0 else np.ascontiguousarray(vectors, dtype=np.uint16)
         if v.ndim != 2:
             v = v.reshape(len(levels), -1) if len(levels) else v.reshape(0, 0)
         n, d = (v.shape if v.size else (0, 0))
-        self.vectors, self.m, self.m0 = v, m, m0
+        # (bf16 rows: get_vector asks the library, which widens)
+        self.vectors, self.m, self.m0 = (v if _dtype == 0 else None), m, m0
         self.ef_construction, self.metric = ef_construction, DistanceMetric(metric)
         offs, adjs = [], []
         for L in range(len(layers)):
@@ -1067,11 +1070,40 @@ class HnswGraph:
         padj = (C.c_void_p * max(nl, 1))(*[a.ctypes.data for a in adjs])
         lv = np.ascontiguousarray(levels, dtype=np.uint64)
         h = C.c_void_p()
-        _check(_ffi.lib().isl_hnsw_from_layers(
+        _check(_ffi.lib().isl_hnsw_from_layers_rows(
             m, m0, ef_construction, int(metric), n, d, nl, poff, padj,
             _ptr(lv) if n else None, 0 if entry_point is None else 1, entry_point or 0,
-            max_level, _ptr(v) if n else None, device, C.byref(h)))
+            max_level, _ptr(v) if n else None, _dtype, device, C.byref(h)))
         self._h = h
+
+    @classmethod
+    def from_layers_bf16(cls, rows_bits, layers, levels, entry_point: int | None, max_level: int,
+                         m: int = 16, m0: int = 32, ef_construction: int = 200,
+                         metric: DistanceMetric = DistanceMetric.Cosine, device: int = 0) -> "HnswGraph":
+        """The constructor for a graph whose rows are bf16 (isl_hnsw_from_layers_rows): `rows_bits` is [n, d]
+        uint16 bit patterns.  The graph's vectors are their exact f32 images; the rows stay bf16 on the device."""
+        return cls(rows_bits, layers, levels, entry_point, max_level, m, m0, ef_construction, metric, device, _dtype=1)
+
+    @staticmethod
+    def _rows_arg(rows, dtype: int, as_matrix: bool):
+        """(keep-alive, pointer, n, d, on_device) of f32 rows (dtype 0) or bf16 bit patterns (dtype 1): an array, or
+        a torch tensor resident on the device (float32; int16 / uint16 / bfloat16)."""
+        want = ("torch.float32",) if dtype == 0 else ("torch.uint16", "torch.int16", "torch.bfloat16")
+        on_device = hasattr(rows, "data_ptr") and getattr(rows, "is_cuda", False)
+        if on_device:
+            v = rows.contiguous()
+            if str(v.dtype) not in want:
+                raise TypeError("device rows must be float32" if dtype == 0 else
+                                "device rows must be bf16 (or their 16-bit patterns)")
+            if as_matrix and v.dim() == 1:
+                v = v.reshape(1, -1)
+            n, d = (int(v.shape[0]), int(v.shape[1])) if v.dim() == 2 else (0, 0)
+            return v, C.c_void_p(v.data_ptr()), n, d, True
+        v = _f32(rows) if dtype == 0 else np.ascontiguousarray(rows, dtype=np.uint16)
+        if as_matrix and v.ndim == 1:
+            v = v.reshape(1, -1)
+        n, d = v.shape if v.ndim == 2 else (0, 0)
+        return v, _ptr(v), n, d, False
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -1117,17 +1149,25 @@ class HnswGraph:
         is the rule for an index meant to be searched.  batch > 1 inserts that many nodes per step
         (same rules, no parity claim).  `vectors`: an array, or a float32 torch tensor resident on
         `device` (used in place)."""
-        on_device = hasattr(vectors, "data_ptr") and getattr(vectors, "is_cuda", False)
-        if on_device:
-            v = vectors.contiguous()
-            if str(v.dtype) != "torch.float32":
-                raise TypeError("device rows must be float32")
-            n, d = (int(v.shape[0]), int(v.shape[1])) if v.dim() == 2 else (0, 0)
-            vp = C.c_void_p(v.data_ptr())
-        else:
-            v = _f32(vectors)
-            n, d = v.shape if v.ndim == 2 else (0, 0)
-            vp = _ptr(v)
+        return cls._build(vectors, 0, m, m0, ef_construction, metric, ml, max_layers, levels, level_seed, batch,
+                          select, alpha, keep_pruned, device)
+
+    @classmethod
+    def build_bf16(cls, rows_bits, m: int = 16, m0: int = 32, ef_construction: int = 200,
+                   metric: DistanceMetric = DistanceMetric.Cosine, ml: float | None = None, max_layers: int = 16,
+                   levels=None, level_seed: int = 0, batch: int = 1, select="reference", alpha: float = 1.0,
+                   keep_pruned: bool = True, device: int = 0) -> "HnswGraph":
+        """build() from bf16 rows (isl_hnsw_build_rows): `rows_bits` is [n, d] uint16 bit patterns, or a torch
+        int16 / uint16 / bfloat16 tensor resident on `device`.  The graph is the one build() makes from their
+        exact f32 images, list for list, and searches answer as that graph does; the rows stay bf16 on the
+        device -- half the bytes (row_storage())."""
+        return cls._build(rows_bits, 1, m, m0, ef_construction, metric, ml, max_layers, levels, level_seed, batch,
+                          select, alpha, keep_pruned, device)
+
+    @classmethod
+    def _build(cls, rows, dtype, m, m0, ef_construction, metric, ml, max_layers, levels, level_seed, batch, select,
+               alpha, keep_pruned, device) -> "HnswGraph":
+        v, vp, n, d, on_device = cls._rows_arg(rows, dtype, False)
         c = _ffi.HnswConfigC()
         _ffi.lib().isl_hnsw_config_default(C.byref(c))
         c.m, c.m0, c.ef_construction, c.metric, c.max_layers = m, m0, ef_construction, int(metric), max_layers
@@ -1138,9 +1178,9 @@ class HnswGraph:
             raise ValueError("one level per row")
         o = LeannIndex._build_options(select, alpha, keep_pruned, batch)
         h = C.c_void_p()
-        _check(_ffi.lib().isl_hnsw_build(C.byref(c), C.byref(o), vp if n else None, n, d,
-                                         None if lv is None or not n else _ptr(lv), level_seed,
-                                         MEM_DEVICE if on_device else MEM_HOST, device, C.byref(h)))
+        _check(_ffi.lib().isl_hnsw_build_rows(C.byref(c), C.byref(o), vp if n else None, dtype, n, d,
+                                              None if lv is None or not n else _ptr(lv), level_seed,
+                                              MEM_DEVICE if on_device else MEM_HOST, device, C.byref(h)))
         g = cls.__new__(cls)
         g._h = h
         g._keep = None
@@ -1156,30 +1196,28 @@ class HnswGraph:
         at position len, so build(v, level_seed=s) equals build(v[:n0], level_seed=s) then
         insert(v[n0:], level_seed=s).  With batch = 1 the graph afterwards is the one `build` makes of all
         rows.  On an error the graph is unchanged.  `vectors`: an array, or a float32 torch tensor resident
-        on the graph's device.  Not beside searches on the same graph."""
-        on_device = hasattr(vectors, "data_ptr") and getattr(vectors, "is_cuda", False)
-        if on_device:
-            v = vectors.contiguous()
-            if str(v.dtype) != "torch.float32":
-                raise TypeError("device rows must be float32")
-            if v.dim() == 1:
-                v = v.reshape(1, -1)
-            n, d = int(v.shape[0]), int(v.shape[1])
-            vp = C.c_void_p(v.data_ptr())
-        else:
-            v = _f32(vectors)
-            if v.ndim == 1:
-                v = v.reshape(1, -1)
-            n, d = v.shape
-            vp = _ptr(v)
+        on the graph's device.  The graph must store float32 rows (an empty one takes them as `build` would).
+        Not beside searches on the same graph."""
+        return self._insert(vectors, 0, levels, level_seed, batch, select, alpha, keep_pruned)
+
+    def insert_bf16(self, rows_bits, levels=None, level_seed: int = 0, batch: int = 1, select="reference",
+                    alpha: float = 1.0, keep_pruned: bool = True) -> int:
+        """insert() for a graph that stores bf16 rows (isl_hnsw_insert_rows): `rows_bits` is [n, d] uint16 bit
+        patterns (or a 16-bit torch tensor on the graph's device).  The construction runs over their exact f32
+        images and the grown graph keeps bf16 rows; an empty graph becomes a bf16 graph.  Rows of the other type
+        than the graph stores are refused (Unsupported) and leave the graph unchanged."""
+        return self._insert(rows_bits, 1, levels, level_seed, batch, select, alpha, keep_pruned)
+
+    def _insert(self, rows, dtype, levels, level_seed, batch, select, alpha, keep_pruned) -> int:
+        v, vp, n, d, on_device = self._rows_arg(rows, dtype, True)
         lv = None if levels is None else np.ascontiguousarray(levels, dtype=np.uint64).reshape(-1)
         if lv is not None and lv.size != n:
             raise ValueError("one level per row")
         o = LeannIndex._build_options(select, alpha, keep_pruned, batch)
         first = u64()
-        _check(_ffi.lib().isl_hnsw_insert(self._h, C.byref(o), vp if n else None, n, d,
-                                          None if lv is None or not n else _ptr(lv), level_seed,
-                                          MEM_DEVICE if on_device else MEM_HOST, C.byref(first)))
+        _check(_ffi.lib().isl_hnsw_insert_rows(self._h, C.byref(o), vp if n else None, dtype, n, d,
+                                               None if lv is None or not n else _ptr(lv), level_seed,
+                                               MEM_DEVICE if on_device else MEM_HOST, C.byref(first)))
         # what the object kept of the smaller graph: the library answers for the grown one
         self._levels = None
         self.vectors = None
@@ -1262,6 +1300,13 @@ class HnswGraph:
             return C.string_at(p, n.value)
         finally:
             _ffi.lib().isl_free_bytes(p)
+
+    def row_storage(self) -> dict:
+        """What the graph's rows cost on the device (isl_hnsw_row_storage): {"dtype": ISL_DTYPE_* (0 f32, 1 bf16),
+        "block_bytes": bytes of the row table}.  An empty graph stores nothing: dtype 0 and 0 bytes."""
+        dt, nb = _ffi.i32(0), u64(0)
+        _check(_ffi.lib().isl_hnsw_row_storage(self._h, C.byref(dt), C.byref(nb)))
+        return {"dtype": int(dt.value), "block_bytes": int(nb.value)}
 
     def last_stats(self) -> dict:
         s = SearchStatsC()

@@ -213,6 +213,13 @@ SIGNATURES = {
     "isl_index_remove": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, C.c_void_p, P(u64)]),
     "isl_hnsw_insert": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, u64, C.c_void_p, u64, i32, P(u64)]),
     "isl_hnsw_remove": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, u64, C.c_void_p, P(u64)]),
+    "isl_hnsw_build_rows": (i32, [P(HnswConfigC), P(BuildOptionsC), C.c_void_p, i32, u64, u64, C.c_void_p, u64, i32,
+                                  i32, P(C.c_void_p)]),
+    "isl_hnsw_insert_rows": (i32, [C.c_void_p, P(BuildOptionsC), C.c_void_p, i32, u64, u64, C.c_void_p, u64, i32,
+                                   P(u64)]),
+    "isl_hnsw_from_layers_rows": (i32, [u64, u64, u64, i32, u64, u64, u64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, i32, u64, u64, C.c_void_p, i32, i32, P(C.c_void_p)]),
+    "isl_hnsw_row_storage": (i32, [C.c_void_p, P(i32), P(u64)]),
     "isl_hnsw_info": (i32, [C.c_void_p, P(i32), P(u64), P(u64), P(u64)]),
     "isl_hnsw_levels": (i32, [C.c_void_p, C.c_void_p]),
     "isl_hnsw_get_neighbors": (i32, [C.c_void_p, u64, u64, C.c_void_p, u64, P(u64), P(i32)]),

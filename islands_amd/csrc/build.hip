@@ -101,22 +101,11 @@ __device__ __forceinline__ float load_row_query(const SelCtx& c, uint32_t id, fl
   __syncthreads();
   return (METRIC == ISL_METRIC_COSINE || METRIC == METRIC_COSINE_PRE) ? c.norm2[id] : 0.0f;
 }
-// The same for a bf16 row: widened (exactly) into the f32 query area, 8 elements per lane and turn.  A row
-// starts 16-byte aligned and is padded with zeros to 8 elements; the area holds d rounded up to 32.
+// The same for a bf16 row: widened (exactly) into the f32 query area (widen_row_query, device_common.hip.h, which
+// the HnswGraph builder's descent shares)
 template <int METRIC>
 __device__ __forceinline__ float load_row_query(const SelCtxT<uint16_t>& c, uint32_t id, float* qs) {
-  const uint16_t* q = c.emb + (uint64_t)id * c.stride;
-  const uint32_t d8 = (c.d + 7u) & ~7u;
-  for (uint32_t j = threadIdx.x * 8u; j < d8; j += 512u) {
-    const v4u w = *reinterpret_cast<const v4u*>(q + j);
-    *reinterpret_cast<float4*>(qs + j) =
-        make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
-                    __uint_as_float(w.y & 0xFFFF0000u));
-    *reinterpret_cast<float4*>(qs + j + 4u) =
-        make_float4(__uint_as_float(w.z << 16), __uint_as_float(w.z & 0xFFFF0000u), __uint_as_float(w.w << 16),
-                    __uint_as_float(w.w & 0xFFFF0000u));
-  }
-  __syncthreads();
+  widen_row_query(c.emb + (uint64_t)id * c.stride, c.d, qs);
   return (METRIC == ISL_METRIC_COSINE || METRIC == METRIC_COSINE_PRE) ? c.norm2[id] : 0.0f;
 }
 
@@ -334,7 +323,7 @@ __global__ __launch_bounds__(64) void select_neighbors_kernel(SelectNeighborsPar
 // selected neighbour takes the back link only if it has the layer, the new id is appended without a
 // `contains` test, and the reference rule's re-sort (prune_connections, :405-446) leaves the new id out --
 // it looks every id up in the node map, which the node being inserted has not entered yet.
-// ROWT = uint16_t: LeannIndex::build over bf16 rows (no tile; norm_a of a row is its norm2, the bits the
+// ROWT = uint16_t: either builder over bf16 rows (no tile; norm_a of a row is its norm2, the bits the
 // d-step sum over the widened values gives).
 template <int METRIC_API, bool DIVERSE = false, bool HNSW = false, typename ROWT = float>
 __global__ __launch_bounds__(64) void link_kernel(BuildParams p) {
@@ -479,12 +468,22 @@ __global__ void gather_rows_kernel(const float* __restrict__ emb, uint64_t strid
   if (i >= (uint64_t)B * d) return;
   out[i] = emb[(id0 + i / d) * stride + i % d];
 }
-// ... from bf16 rows: the queries of a step are the widened rows
+// ... from bf16 rows: the queries of a step are the widened rows.  One kernel for both builders: query i is node
+// id0 + i (LeannIndex::build; node_ids NULL) or node_ids[i] (one layer of an HnswGraph under construction, which
+// also takes where each query starts, as gather_layer_kernel of hnsw_build.hip leaves it for f32 rows)
 __global__ void gather_rows_bf16_kernel(const uint16_t* __restrict__ emb, uint64_t stride, uint32_t d,
-                                        uint64_t id0, uint32_t B, float* __restrict__ out) {
+                                        uint64_t id0, const uint32_t* __restrict__ node_ids, uint32_t B,
+                                        const uint32_t* __restrict__ cur_of, const uint32_t* __restrict__ evals_of,
+                                        float* __restrict__ out, uint32_t* __restrict__ q_entry,
+                                        uint32_t* __restrict__ q_evals) {
   uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (node_ids && i < B) {
+    q_entry[i] = cur_of[node_ids[i]];
+    q_evals[i] = evals_of[node_ids[i]];
+  }
   if (i >= (uint64_t)B * d) return;
-  out[i] = __uint_as_float((uint32_t)emb[(id0 + i / d) * stride + i % d] << 16);
+  const uint64_t node = node_ids ? node_ids[i / d] : id0 + i / d;
+  out[i] = __uint_as_float((uint32_t)emb[node * stride + i % d] << 16);
 }
 
 // ---------------------------------------------------------------- isl_index_remove
@@ -661,9 +660,11 @@ void launch_link_as(uint32_t metric, uint32_t grid, size_t lds, const BuildParam
   });
 }
 void launch_link(uint32_t metric, bool diverse, bool hnsw, uint32_t grid, size_t lds, const BuildParams& p) {
-  if (p.emb16) {  // LeannIndex::build alone takes bf16 rows (Scaffold::open)
-    if (diverse) launch_link_as<true, false, uint16_t>(metric, grid, lds, p);
-    else launch_link_as<false, false, uint16_t>(metric, grid, lds, p);
+  if (p.emb16) {  // bf16 rows, either builder
+    if (!diverse && !hnsw) launch_link_as<false, false, uint16_t>(metric, grid, lds, p);
+    else if (!hnsw) launch_link_as<true, false, uint16_t>(metric, grid, lds, p);
+    else if (!diverse) launch_link_as<false, true, uint16_t>(metric, grid, lds, p);
+    else launch_link_as<true, true, uint16_t>(metric, grid, lds, p);
   }
   else if (!diverse && !hnsw) launch_link_as<false, false>(metric, grid, lds, p);
   else if (!hnsw) launch_link_as<true, false>(metric, grid, lds, p);
@@ -940,10 +941,8 @@ isl_status Scaffold::alloc_bytes(void** out, uint64_t bytes, bool zero, bool kep
 isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw_, const void* vectors,
                           int32_t dtype, uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0,
                           uint32_t ef, const isl_index* old) {
-  if (dtype != ISL_DTYPE_F32 && hnsw_) return isl::fail(ISL_ERR_UNSUPPORTED, "the HnswGraph builder keeps f32 vectors");
   ISL_TRY(isl_index_new(&cfg, &g));
   g->cfg.prune_ratio = 0.0f;  // construction searches do not prune (leann.rs:692-749)
-  g->is_hnsw = hnsw_;         // HnswGraph heap order: distance alone
   g->host_csr_valid = false;
   g->num_nodes = n;
   g->device = device;
@@ -952,6 +951,9 @@ isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& 
   g->max_degree = m0;  // the widest row a construction search can meet: a row is back at <= m0 ids before the next search
   if (old) ISL_TRY(isl::set_grown_embeddings(g, old, vectors, dtype, n - old->nvec, d, mem));
   else ISL_TRY(isl_set_embeddings(g, vectors, n, d, dtype, mem));
+  // HnswGraph heap order: distance alone.  (Set once the rows are in: isl_set_embeddings refuses a caller who swaps
+  // the rows of a facade's core index for another type; the builder's own graph takes the type it is given.)
+  g->is_hnsw = hnsw_;
   hnsw = hnsw_;
   diverse = opts.select_rule == ISL_SELECT_DIVERSE;
   ISL_TRY(alloc(&p.lock, n, true));
@@ -993,6 +995,13 @@ isl_status Scaffold::insert(const Table& t, uint32_t cnt, bool locking, uint64_t
   }
   if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "builder launch failed");
   return ISL_OK;
+}
+
+void Scaffold::gather_bf16(uint64_t id0, uint32_t cnt, const uint32_t* node_ids, const uint32_t* cur_of,
+                           const uint32_t* evals_of) {
+  hipLaunchKernelGGL(gather_rows_bf16_kernel, dim3((uint32_t)(((uint64_t)cnt * p.d + 255) / 256)), dim3(256), 0, 0,
+                     g->rows.bf16(), g->rows.stride(), p.d, id0, node_ids, cnt, cur_of, evals_of, qbuf, g->build_q_entry,
+                     g->build_q_evals);
 }
 
 isl_status Scaffold::csr_to_table(const Table& t, const uint64_t* off, const uint32_t* adj, uint64_t nnz, uint64_t n0,
@@ -1127,8 +1136,7 @@ isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts,
     g->entry_point = entry;  // :669: entry_point.unwrap_or(0) as of the start of the step
     const dim3 ggrid((uint32_t)((s.count * d + 255) / 256));
     if (g->rows.is_bf16())  // the step's queries are the widened rows
-      hipLaunchKernelGGL(gather_rows_bf16_kernel, ggrid, dim3(256), 0, 0, g->rows.bf16(), g->rows.stride(), (uint32_t)d,
-                         s.first, s.count, c.qbuf);
+      c.gather_bf16(s.first, s.count);
     else
       hipLaunchKernelGGL(gather_rows_kernel, ggrid, dim3(256), 0, 0, g->rows.f32(), g->rows.stride(), (uint32_t)d,
                          s.first, s.count, c.qbuf);

@@ -36,7 +36,7 @@ struct BuildParams {
   const uint32_t* node_levels;  // [n] HnswNode::level
   uint32_t layer;
   uint32_t* cur_of;             // [n] `current` of every node being inserted: selected[0] after a layer
-  // LeannIndex::build over bf16 rows (isl_index_build_rows): the table the kernels' bf16 instantiations read
+  // bf16 rows (isl_index_build_rows, isl_hnsw_build_rows): the table the kernels' bf16 instantiations read
   // instead of emb (NULL otherwise); stride is then in bf16 elements, norm2 is of the widened values
   const uint16_t* emb16;
 };
@@ -50,7 +50,8 @@ isl_status resolve_build_options(const isl_build_options* in, bool need_rule, is
 bool device_lists_differ(const isl_index* idx);
 // old -> new ids of a removal for the caller, ISL_REMOVED for a removed one; `remap` NULL: nothing was removed
 void write_remap(const std::vector<uint32_t>* remap, uint64_t n0, uint64_t* out_remap);
-// bytes of LDS of the reference-rule link kernel and of the insertion descent (tile + query)
+// bytes of LDS of the reference-rule link kernel and of the insertion descent over f32 rows (tile + query; bf16 rows:
+// isl_plan::link_lds_bf16)
 size_t link_lds(uint64_t d);
 // ISL_DTYPE_F32 / ISL_DTYPE_BF16, before any device call
 isl_status check_row_dtype(int32_t dtype);
@@ -92,8 +93,7 @@ struct Scaffold {
   isl_status alloc_bytes(void** out, uint64_t bytes, bool zero, bool kept);
   // The construction graph over `vectors` and the buffers of steps of up to B nodes, rows of up to m0 ids.
   // cfg: metric (and, for LeannIndex::build, the hub rule); opts: the selection rule.
-  // dtype: what `vectors` holds and the construction graph stores (isl_set_embeddings); bf16 rows are for
-  // LeannIndex::build alone (not with hnsw).
+  // dtype: what `vectors` holds and the construction graph stores (isl_set_embeddings): f32 or bf16, either builder.
   // With `old` (a finished graph that grows, isl_index_insert / isl_hnsw_insert) the rows come from two sources:
   // the first old->nvec of the n are old's rows and norms, copied on the device; `vectors` holds the
   // n - old->nvec new ones, of old's stored type.
@@ -105,6 +105,11 @@ struct Scaffold {
   // on `layer` of an HnswGraph.  Returns once the kernels are launched.
   isl_status insert(const Table& t, uint32_t cnt, bool locking, uint64_t id0, const uint32_t* node_ids = nullptr,
                     uint32_t layer = 0);
+  // bf16 rows: the queries of a step, widened into qbuf -- nodes id0 .. id0 + cnt - 1, or node_ids[] of an HnswGraph
+  // layer, whose searches also start where cur_of / evals_of say (g->build_q_entry / build_q_evals).  Enqueues one
+  // kernel; the caller reads hipGetLastError.
+  void gather_bf16(uint64_t id0, uint32_t cnt, const uint32_t* node_ids = nullptr, const uint32_t* cur_of = nullptr,
+                   const uint32_t* evals_of = nullptr);
   // CSR arrays of a finished layer -> the first n0 rows of table `t` (one wave per row), the way back in
   // for a graph that grows.  *d_flag (device, zeroed by the caller) collects what the table cannot take:
   // 1 = a list longer than t.M, 2 = offsets that do not fit `nnz`, 4 = an id that is not below n0; such a

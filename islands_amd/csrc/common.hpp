@@ -389,6 +389,9 @@ void free_group_state(isl_index* idx);
 isl_status ensure_padded_adjacency(isl_index* idx);
 // hnsw.hip -- HnswConfig::validate (hnsw.rs:72-85) and the metric's range
 isl_status hnsw_config_validate(uint64_t m, uint64_t m0, uint64_t ef_construction, int64_t metric);
+// hnsw.hip -- the row types an HnswGraph stores, before any device call: f32 or bf16; fp8 -> ISL_ERR_UNSUPPORTED,
+// anything else -> ISL_ERR_INVALID_ARGUMENT
+isl_status hnsw_row_dtype(int32_t dtype);
 // hnsw.hip -- the upper layers of a finished graph, device CSR arrays per layer (entry 0 unused: layer 0 is the
 // core index): uploads the two pointer tables the descent reads and records them in `h`
 isl_status attach_upper_layers(isl_hnsw* h, const std::vector<const uint64_t*>& offs,

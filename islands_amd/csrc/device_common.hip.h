@@ -924,4 +924,21 @@ __device__ __forceinline__ float load_query_bf16(const float* __restrict__ q, ui
   return na;
 }
 
+// A stored bf16 row as the query of the distance routines: widened (exactly) into the f32 query area, 8 elements
+// per lane and turn.  A row starts 16-byte aligned and is padded with zeros to 8 elements; the area holds d rounded
+// up to 32.  (norm_a of such a query is the row's own norm2: the caller reads it, nothing is summed here.)
+__device__ __forceinline__ void widen_row_query(const uint16_t* __restrict__ q, uint32_t d, float* qs) {
+  const uint32_t d8 = (d + 7u) & ~7u;
+  for (uint32_t j = threadIdx.x * 8u; j < d8; j += 512u) {
+    const v4u w = *reinterpret_cast<const v4u*>(q + j);
+    *reinterpret_cast<float4*>(qs + j) =
+        make_float4(__uint_as_float(w.x << 16), __uint_as_float(w.x & 0xFFFF0000u), __uint_as_float(w.y << 16),
+                    __uint_as_float(w.y & 0xFFFF0000u));
+    *reinterpret_cast<float4*>(qs + j + 4u) =
+        make_float4(__uint_as_float(w.z << 16), __uint_as_float(w.z & 0xFFFF0000u), __uint_as_float(w.w << 16),
+                    __uint_as_float(w.w & 0xFFFF0000u));
+  }
+  __syncthreads();
+}
+
 }  // namespace isl_dev

@@ -56,13 +56,27 @@ isl_status ensure_host_layers(const isl_hnsw* h) {
 // HnswNode::level: what the caller supplied, or 0 for all where a handle came without levels
 uint64_t level_of(const isl_index* c, uint64_t i) { return i < c->levels.size() ? c->levels[i] : 0; }
 
-// node rows [i0, i0 + cnt) of the handle's f32 provider -> host
+// node rows [i0, i0 + cnt) of the handle's provider -> host, as f32: the rows themselves, or the exact images of
+// bf16 rows -- their bits staged on the host a chunk at a time and widened there (nothing is allocated on the device)
 isl_status read_rows(const isl_index* c, uint64_t i0, uint64_t cnt, float* out) {
-  if (!cnt || !c->rows.d()) return ISL_OK;
-  if (!c->rows.f32()) return isl::fail(ISL_ERR_EMBEDDING, "Embedding error: no embedding provider attached");
+  const uint64_t d = c->rows.d(), stride = c->rows.stride();
+  if (!cnt || !d) return ISL_OK;
+  if (!c->rows.f32() && !c->rows.bf16())
+    return isl::fail(ISL_ERR_EMBEDDING, "Embedding error: no embedding provider attached");
   ISL_TRY(isl::use_device(c->device));
-  ISL_HIP(hipMemcpy2D(out, c->rows.d() * 4, c->rows.f32() + i0 * c->rows.stride(), c->rows.stride() * 4, c->rows.d() * 4, cnt,
-                      hipMemcpyDeviceToHost));
+  if (c->rows.f32()) {
+    ISL_HIP(hipMemcpy2D(out, d * 4, c->rows.f32() + i0 * stride, stride * 4, d * 4, cnt, hipMemcpyDeviceToHost));
+    return ISL_OK;
+  }
+  const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(cnt, ((uint64_t)16 << 20) / d));  // 32 MiB of bits
+  std::vector<uint16_t> bits((size_t)(chunk * d));
+  for (uint64_t o = 0; o < cnt; o += chunk) {
+    const uint64_t rows = std::min(chunk, cnt - o);
+    ISL_HIP(hipMemcpy2D(bits.data(), d * 2, c->rows.bf16() + (i0 + o) * stride, stride * 2, d * 2, rows,
+                        hipMemcpyDeviceToHost));
+    uint32_t* w = reinterpret_cast<uint32_t*>(out + (size_t)(o * d));
+    for (uint64_t j = 0; j < rows * d; ++j) w[j] = (uint32_t)bits[j] << 16;
+  }
   return ISL_OK;
 }
 
@@ -74,6 +88,12 @@ isl_status isl::hnsw_config_validate(uint64_t m, uint64_t m0, uint64_t ef_constr
   if (m0 < m) return fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: M0 must be >= M");
   if (ef_construction < m) return fail(ISL_ERR_INVALID_CONFIG, "Invalid configuration: ef_construction must be >= M");
   if (metric < 0 || metric > ISL_METRIC_MANHATTAN) return fail(ISL_ERR_INVALID_ARGUMENT, "unknown metric");
+  return ISL_OK;
+}
+
+isl_status isl::hnsw_row_dtype(int32_t dtype) {
+  if (dtype == ISL_DTYPE_FP8_E4M3) return fail(ISL_ERR_UNSUPPORTED, "an HnswGraph keeps float32 or bf16 rows, not fp8");
+  if (dtype != ISL_DTYPE_F32 && dtype != ISL_DTYPE_BF16) return fail(ISL_ERR_INVALID_ARGUMENT, "unknown row dtype");
   return ISL_OK;
 }
 
@@ -112,7 +132,19 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
                                 const uint64_t* const* layer_neighbors, const uint64_t* levels,
                                 int32_t has_entry, uint64_t entry_point, uint64_t max_level,
                                 const float* vectors, int32_t device, isl_hnsw** out) {
+  return isl_hnsw_from_layers_rows(m, m0, ef_construction, metric, num_nodes, d, num_layers, layer_offsets,
+                                   layer_neighbors, levels, has_entry, entry_point, max_level, vectors, ISL_DTYPE_F32,
+                                   device, out);
+}
+
+isl_status isl_hnsw_from_layers_rows(uint64_t m, uint64_t m0, uint64_t ef_construction, int32_t metric,
+                                     uint64_t num_nodes, uint64_t d, uint64_t num_layers,
+                                     const uint64_t* const* layer_offsets,
+                                     const uint64_t* const* layer_neighbors, const uint64_t* levels,
+                                     int32_t has_entry, uint64_t entry_point, uint64_t max_level,
+                                     const void* rows, int32_t dtype, int32_t device, isl_hnsw** out) {
   if (!out) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "out is NULL");
+  ISL_TRY(isl::hnsw_row_dtype(dtype));
   ISL_TRY(isl::hnsw_config_validate(m, m0, ef_construction, metric));
   if (num_nodes && (num_layers == 0 || max_level >= num_layers || !layer_offsets || !layer_neighbors))
     return isl::fail(ISL_ERR_INVALID_ARGUMENT, "layers do not cover max_level");
@@ -130,12 +162,14 @@ isl_status isl_hnsw_from_layers(uint64_t m, uint64_t m0, uint64_t ef_constructio
                                      num_nodes ? layer_neighbors[0] : nullptr, levels, nullptr,
                                      has_entry, entry_point, max_level, num_nodes ? 1 : 0, d, &h->core);
   if (st != ISL_OK) return bail(st);
-  h->core->is_hnsw = true;
-  if (num_nodes == 0) { *out = h; return ISL_OK; }
+  if (num_nodes == 0) { h->core->is_hnsw = true; *out = h; return ISL_OK; }
   st = isl_index_upload(h->core, device);
   if (st != ISL_OK) return bail(st);
-  st = isl_set_embeddings(h->core, vectors, num_nodes, d, ISL_DTYPE_F32, ISL_MEM_HOST);
+  // (the rows go in before the core becomes a facade's: isl_set_embeddings refuses a caller who swaps a facade's
+  // rows for another type, as Scaffold::open of the builder has it)
+  st = isl_set_embeddings(h->core, rows, num_nodes, d, dtype, ISL_MEM_HOST);
   if (st != ISL_OK) return bail(st);
+  h->core->is_hnsw = true;
   // upper layers -> device CSR (u64 offsets, u32 ids)
   isl_index* c = h->core;
   std::vector<const uint64_t*> offs(max_level + 1, nullptr);
@@ -320,6 +354,11 @@ isl_status isl_hnsw_get_vector(const isl_hnsw* h, uint64_t node, float* out) {
   if (!h || !h->core || !out) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   if (node >= h->core->num_nodes) return isl::fail_node(node);
   return read_rows(h->core, node, 1, out);
+}
+
+isl_status isl_hnsw_row_storage(const isl_hnsw* h, int32_t* dtype, uint64_t* block_bytes) {
+  if (!h || !h->core) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "hnsw handle is NULL");
+  return isl_index_row_storage(h->core, dtype, nullptr, block_bytes);
 }
 
 isl_status isl_hnsw_to_bytes(const isl_hnsw* h, uint8_t** out, size_t* len) {

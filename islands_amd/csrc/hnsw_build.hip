@@ -17,6 +17,9 @@
 // whole plan is laid out once (plan_steps, build_plan.hpp): the nodes of a step sorted by level, highest first
 // -- the nodes that have layer L are then a prefix of the step.
 // With batch = 1 and ISL_SELECT_REFERENCE this is the reference's construction, list by list.
+// Rows are f32 or bf16 bit patterns (isl_hnsw_build_rows / isl_hnsw_insert_rows): bf16 rows stay bf16 in the
+// construction graph and in the finished one, every kernel that measures takes the row type as a template parameter
+// and works on the exact f32 images, so the graph is the one built from the widened rows.
 // A graph that grows returns to this layout first: its CSR layers are written back into tables of len + n_new
 // rows (Scaffold::csr_to_table), its rows are copied beside the new ones, and the plan starts at node len.  The
 // grown graph is built beside the old one and swapped into the handle at the end.
@@ -39,9 +42,9 @@ using namespace isl_dev;
 using isl_build::BuildParams;
 
 struct DescentParams {
-  const float* emb;
-  const float* norm2;
-  uint64_t stride;
+  const void* emb;     // rows of the stored type: f32, or bf16 bit patterns (ROWT of the kernel)
+  const float* norm2;  // of the (widened) rows
+  uint64_t stride;     // in elements of that type
   uint32_t d;
   const uint32_t* const* tab;  // [top + 1] device pointers: layer tables (index 0 unused here)
   const uint32_t* const* deg;  // [top + 1] their degree arrays
@@ -57,20 +60,33 @@ struct DescentParams {
 // hnsw.rs:254-282 for one new node per wave: current = entry point, then per layer max_level .. level + 1
 // rounds in which the list of the node the round STARTED at is scanned in order and `current` moves to
 // every strictly closer id, until a round changes nothing.
-template <int METRIC_API>
+// ROWT = uint16_t: bf16 rows.  The node's own row is widened exactly into the query area (no tile in front of it;
+// norm_a is the row's norm2, the bits the d-step sum over the widened values gives) and the neighbours are measured
+// with the tile-free routine: the f32 chain over the exact images.
+template <int METRIC_API, typename ROWT = float>
 __global__ __launch_bounds__(64) void insert_descent_kernel(DescentParams p) {
   constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
+  constexpr bool BF16 = sizeof(ROWT) == 2;
   extern __shared__ __align__(16) unsigned char smem[];
   float* tile = reinterpret_cast<float*>(smem);
-  float* qs = tile + TILE_ROWS * TILE_LD;
+  float* qs = tile + (BF16 ? 0 : TILE_ROWS * TILE_LD);
+  const ROWT* emb = static_cast<const ROWT*>(p.emb);
   const uint32_t lane = threadIdx.x, b = blockIdx.x;
   if (b >= p.B) return;
   const uint32_t node = p.node_ids[b];
   const uint32_t level = p.levels[node];
-  const float q_norm = load_query<METRIC>(p.emb + (uint64_t)node * p.stride, p.d, qs);
+  float q_norm;
+  if constexpr (BF16) {
+    widen_row_query(emb + (uint64_t)node * p.stride, p.d, qs);
+    q_norm = METRIC == METRIC_COSINE_PRE ? p.norm2[node] : 0.0f;
+  } else {
+    q_norm = load_query<METRIC>(emb + (uint64_t)node * p.stride, p.d, qs);
+  }
   uint32_t cur = p.entry, cV = 1;
   const float e_aux = METRIC == METRIC_COSINE_PRE ? p.norm2[cur] : 0.0f;
-  float cd = rl_f(wave_distances<METRIC>(p.emb, p.stride, p.d, cur, 1, qs, tile, q_norm, e_aux), 0);
+  float cd;
+  if constexpr (BF16) cd = rl_f(direct_distances<METRIC, uint16_t>(emb, p.stride, p.d, cur, 1, qs, q_norm, e_aux), 0);
+  else cd = rl_f(wave_distances<METRIC>(emb, p.stride, p.d, cur, 1, qs, tile, q_norm, e_aux), 0);
   for (uint32_t layer = p.max_level; layer > level; --layer) {
     const uint32_t* tab = p.tab[layer];
     const uint32_t* deg = p.deg[layer];
@@ -84,7 +100,9 @@ __global__ __launch_bounds__(64) void insert_descent_kernel(DescentParams p) {
         const uint32_t R = dg - base < 64u ? dg - base : 64u;
         const uint32_t gid = lane < R ? row[base + lane] : cur;
         const float aux = (METRIC == METRIC_COSINE_PRE && lane < R) ? p.norm2[gid] : 0.0f;
-        const float gd = wave_distances<METRIC>(p.emb, p.stride, p.d, gid, R, qs, tile, q_norm, aux);
+        float gd;  // lane j < R: d(node, row gid(j)), by the routine that reads the stored type
+        if constexpr (BF16) gd = direct_distances<METRIC, uint16_t>(emb, p.stride, p.d, gid, R, qs, q_norm, aux);
+        else gd = wave_distances<METRIC>(emb, p.stride, p.d, gid, R, qs, tile, q_norm, aux);
         cV += R;
         for (uint32_t r = 0; r < R; ++r) {  // list order, strict `<` (hnsw.rs:271)
           const float dr = rl_f(gd, (int)r);
@@ -199,9 +217,11 @@ isl_status check_import(const char* call, const uint32_t* d_flag, const isl_hnsw
 // node, whose CSR layers return to the builder's tables; NULL: nothing, node 0 starts the graph).  One loop
 // over the plan's steps -- descent, per-layer gather, Scaffold::insert -- then compaction and
 // attach_upper_layers.  `from` is only read; the graph of all n nodes leaves in `out`, built beside it.
-isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const isl_hnsw* from, const float* vectors,
-                uint64_t n_new, uint64_t d, const std::vector<uint64_t>& levels, uint64_t top, int32_t mem,
-                int32_t device, std::unique_ptr<isl_hnsw>& out) {
+// `vectors`: the n_new rows, of `dtype` (f32 or bf16 bit patterns; the stored type of `from` where there is one), which
+// the grown graph keeps as they are.
+isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const isl_hnsw* from, const void* vectors,
+                int32_t dtype, uint64_t n_new, uint64_t d, const std::vector<uint64_t>& levels, uint64_t top,
+                int32_t mem, int32_t device, std::unique_ptr<isl_hnsw>& out) {
   using isl::fail;
   const isl_index* old = from ? from->core : nullptr;
   const uint64_t n0 = old ? old->num_nodes : 0, n = n0 + n_new;
@@ -220,7 +240,7 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
   lcfg.metric = cfg.metric;
   lcfg.prune_ratio = 0.0f;
   isl_build::Scaffold c;
-  ISL_TRY(c.open(lcfg, opts, true, vectors, ISL_DTYPE_F32, n, d, mem, device, B, m0, ef, old));
+  ISL_TRY(c.open(lcfg, opts, true, vectors, dtype, n, d, mem, device, B, m0, ef, old));
   isl_index* g = c.g;
 
   // one table per layer, and what the descent and the per-layer gathers read
@@ -265,7 +285,7 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
     return fail(ISL_ERR_DEVICE, "cannot stage the build plan");
 
   DescentParams dp{};
-  dp.emb = g->rows.f32(); dp.norm2 = g->rows.norm2(); dp.stride = g->rows.stride(); dp.d = (uint32_t)d;
+  dp.emb = g->rows.data(); dp.norm2 = g->rows.norm2(); dp.stride = g->rows.stride(); dp.d = (uint32_t)d;
   dp.tab = d_tab; dp.deg = d_deg; dp.W = m + 1; dp.levels = d_lv;
   dp.cur_of = cur_of; dp.evals_of = evals_of;
   c.p.node_levels = d_lv;
@@ -274,11 +294,17 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
   // the graph as the first step finds it: the old one's entry point and top layer, or node 0 alone -- entry
   // point, max_level = its level, every list empty (hnsw.rs:240-245)
   uint64_t entry = old ? old->entry_point : 0, max_level = old ? old->max_level : lv[0];
+  const bool bf16 = g->rows.is_bf16();
+  // (the descent over bf16 rows holds the widened query alone: what the bf16 link kernel holds)
+  const size_t descent_lds = bf16 ? isl_plan::link_lds_bf16((uint32_t)d) : isl_build::link_lds(d);
   for (const isl_plan::Step& s : steps) {
     const uint32_t* ids = d_order + s.first;
     dp.node_ids = ids; dp.B = s.count; dp.entry = (uint32_t)entry; dp.max_level = (uint32_t)max_level;
     isl::by_metric(cfg.metric, [&](auto mc) {
-      hipLaunchKernelGGL(insert_descent_kernel<decltype(mc)::value>, dim3(s.count), dim3(64), isl_build::link_lds(d), 0, dp);
+      if (bf16)
+        hipLaunchKernelGGL((insert_descent_kernel<decltype(mc)::value, uint16_t>), dim3(s.count), dim3(64), descent_lds, 0, dp);
+      else
+        hipLaunchKernelGGL(insert_descent_kernel<decltype(mc)::value>, dim3(s.count), dim3(64), descent_lds, 0, dp);
     });
     if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "descent launch failed");
     g->has_entry = true;
@@ -286,9 +312,12 @@ isl_status grow(const isl_hnsw_config& cfg, const isl_build_options& opts, const
     uint32_t cnt = 0;  // nodes of the step that have the layer: a prefix, growing as the layer falls
     for (uint64_t L = s.top + 1; L-- > 0;) {
       while (cnt < s.count && lv[order[s.first + cnt]] >= L) ++cnt;
-      hipLaunchKernelGGL(gather_layer_kernel, dim3((uint32_t)(((uint64_t)cnt * d + 255) / 256)), dim3(256), 0, 0,
-                         g->rows.f32(), g->rows.stride(), (uint32_t)d, ids, cnt, cur_of, evals_of, c.qbuf, g->build_q_entry,
-                         g->build_q_evals);
+      if (bf16)  // the widened rows, through the flat builder's gather
+        c.gather_bf16(0, cnt, ids, cur_of, evals_of);
+      else
+        hipLaunchKernelGGL(gather_layer_kernel, dim3((uint32_t)(((uint64_t)cnt * d + 255) / 256)), dim3(256), 0, 0,
+                           g->rows.f32(), g->rows.stride(), (uint32_t)d, ids, cnt, cur_of, evals_of, c.qbuf,
+                           g->build_q_entry, g->build_q_evals);
       if (hipGetLastError() != hipSuccess) return fail(ISL_ERR_DEVICE, "gather launch failed");
       ISL_TRY(c.insert(tab[L], cnt, s.count > 1, 0, ids, (uint32_t)L));
     }
@@ -342,7 +371,7 @@ isl_status check_entry_and_levels(const char* call, const isl_index* core) {
 // The graph of `from` without the nodes `remap` marks kGone (include/islands_amd.h, isl_hnsw_remove), every layer
 // in one pass of the removal routine (isl_build::shrink_import / shrink_finish): layer 0 is the core index's CSR,
 // the layers above are the descent's arrays, and the levels say which node has which layer.  `from` (non-empty,
-// resident f32 rows, levels that match its layers, at least one survivor) is only read; the shrunk graph leaves in
+// resident f32 or bf16 rows, levels that match its layers, at least one survivor) is only read; the shrunk graph leaves in
 // `out`, built beside it.
 isl_status shrink(const isl_build_options& opts, const isl_hnsw* from, const std::vector<uint32_t>& remap,
                   const std::vector<uint32_t>& survivors, std::unique_ptr<isl_hnsw>& out) {
@@ -440,10 +469,17 @@ isl_status isl_hnsw_random_levels(uint64_t seed, uint64_t n, double ml, uint64_t
 isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options* opts_in, const float* vectors,
                           uint64_t n, uint64_t d, const uint64_t* levels_in, uint64_t level_seed, int32_t mem,
                           int32_t device, isl_hnsw** out) {
+  return isl_hnsw_build_rows(cfg_in, opts_in, vectors, ISL_DTYPE_F32, n, d, levels_in, level_seed, mem, device, out);
+}
+
+isl_status isl_hnsw_build_rows(const isl_hnsw_config* cfg_in, const isl_build_options* opts_in, const void* vectors,
+                               int32_t dtype, uint64_t n, uint64_t d, const uint64_t* levels_in, uint64_t level_seed,
+                               int32_t mem, int32_t device, isl_hnsw** out) {
   using isl::fail;
   if (!out || (!vectors && n)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
   ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
+  ISL_TRY(isl::hnsw_row_dtype(dtype));
   isl_hnsw_config cfg;
   if (cfg_in) cfg = *cfg_in;
   else isl_hnsw_config_default(&cfg);
@@ -460,7 +496,7 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options
   uint64_t top = 0;
   ISL_TRY(all_levels(nullptr, cfg, n, levels_in, level_seed, levels, top));
   std::unique_ptr<isl_hnsw> h;
-  ISL_TRY(grow(cfg, opts, nullptr, vectors, n, d, levels, top, mem, device, h));  // insert into nothing
+  ISL_TRY(grow(cfg, opts, nullptr, vectors, dtype, n, d, levels, top, mem, device, h));  // insert into nothing
   *out = h.release();
   return ISL_OK;
 }
@@ -468,10 +504,17 @@ isl_status isl_hnsw_build(const isl_hnsw_config* cfg_in, const isl_build_options
 isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const float* vectors, uint64_t n_new,
                            uint64_t d, const uint64_t* levels_in, uint64_t level_seed, int32_t mem,
                            uint64_t* first_id) {
+  return isl_hnsw_insert_rows(h, opts_in, vectors, ISL_DTYPE_F32, n_new, d, levels_in, level_seed, mem, first_id);
+}
+
+isl_status isl_hnsw_insert_rows(isl_hnsw* h, const isl_build_options* opts_in, const void* vectors, int32_t dtype,
+                                uint64_t n_new, uint64_t d, const uint64_t* levels_in, uint64_t level_seed,
+                                int32_t mem, uint64_t* first_id) {
   using isl::fail;
   if (!h || !h->core || (!vectors && n_new)) return fail(ISL_ERR_INVALID_ARGUMENT, "NULL argument");
   isl_build_options opts;
   ISL_TRY(isl_build::resolve_build_options(opts_in, true, opts));
+  ISL_TRY(isl::hnsw_row_dtype(dtype));
   const isl_index* core = h->core;
   const uint64_t n0 = core->num_nodes;
   if (n_new == 0) {
@@ -487,9 +530,12 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const 
   uint64_t top = 0;
   ISL_TRY(all_levels(n0 ? core : nullptr, cfg, n0 + n_new, levels_in, level_seed, levels, top));
   if (n0) {
-    if (core->recompute || !core->rows.f32() || !core->rows.norm2() || core->nvec != n0 || core->rows.d() != d ||
-        core->device < 0)
-      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert needs the graph's float32 rows resident on the device");
+    if (core->recompute || !(core->rows.f32() || core->rows.bf16()) || !core->rows.norm2() || core->nvec != n0 ||
+        core->rows.d() != d || core->device < 0)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert needs the graph's float32 or bf16 rows resident on the device");
+    if (core->rows.dtype() != dtype)  // isl_index_insert's rule
+      return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: the graph stores %s rows and takes no other type",
+                  core->rows.is_bf16() ? "bf16" : "float32");
     ISL_TRY(check_entry_and_levels("isl_hnsw_insert", core));
     if (core->max_degree > h->m0)
       return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_insert: a layer-0 list of %u ids is longer than m0 = %llu",
@@ -505,7 +551,7 @@ isl_status isl_hnsw_insert(isl_hnsw* h, const isl_build_options* opts_in, const 
       return fail(ISL_ERR_SEARCH, "Search error: the graph cannot grow while searches are in flight");
   }
   std::unique_ptr<isl_hnsw> grown;
-  ISL_TRY(grow(cfg, opts, n0 ? h : nullptr, vectors, n_new, d, levels, top, mem, n0 ? core->device : h->device,
+  ISL_TRY(grow(cfg, opts, n0 ? h : nullptr, vectors, dtype, n_new, d, levels, top, mem, n0 ? core->device : h->device,
                grown));
   ISL_TRY(install_core(h, grown.get(), d, grown->core->device, "grow"));
   if (first_id) *first_id = n0;
@@ -528,9 +574,9 @@ isl_status isl_hnsw_remove(isl_hnsw* h, const isl_build_options* opts_in, const 
   uint64_t bad = 0;
   if (isl_plan::first_unknown_id(ids, n_ids, n0, &bad)) return isl::fail_node(bad);
   // (an id below len exists: the graph is not empty)
-  if (core->recompute || !core->rows.f32() || !core->rows.norm2() || core->rows.n() != n0 || core->nvec != n0 ||
-      core->device < 0 || !core->d_off)
-    return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove needs the graph's float32 rows resident on the device");
+  if (core->recompute || !(core->rows.f32() || core->rows.bf16()) || !core->rows.norm2() || core->rows.n() != n0 ||
+      core->nvec != n0 || core->device < 0 || !core->d_off)
+    return fail(ISL_ERR_UNSUPPORTED, "isl_hnsw_remove needs the graph's float32 or bf16 rows resident on the device");
   ISL_TRY(check_entry_and_levels("isl_hnsw_remove", core));
   if (h->m0 > isl_plan::kMaxM0 || h->m > isl_plan::kMaxM0)
     return fail(ISL_ERR_UNSUPPORTED, "%s", isl_plan::shape_limit(isl_plan::kMaxM0 + 1, 0, 0));

@@ -468,7 +468,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
     p.q_entry = ws.q_entry;
     p.q_evals = ws.q_entry + nq;
     const uint32_t dgrid = (uint32_t)std::min<uint64_t>(nq_grid, 8192);
-    isl_launch::launch_descent(metric, dgrid, cg.descent_lds, st, &p);
+    isl_launch::launch_descent(metric, idx->rows.is_bf16(), dgrid, cg.descent_lds, st, &p);
     ISL_HIP(hipGetLastError());
   }
   if (seeded) {

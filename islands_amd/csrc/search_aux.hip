@@ -37,14 +37,20 @@ void isl_launch::launch_two_level(int metric, bool bf16, bool resume, bool qh, u
   else launch_two_level_t<float, false, false>(metric, grid, lds, st, p);
 }
 
-void isl_launch::launch_descent(int metric, uint32_t grid, size_t lds, hipStream_t st, const void* params) {
-  const SearchParams& p = *static_cast<const SearchParams*>(params);
+template <typename ROWT>
+static void launch_descent_t(int metric, uint32_t grid, size_t lds, hipStream_t st, const SearchParams& p) {
   switch (metric) {
-    case ISL_METRIC_COSINE: launch_one(hnsw_descent_kernel<ISL_METRIC_COSINE>, grid, lds, st, p); break;
-    case ISL_METRIC_EUCLIDEAN: launch_one(hnsw_descent_kernel<ISL_METRIC_EUCLIDEAN>, grid, lds, st, p); break;
-    case ISL_METRIC_DOT: launch_one(hnsw_descent_kernel<ISL_METRIC_DOT>, grid, lds, st, p); break;
-    default: launch_one(hnsw_descent_kernel<ISL_METRIC_MANHATTAN>, grid, lds, st, p); break;
+    case ISL_METRIC_COSINE: launch_one(hnsw_descent_kernel<ISL_METRIC_COSINE, ROWT>, grid, lds, st, p); break;
+    case ISL_METRIC_EUCLIDEAN: launch_one(hnsw_descent_kernel<ISL_METRIC_EUCLIDEAN, ROWT>, grid, lds, st, p); break;
+    case ISL_METRIC_DOT: launch_one(hnsw_descent_kernel<ISL_METRIC_DOT, ROWT>, grid, lds, st, p); break;
+    default: launch_one(hnsw_descent_kernel<ISL_METRIC_MANHATTAN, ROWT>, grid, lds, st, p); break;
   }
+}
+
+void isl_launch::launch_descent(int metric, bool bf16, uint32_t grid, size_t lds, hipStream_t st, const void* params) {
+  const SearchParams& p = *static_cast<const SearchParams*>(params);
+  if (bf16) launch_descent_t<uint16_t>(metric, grid, lds, st, p);
+  else launch_descent_t<float>(metric, grid, lds, st, p);
 }
 
 void isl_launch::launch_classify(uint32_t grid, hipStream_t st, const void* params) {

@@ -89,7 +89,11 @@ inline size_t exact_lds(uint32_t ef, uint32_t d) {
          (size_t)((d + 3) / 4 * 4) * 4;
 }
 // the greedy descent through an HnswGraph's upper layers holds the query alone
-inline size_t descent_lds(uint32_t d) { return (size_t)((d + 3) / 4 * 4) * 4 + 64; }
+// (bf16 rows: their distance routine walks the query in steps of 32 elements and fetches the operand of a step
+// whole, the last one included -- d rounded up to whole steps, as build_plan.hpp's query_floats_bf16)
+inline size_t descent_lds(uint32_t d, bool bf16_rows = false) {
+  return (size_t)(bf16_rows ? (d + 31) / 32 * 32 : (d + 3) / 4 * 4) * 4 + 64;
+}
 
 // Two-level search: LDS of one wave = visited table + approximate-queue window + R + staging + query
 struct TwoLevelCall {
@@ -180,7 +184,7 @@ inline isl_status call_geometry(const isl_index* idx, uint64_t d, uint64_t k, ui
                      : isl_launch::fast_state_words(g.segments, g.fg.hbits);
   g.plog_cap = push_log_cap(ef);
   g.exact_lds = exact_lds(ef, (uint32_t)d);
-  g.descent_lds = descent_lds((uint32_t)d);
+  g.descent_lds = descent_lds((uint32_t)d, idx->is_hnsw && idx->rows.is_bf16());  // (an HnswGraph alone descends)
   return ISL_OK;
 }
 

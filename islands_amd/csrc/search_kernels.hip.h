@@ -433,12 +433,14 @@ __device__ void replay_result_order(const uint2* plog, uint32_t npush, uint32_t 
 // the neighbours of the node the round started at are scanned in order and `current` moves to
 // every strictly closer one.  One wave per query; leaves the layer-0 entry in q_entry (a missing
 // node id is reported through status / payload like everywhere else).
-template <int METRIC_API>
+// ROWT = float, or uint16_t for a graph whose rows are bf16 bit patterns: the query stays f32 in LDS and the rows
+// are widened as they are measured (norm2 is of the widened values).
+template <int METRIC_API, typename ROWT = float>
 __global__ __launch_bounds__(64) void hnsw_descent_kernel(SearchParams p) {
   constexpr int METRIC = METRIC_API == ISL_METRIC_COSINE ? METRIC_COSINE_PRE : METRIC_API;
   extern __shared__ __align__(16) unsigned char smem[];
   float* qs = reinterpret_cast<float*>(smem);
-  const float* emb = reinterpret_cast<const float*>(p.emb);
+  const ROWT* emb = reinterpret_cast<const ROWT*>(p.emb);
   const int lane = threadIdx.x;
   for (uint32_t qi = blockIdx.x; qi < p.nq; qi += gridDim.x) {
     __syncthreads();
@@ -452,7 +454,7 @@ __global__ __launch_bounds__(64) void hnsw_descent_kernel(SearchParams p) {
       payload = entry;
     } else {
       float e_aux = METRIC == METRIC_COSINE_PRE ? p.norm2[entry] : 0.0f;
-      ed = rl_f(direct_distances<METRIC>(emb, p.stride, p.d, entry, 1, qs, q_norm, e_aux), 0);
+      ed = rl_f(direct_distances<METRIC, ROWT>(emb, p.stride, p.d, entry, 1, qs, q_norm, e_aux), 0);
       for (uint32_t layer = p.max_level; layer >= 1 && status == QS_OK; --layer) {
         const uint64_t* loff = p.layer_off[layer];
         const uint32_t* ladj = p.layer_adj[layer];
@@ -472,7 +474,7 @@ __global__ __launch_bounds__(64) void hnsw_descent_kernel(SearchParams p) {
               break;
             }
             const float g_aux = (METRIC == METRIC_COSINE_PRE && (uint32_t)lane < R) ? p.norm2[gid] : 0.0f;
-            const float gd = direct_distances<METRIC>(emb, p.stride, p.d, gid, R, qs, q_norm, g_aux);
+            const float gd = direct_distances<METRIC, ROWT>(emb, p.stride, p.d, gid, R, qs, q_norm, g_aux);
             cV += R;
             for (uint32_t r = 0; r < R; ++r) {  // list order, strict `<` (hnsw.rs:485)
               const float dr = rl_f(gd, (int)r);
@@ -1902,6 +1904,7 @@ void launch_exact(int metric, bool hnsw, uint32_t grid, size_t lds, hipStream_t 
 // resume = the RESUME instantiation (recompute provider, f32 rows); qh = bf16 rows, query held as bf16 in LDS
 void launch_two_level(int metric, bool bf16, bool resume, bool qh, uint32_t grid, size_t lds, hipStream_t st, const void* params);
 inline uint32_t tl_state_words(uint32_t ef, uint32_t wcap, uint32_t hbits) { return tl_state_words_of(ef, wcap, hbits); }
-void launch_descent(int metric, uint32_t grid, size_t lds, hipStream_t st, const void* params);
+// bf16 = the graph's rows are bf16 bit patterns (idx->rows.dtype())
+void launch_descent(int metric, bool bf16, uint32_t grid, size_t lds, hipStream_t st, const void* params);
 void launch_classify(uint32_t grid, hipStream_t st, const void* params);
 }  // namespace isl_launch
