@@ -5,138 +5,17 @@ isl_search_batch_device and to the CPU oracle.
 
 ISL_GROUP_ROOM=1 makes "the chip is full" hold as soon as one query is in flight, and a first call of two queries
 ordered behind a few milliseconds of matrix products on the caller's stream keeps it so while the others arrive."""
-import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import islands_amd as ia
 from islands_amd import _ffi
-from _data import clustered_vectors, knn_graph
-from test_gpu_parity import bits, make_index
+from _group_case import EF, K, SIZES, Case, counters, switches
+from test_gpu_parity import make_index
 
 pytestmark = pytest.mark.gpu
-
-N, DEG, EF, K = 4000, 16, 32, 5
-SIZES = [1, 3, 17, 40, 64, 64]
-TIED = [False, True, False, True, False, True]  # which calls ask near the duplicated rows
-COUNTERS = ["queries", "expansions", "edges", "evals", "pushes", "exact_path", "replayed", "encoded_nodes",
-            "recompute_rounds"]
-
-
-@contextlib.contextmanager
-def switches(**env):
-    """The group switches are read when an index handle is created."""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update({k: str(v) for k, v in env.items()})
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
-def counters(idx):
-    a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-    assert _ffi.lib().isl_index_group_counters(idx._h, C.byref(a), C.byref(b), C.byref(c)) == 0
-    return int(a.value), int(b.value), int(c.value)
-
-
-class Case:
-    """Rows: half of them continuous, the other half quantised to a grid of 1/8 and every one of those stored
-    twice (equal distances wherever a query comes near them), in clusters of their own.  One query block per call."""
-
-    def __init__(self, orc, d):
-        import torch
-
-        self.torch, self.orc, self.d = torch, orc, d
-        half, quarter = N // 2, N // 4
-        a = clustered_vectors(half, d, 7 + d)
-        b = np.round(clustered_vectors(quarter, d, 11 + d) * 8) / 8
-        b[np.abs(b).sum(1) == 0, 0] = 0.125
-        self.v = np.concatenate([a, b, b]).astype(np.float32)
-        off, nb = knn_graph(self.v, DEG, seed=3)
-        self.csr = orc.Csr(off, nb, entry_point=0)
-        rng = np.random.default_rng(100 + d)
-        self.q = []
-        for nq, tied in zip(SIZES, TIED):
-            rows = rng.integers(half, N, nq) if tied else rng.integers(0, half, nq)
-            self.q.append((self.v[rows] + 0.05 * rng.standard_normal((nq, d))).astype(np.float32))
-        self.extra = (self.v[:2] + 0.05 * rng.standard_normal((2, d))).astype(np.float32)  # the call that fills the chip
-        self.busy = torch.randn(4096, 4096, device="cuda")
-        (self.busy @ self.busy).sum().item()  # (the first product loads its library: not inside a test's sequence)
-        self.alone = {}  # (call, k, ef) -> (ids, distance bits, counts, counters), made once, never changed
-        with switches(ISL_NO_GROUP=1):
-            self.ref_idx = make_index(self.csr, self.v)
-        # everything a test's sequence of calls reads is on the device beforehand: a copy from the host inside the
-        # sequence would wait for the card, and with it for the matrix products that keep the first call in flight
-        self.dq = [self.dev(q) for q in self.q]
-        self.dextra, self.extra_out = self.dev(self.extra), self.outputs(2, K)
-
-    def dev(self, q):
-        return self.torch.from_numpy(np.ascontiguousarray(q)).cuda()
-
-    def outputs(self, nq, k):
-        t = self.torch
-        return (t.full((nq, max(k, 1)), -1, dtype=t.int64, device="cuda"),
-                t.full((nq, max(k, 1)), -1.0, dtype=t.float32, device="cuda"), t.full((nq,), -1, dtype=t.int32, device="cuda"))
-
-    def answer_alone(self, call, k=K, ef=EF):
-        """The call made by itself through isl_search_batch_device, checked against the oracle."""
-        key = (call, k, ef)
-        if key not in self.alone:
-            q = self.q[call]
-            dq, (ids, dist, cnt) = self.dev(q), self.outputs(len(q), k)
-            self.ref_idx.search_batch_device(dq.data_ptr(), len(q), self.d, k, ef, ids.data_ptr(), dist.data_ptr(), cnt.data_ptr())
-            st = self.ref_idx.last_stats()
-            ids, dist, cnt = ids.cpu().numpy(), dist.cpu().numpy(), cnt.cpu().numpy()
-            for i in range(len(q)):
-                r = self.orc.leann_search(self.csr, self.v, q[i], k, ef)
-                m = int(cnt[i])
-                assert ids[i, :m].tolist() == r.ids.tolist(), (call, i)
-                assert bits(dist[i, :m]).tolist() == bits(r.dist).tolist(), (call, i)
-            self.alone[key] = (ids, bits(dist), cnt, {f: st[f] for f in COUNTERS})
-        return self.alone[key]
-
-    def fill_the_chip(self, idx, stream):
-        """A call of two queries behind some 50 ms of matrix products on `stream`: in flight until they are done."""
-        t = self.torch
-        with t.cuda.stream(stream):
-            x = self.busy
-            for _ in range(64):
-                x = (x @ self.busy) * 1e-2
-        dq, o = self.dextra, self.extra_out
-        tok = idx.search_batch_device_async(dq.data_ptr(), 2, self.d, K, EF, o[0].data_ptr(), o[1].data_ptr(), o[2].data_ptr(),
-                                            stream=stream.cuda_stream)
-        return tok, x
-
-    def buffers(self, shapes):
-        """Output buffers for calls [(call, k)], made (and the card idle) before the sequence starts."""
-        outs = [self.outputs(len(self.q[c]), k) for c, k in shapes]
-        self.torch.cuda.synchronize()
-        return outs
-
-    def submit(self, idx, call, o, k=K, ef=EF):
-        dq = self.dq[call]
-        tok = idx.search_batch_device_async(dq.data_ptr(), len(self.q[call]), self.d, k, ef, o[0].data_ptr(), o[1].data_ptr(),
-                                            o[2].data_ptr())
-        return tok, dq, o
-
-    def check(self, call, o, st, k=K, ef=EF):
-        ids, dist, cnt = (x.cpu().numpy() for x in o)
-        r_ids, r_bits, r_cnt, r_st = self.answer_alone(call, k, ef)
-        assert cnt.tolist() == r_cnt.tolist(), call
-        for i in range(len(cnt)):
-            m = int(cnt[i])
-            assert ids[i, :m].tolist() == r_ids[i, :m].tolist(), (call, i)
-            assert bits(dist[i, :m]).tolist() == r_bits[i, :m].tolist(), (call, i)
-        if st is not None:
-            assert {f: st[f] for f in COUNTERS} == r_st, (call, st, r_st)
 
 
 @pytest.fixture(scope="module", params=[32, 50])
