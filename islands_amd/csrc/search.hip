@@ -22,8 +22,7 @@
 //   * exact kernel: emulates Rust's BinaryHeap push/pop/into_iter byte for byte (candidates in
 //     HBM scratch, results in LDS) for those queries, for ef > 512, for adjacency rows longer
 //     than 64 and for NaN / -0.0 distances.
-#include "search_geometry.hpp"
-#include "search_internal.hpp"
+#include "search_launch_plan.hpp"
 
 #include <cmath>
 
@@ -267,45 +266,39 @@ void launch_fast(const isl_launch::FastKernel& k, uint32_t grid, size_t lds, hip
   }
 }
 
-// Enqueues the kernels of one search on a claimed lane.
-// warm = true: the same launches over zero queries (isl_index_prepare: loads the code objects and
-// brings the lane's stream up) -- nothing is read or written beyond the ticket words.
-isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c,
-                               const RoundPlan& plan, bool warm) {
-  const uint64_t nq = c.nq, d = c.d, k = c.k;
-  if (nq > 0x7FFFFFFFull) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "too many queries");
-  const TwoLevelCall tl_call{c.ratio, plan.window_scale};
-  const TwoLevelCall* tl = c.two_level ? &tl_call : nullptr;
-  CallGeometry cg;
-  ISL_TRY(call_geometry(idx, d, k, c.ef, tl, cg));
-  const uint32_t ef = cg.ef;
-  const bool use_fast = cg.use_fast;
-  // searches over the recompute provider park and resume on the fast kernel (f32 rows; the
-  // two-level and heap-exact kernels re-run a blocked query from its start instead)
-  const bool resume = !warm && (plan.active != 0 || plan.exact != 0);
-  // two-level search over bf16 rows: first the instantiation that keeps a bf16-valued query as bf16
-  // in LDS, then the float32-query one over the queries it passed on (not in a retry's list mode)
-  const bool tl_qh = tl && !warm && !resume && idx->rows.is_bf16() && plan.retry == 0 && cg.tl_hbits_q == cg.fg.hbits;
-  const bool qh = cg.qh && !resume;  // (the fast kernel's bf16-query instantiation in front)
-  // per-slot state is indexed by blockIdx.x < min(nq, slots) -- by the query when it can come back on
-  // another wave
-  if (!warm)
-    ISL_TRY(prepare_workspace(idx, ws, (uint32_t)nq,
-                              (uint32_t)(idx->recompute ? nq : std::min<uint64_t>(nq, cg.lane_slots)), cg.plog_cap));
-  if (!idx->pool.slots || ((use_fast || (tl && idx->max_degree <= 128)) && !idx->d_ell && idx->d_off && idx->num_nodes)) {
-    // not prepared (isl_index_prepare / isl_index_upload do this ahead of time)
-    std::lock_guard<std::mutex> lock(idx->mu);
-    ISL_TRY(ensure_pool(idx, ws));
-    const uint32_t* before = idx->d_ell;
-    ISL_TRY(isl::ensure_padded_adjacency(const_cast<isl_index*>(idx)));
-    if (idx->d_ell != before) ws.alloc_events += 2;
-  }
-  hipStream_t st = call_stream(ws, c);
-  if (c.mode == StreamMode::OWN_AFTER_USER || c.mode == StreamMode::OWN_AFTER_EVENT) {
-    if (c.mode == StreamMode::OWN_AFTER_USER) ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));
-    ISL_HIP(hipStreamWaitEvent(ws.stream, ws.ev_in, 0));
-  }
+// the two environment switches of the measurement aids, read once; the enqueue and the finish share them
+bool debug_on() {
+  static const bool on = getenv("ISL_DEBUG") != nullptr;
+  return on;
+}
+// ISL_TIMELINE=<file>: start / end tick of every query of every call, appended at wait time
+// (measurement aid: where a run's fill and drain go; tools/timeline.py reads the file)
+const char* timeline_path() {
+  static const char* const path = getenv("ISL_TIMELINE");
+  return path;
+}
 
+// what plan_launches reads from the index (an index without its scratch pool gets the slots ensure_pool
+// gives it ahead of the launches)
+LaunchFacts launch_facts(const isl_index* idx) {
+  LaunchFacts f;
+  f.dtype = idx->rows.dtype();
+  f.metric = (int)idx->cfg.metric;
+  f.is_hnsw = idx->is_hnsw;
+  f.max_level = (uint32_t)idx->max_level;
+  f.recompute = idx->recompute;
+  f.max_degree = idx->max_degree;
+  f.seeds = idx->seeds.count() != 0;
+  f.build_q_entry = idx->build_q_entry != nullptr;
+  f.pool_slots = idx->pool.slots ? idx->pool.slots : kExactSlots;
+  return f;
+}
+
+// The SearchParams of a call, every field assigned once; the lane's buffers are reserved by now.  What a
+// single launch is told differently (nq, hbits, hcap, qsel_mode) is its step's (search_launch_plan.hpp).
+SearchParams fill_params(const isl_index* idx, const isl::SearchWorkspace& ws, const SearchCall& c,
+                         const CallGeometry& cg, const LaunchPlan& lp) {
+  const uint64_t nq = c.nq, d = c.d, k = c.k;
   SearchParams p{};
   p.off = idx->d_off;
   p.adj = idx->d_ell ? idx->d_ell : idx->d_adj;
@@ -320,9 +313,9 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.stride = idx->rows.stride();
   p.d = (uint32_t)d;
   p.queries = c.queries;
-  p.nq = warm ? 0u : (uint32_t)nq;
+  p.nq = lp.nq;
   p.k = (uint32_t)k;
-  p.ef = ef;
+  p.ef = cg.ef;
   p.prune_ratio = idx->cfg.prune_ratio;
   p.prune_strategy = idx->cfg.pruning_strategy;
   p.entry = (uint32_t)std::min<uint64_t>(idx->entry_point, 0x7FFFFFF0ull);
@@ -334,21 +327,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.ctr = ws.ctr;
   p.ticket = ws.ticket;
   p.redo = ws.redo;
-  ws.d_prof.reset();
-  static const bool debug_env = getenv("ISL_DEBUG") != nullptr;
-  if (debug_env && !warm) {
-    ISL_TRY(ws.d_prof.reserve(nq * 8));
-    ISL_HIP(hipMemset(ws.d_prof, 0, nq * 64));
-  }
   p.prof = ws.d_prof;
-  // ISL_TIMELINE=<file>: start / end tick of every query of every call, appended at wait time
-  // (measurement aid: where a run's fill and drain go; tools/timeline.py reads the file)
-  static const char* tline_env = getenv("ISL_TIMELINE");
-  ws.d_tline.reset();
-  if (tline_env && !warm) {
-    ISL_TRY(ws.d_tline.reserve(nq * 2));
-    ISL_HIP(hipMemset(ws.d_tline, 0, nq * 16));
-  }
   p.tline = ws.d_tline;
   p.replay = ws.replay;
   p.plog = reinterpret_cast<uint2*>(ws.plog.get());
@@ -366,7 +345,7 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.ulist_cap = idx->pool.ulist_cap;
   p.pool_locks = idx->pool.locks;
   p.pool_slots = idx->pool.slots;
-  if (resume && !tl && plan.exact_parks) {  // the heap-exact kernel parks and resumes too (recompute provider, bounded cache)
+  if (lp.exact_park_fields) {  // the heap-exact kernel parks and resumes too (recompute provider, bounded cache)
     p.xslot = ws.xslot;
     p.xstate = idx->pool.xstate;
     p.xstate_words = idx->pool.xstate_words;
@@ -374,152 +353,146 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   p.slot_of = idx->recompute ? idx->d_slot_of : nullptr;
   p.stamp = idx->d_stamp;
   p.round_no = idx->round_no;
-  if (resume) {
+  if (lp.resume) {
     p.qstate = ws.qstate;
     p.qstate_words = cg.state_words;
     p.qflag = ws.qflag;
-    p.qlist = plan.listed ? ws.qlist : nullptr;
-  } else if (tl && plan.retry) {
-    p.qlist = ws.qlist;  // the queries whose queue window was too small, alone, with a larger one
   }
+  // (a listed round's queries, or a retry's: those whose queue window was too small, alone, with a larger one)
+  p.qlist = lp.qlist != QlistUse::None ? ws.qlist.get() : nullptr;
   p.miss = ws.miss;
   p.miss_cap = (uint32_t)std::min<uint64_t>(ws.miss_cap, 0xFFFFFFFFull);
   p.pref = ws.miss ? ws.miss + ws.miss_cap : nullptr;
   p.pref_cap = (uint32_t)ws.pref_cap;
-  p.tl_prefetch = (tl && resume && ws.pref_cap) ? plan.prefetch : 0u;
+  p.tl_prefetch = ws.pref_cap ? lp.tl_prefetch : 0u;
   p.layer_off = idx->d_layer_off;
   p.layer_adj = idx->d_layer_adj;
-  p.max_level = idx->is_hnsw ? (uint32_t)idx->max_level : 0u;
+  p.max_level = lp.max_level;
   p.hnsw_order = idx->is_hnsw ? 1u : 0u;
-  p.q_entry = nullptr;
-  p.q_evals = nullptr;
-  if (idx->build_q_entry && !warm) {
-    // construction search of the HnswGraph builder: per-query entry nodes on the layer in d_ell, no descent
+  if (lp.construction) {
+    // construction search of the HnswGraph builder: per-query entry nodes on the layer in d_ell
     p.q_entry = idx->build_q_entry;
     p.q_evals = idx->build_q_evals;
-    p.entry_given = 1u;
-    p.max_level = 0u;
-    ISL_HIP(hipMemsetAsync(ws.status, 0, nq * 4, st));  // QS_OK: the fast kernel reads it where q_entry is set
-  }
-  // entry seeds: a plain search over resident rows starts every query at the seed nearest to it (the pick is
-  // launched below, ahead of the traversal); two-level searches and the recompute provider keep entry_point
-  const bool seeded = idx->seeds.count() != 0 && !tl && !idx->recompute && !idx->is_hnsw && !idx->build_q_entry &&
-                      !warm && !resume && nq != 0;
-  if (seeded) {
-    ISL_TRY(ws.q_entry.reserve(nq * 4, &ws.alloc_events));
+  } else if (lp.q_entry_words) {  // the seed pick's or the descent's, a launch ahead of the traversal
     p.q_entry = ws.q_entry;
     p.q_evals = ws.q_entry + nq;
-    p.entry_given = 1u;
-    p.max_level = 0u;
   }
-  if (tl) {
-    const isl_pq* pq = idx->pq;
-    const uint64_t want = std::max<uint64_t>(nq, 1) * pq->m * pq->K;
-    ISL_TRY(ws.tl_tables.reserve(want, &ws.alloc_events));
+  p.entry_given = lp.entry_given ? 1u : 0u;
+  if (lp.qsel) {
+    p.qsel = ws.qsel;
+    p.qsel_h = ws.qsel_h;
+  }
+  if (lp.two_level) {
     p.tl_tables = ws.tl_tables;
     p.tl_codes = idx->d_codes;
     p.tl_ncodes = idx->ncodes;
-    p.tl_m = (uint32_t)pq->m;
-    p.tl_K = (uint32_t)pq->K;
-    p.tl_ratio = tl->ratio;
+    p.tl_m = (uint32_t)idx->pq->m;
+    p.tl_K = (uint32_t)idx->pq->K;
+    p.tl_ratio = c.ratio;
     p.tl_wcap = cg.tl_wcap;
   }
-  const uint64_t nq_grid = warm ? 1 : nq;  // a warm launch needs one workgroup to exist
-  const int metric = (int)idx->cfg.metric;
+  return p;
+}
 
+// Enqueues the kernels of one search on a claimed lane: geometry, plan, the lane's buffers, the
+// parameters, then the plan's steps in order.
+// warm = true: the same launches over zero queries (isl_index_prepare: loads the code objects and
+// brings the lane's stream up) -- nothing is read or written beyond the ticket words.
+isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, const SearchCall& c,
+                               const RoundPlan& plan, bool warm) {
+  const uint64_t nq = c.nq, k = c.k;
+  if (nq > 0x7FFFFFFFull) return isl::fail(ISL_ERR_INVALID_ARGUMENT, "too many queries");
+  const TwoLevelCall tl_call{c.ratio, plan.window_scale};
+  CallGeometry cg;
+  ISL_TRY(call_geometry(idx, c.d, k, c.ef, c.two_level ? &tl_call : nullptr, cg));
+  const LaunchPlan lp = plan_launches(launch_facts(idx), CallShape{nq, c.two_level}, plan, warm, cg);
+  if (lp.prepare_lane) ISL_TRY(prepare_workspace(idx, ws, (uint32_t)nq, lp.lane_slots, cg.plog_cap));
+  if (!idx->pool.slots || (lp.wants_ell && !idx->d_ell && idx->d_off && idx->num_nodes)) {
+    // not prepared (isl_index_prepare / isl_index_upload do this ahead of time)
+    std::lock_guard<std::mutex> lock(idx->mu);
+    ISL_TRY(ensure_pool(idx, ws));
+    const uint32_t* before = idx->d_ell;
+    ISL_TRY(isl::ensure_padded_adjacency(const_cast<isl_index*>(idx)));
+    if (idx->d_ell != before) ws.alloc_events += 2;
+  }
+  hipStream_t st = call_stream(ws, c);
+  if (c.mode == StreamMode::OWN_AFTER_USER || c.mode == StreamMode::OWN_AFTER_EVENT) {
+    if (c.mode == StreamMode::OWN_AFTER_USER) ISL_HIP(hipEventRecord(ws.ev_in, c.user_stream));
+    ISL_HIP(hipStreamWaitEvent(ws.stream, ws.ev_in, 0));
+  }
+
+  ws.d_prof.reset();
+  if (debug_on() && lp.measures) {
+    ISL_TRY(ws.d_prof.reserve(nq * 8));
+    ISL_HIP(hipMemset(ws.d_prof, 0, nq * 64));
+  }
+  ws.d_tline.reset();
+  if (timeline_path() && lp.measures) {
+    ISL_TRY(ws.d_tline.reserve(nq * 2));
+    ISL_HIP(hipMemset(ws.d_tline, 0, nq * 16));
+  }
+  if (lp.q_entry_words) ISL_TRY(ws.q_entry.reserve(lp.q_entry_words, &ws.alloc_events));
+  if (lp.two_level)
+    ISL_TRY(ws.tl_tables.reserve(std::max<uint64_t>(nq, 1) * idx->pq->m * idx->pq->K, &ws.alloc_events));
+  const SearchParams p = fill_params(idx, ws, c, cg, lp);
+
+  // (QS_OK: the fast kernel reads status where q_entry is set)
+  if (lp.construction) ISL_HIP(hipMemsetAsync(ws.status, 0, nq * 4, st));
   // the work-queue heads are zero at this point: the publish kernel of the lane's previous call
   // left them so; only a lane's first call (or one after a failed enqueue) clears them itself
   if (!ws.ticket_clean) ISL_HIP(hipMemsetAsync(ws.ticket, 0, 64, st));
   ws.ticket_clean = false;
   ISL_HIP(hipEventRecord(ws.ev0, st));
   ws.launch_ms_read = false;
-  if (resume && !tl && plan.exact) {
-    hipLaunchKernelGGL(seed_redo_kernel, dim3(1), dim3(256), 0, st, ws.h_xlist, plan.exact, ws.redo, ws.ticket);
-    ISL_HIP(hipGetLastError());
-  }
-  if (tl) {
-    // build_distance_tables for the whole batch (pq.rs:307-338; once per call: the rounds of the
-    // recompute provider and a retry keep them), then one wave per query
-    if (!warm && !plan.tables_built) ISL_TRY(isl::pq_launch_tables(idx->pq, c.queries, nq, ws.tl_tables, st));
-    const uint64_t n_run = resume ? plan.active : plan.retry ? plan.retry : nq_grid;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_run, cg.slots);
-    p.nq = warm ? 0u : (uint32_t)n_run;
-    if (tl_qh) {
-      p.qsel = ws.qsel;
-      p.qsel_h = ws.qsel_h;
-      isl_launch::launch_classify((uint32_t)std::min<uint64_t>(nq_grid, 2048), st, &p);
-      ISL_HIP(hipGetLastError());
-      isl_launch::launch_two_level(metric, true, false, true, (uint32_t)std::min<uint64_t>(nq_grid, cg.tl_slots_q),
-                                   cg.tl_lds_q, st, &p);
-      ISL_HIP(hipGetLastError());
-      p.qsel_mode = 1;  // the others
-      isl_launch::launch_two_level(metric, true, false, false, grid, cg.tl_lds, st, &p);
-      p.qsel_mode = 0;
-    } else {
-      isl_launch::launch_two_level(metric, idx->rows.is_bf16(), resume || (warm && idx->recompute), false, grid, cg.tl_lds, st, &p);
+  for (uint32_t i = 0; i < lp.count; ++i) {
+    const LaunchStep& s = lp.steps[i];
+    SearchParams sp = p;  // what this launch is told
+    sp.nq = s.nq;
+    sp.hbits = s.hbits;
+    sp.hcap = s.hcap;
+    sp.qsel_mode = s.qsel_mode;
+    switch (s.kind) {
+      case StepKind::SeedRedo:
+        hipLaunchKernelGGL(seed_redo_kernel, dim3(1), dim3(256), 0, st, ws.h_xlist, s.nq, ws.redo, ws.ticket);
+        break;
+      case StepKind::PqTables:
+        ISL_TRY(isl::pq_launch_tables(idx->pq, c.queries, s.nq, ws.tl_tables, st));
+        break;
+      case StepKind::Classify:
+        isl_launch::launch_classify(s.grid, st, &sp);
+        break;
+      case StepKind::TwoLevel:
+        isl_launch::launch_two_level(s.metric, s.bf16, s.resume, s.qh, s.grid, s.lds, st, &sp);
+        break;
+      case StepKind::Descent:
+        isl_launch::launch_descent(s.metric, s.bf16, s.grid, s.lds, st, &sp);
+        break;
+      case StepKind::EntryPick:
+        ISL_TRY(isl::launch_entry_pick(idx, c.queries, s.nq, ws.q_entry, ws.q_entry + s.nq,
+                                       reinterpret_cast<unsigned long long*>(ws.q_entry + 2 * (uint64_t)s.nq), ws.status,
+                                       nullptr, st));
+        break;
+      case StepKind::Fast:
+        launch_fast(isl_launch::FastKernel{s.S, s.metric, s.wide, s.dtype, s.resume, s.qh}, s.grid, s.lds, st, sp);
+        break;
+      case StepKind::FillRedoAll: {
+        std::vector<uint32_t> all(s.nq);
+        for (uint32_t q = 0; q < s.nq; q++) all[q] = q;
+        const uint32_t head0[4] = {0, s.nq, 0, 0};
+        ISL_HIP(hipMemcpyAsync(ws.redo, all.data(), (size_t)s.nq * 4, hipMemcpyHostToDevice, st));
+        ISL_HIP(hipMemcpyAsync(ws.ticket, head0, 16, hipMemcpyHostToDevice, st));
+        ISL_HIP(hipStreamSynchronize(st));
+        break;
+      }
+      case StepKind::Exact:
+        isl_launch::launch_exact(s.metric, s.hnsw, s.grid, s.lds, st, &sp);
+        break;
     }
-    ISL_HIP(hipGetLastError());
-    p.nq = warm ? 0u : (uint32_t)nq;
-  } else
-  if (use_fast && idx->is_hnsw && p.max_level > 0) {
-    // HnswGraph::search: greedy descent through the upper layers first (its own kernel, so that
-    // the traversal kernel keeps its register budget)
-    ISL_TRY(ws.q_entry.reserve(std::max<uint64_t>(nq, 1) * 2, &ws.alloc_events));
-    p.q_entry = ws.q_entry;
-    p.q_evals = ws.q_entry + nq;
-    const uint32_t dgrid = (uint32_t)std::min<uint64_t>(nq_grid, 8192);
-    isl_launch::launch_descent(metric, idx->rows.is_bf16(), dgrid, cg.descent_lds, st, &p);
-    ISL_HIP(hipGetLastError());
-  }
-  if (seeded) {
-    // q_entry[q] = the nearest seed, q_evals[q] = 1, status[q] = QS_OK (the fast kernel reads it where q_entry is set)
-    ISL_TRY(isl::launch_entry_pick(idx, c.queries, nq, ws.q_entry, ws.q_entry + nq,
-                                   reinterpret_cast<unsigned long long*>(ws.q_entry + 2 * nq), ws.status, nullptr, st));
-  }
-  if (tl) {
-  } else if (use_fast) {
-    if (resume) p.nq = plan.active;  // the fast kernel runs this round's queries; nothing else reads nq
-    uint32_t grid = (uint32_t)std::min<uint64_t>(resume ? plan.active : nq_grid, cg.slots);
-    const bool skip_fast = resume && plan.active == 0;  // only queries parked in the heap-exact kernel this round
-    isl_launch::FastKernel fk{cg.segments, metric, idx->max_degree > 64, idx->rows.dtype(), resume, false};
-    if (qh) {
-      p.qsel = ws.qsel;
-      p.qsel_h = ws.qsel_h;
-      isl_launch::launch_classify((uint32_t)std::min<uint64_t>(nq_grid, 2048), st, &p);
-      ISL_HIP(hipGetLastError());
-      p.hbits = cg.fgq.hbits;
-      p.hcap = cg.fgq.hcap;
-      fk.qh = true;  // the bf16-valued queries
-      launch_fast(fk, (uint32_t)std::min<uint64_t>(nq_grid, cg.slots_q), cg.fgq.lds, st, p);
-      ISL_HIP(hipGetLastError());
-      p.hbits = cg.fg.hbits;
-      p.hcap = cg.fg.hcap;
-      p.qsel_mode = 1;  // the others
-      fk.qh = false;
-      launch_fast(fk, grid, cg.fg.lds, st, p);
-      p.qsel_mode = 0;
-    } else if (!skip_fast) {
-      launch_fast(fk, grid, cg.fg.lds, st, p);
-    }
-    ISL_HIP(hipGetLastError());
-    p.nq = (uint32_t)nq;
-  } else if (!warm && !resume) {
-    // every query goes to the exact kernel: redo = [0, nq)
-    std::vector<uint32_t> all(nq);
-    for (uint64_t i = 0; i < nq; i++) all[i] = (uint32_t)i;
-    uint32_t head0[4] = {0, (uint32_t)nq, 0, 0};
-    ISL_HIP(hipMemcpyAsync(ws.redo, all.data(), nq * 4, hipMemcpyHostToDevice, st));
-    ISL_HIP(hipMemcpyAsync(ws.ticket, head0, 16, hipMemcpyHostToDevice, st));
-    ISL_HIP(hipStreamSynchronize(st));
-  }
-  if (!tl) {
-    uint32_t grid = (uint32_t)std::min<uint64_t>(nq_grid, idx->pool.slots);
-    isl_launch::launch_exact(metric, idx->is_hnsw, grid, cg.exact_lds, st, &p);
     ISL_HIP(hipGetLastError());
   }
   ISL_HIP(hipEventRecord(ws.ev1, st));
   ws.st_inflight = st;
-  if (warm) return ISL_OK;
+  if (!lp.publishes) return ISL_OK;
 
   if (!ws.union_launch) {  // (a group launch: its scatter kernel publishes per member, search_group.hip)
     ISL_TRY(publish(ws, nq, k, st));
@@ -529,10 +502,14 @@ isl_status search_enqueue_impl(const isl_index* idx, isl::SearchWorkspace& ws, c
   ws.enqueued = true;
   ws.nq_inflight = nq;
   ws.k_inflight = k;
-  ws.ef_inflight = ef;
-  ws.fast_inflight = use_fast;
+  ws.ef_inflight = cg.ef;
+  ws.fast_inflight = lp.use_fast;
   return ISL_OK;
 }
+
+// (defined beside search_finish, below)
+isl_status report_debug(isl::SearchWorkspace& ws, const isl::DeviceBuffer<uint64_t>& d_prof, uint64_t nq, bool use_fast,
+                        float ms);
 
 // counters of the most recent call this thread completed, per index (isl_search_last_stats)
 struct LastStats { const isl_index* idx = nullptr; isl_search_stats st{}; };
@@ -576,7 +553,6 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
   // a member of a group launch: that launch's events (the scatter kernel has filled this lane's mirrors)
   isl::SearchWorkspace& lw = ws.grp_launch ? *ws.grp_launch : ws;
   ISL_HIP(hipEventSynchronize(lw.ev_done));
-  const uint32_t* status = ws.h_status;
   const uint32_t* ctr = ws.h_ctr;
   const uint32_t* head = ws.h_head;
   isl::DeviceBuffer<uint64_t> d_prof = std::move(ws.d_prof);
@@ -610,6 +586,22 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
   if (use_fast && !idx->recompute && !misses && nq >= 16)
     idx->evals_hint.store(((uint64_t)ws.ef_inflight << 32) | std::min<uint64_t>(ss.evals / nq, 0xFFFFFFFFull),
                           std::memory_order_relaxed);
+  ISL_TRY(report_debug(ws, d_prof, nq, use_fast, ms));
+  if (misses) {
+    *misses = head[13];
+    if (head[13]) return ISL_OK;  // a round of the recompute provider: statuses are not final yet
+  }
+  if (defer_statuses) return ISL_OK;
+  return search_statuses(ws, nq);
+}
+
+namespace {
+// The ISL_TIMELINE record and the ISL_DEBUG lines of a finished call (d_prof: its phase timers, taken from the lane).
+isl_status report_debug(isl::SearchWorkspace& ws, const isl::DeviceBuffer<uint64_t>& d_prof, uint64_t nq, bool use_fast,
+                        float ms) {
+  const uint32_t* status = ws.h_status;
+  const uint32_t* ctr = ws.h_ctr;
+  const uint32_t* head = ws.h_head;
   if (ws.d_tline) {
     std::vector<uint64_t> tl(nq * 2 + 2);
     tl[0] = 0x154C494E45ull;  // record header: magic, query count
@@ -618,7 +610,7 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
     ws.d_tline.reset();
     static std::mutex tl_mu;
     std::lock_guard<std::mutex> lock(tl_mu);
-    if (FILE* f = fopen(getenv("ISL_TIMELINE"), "ab")) {
+    if (FILE* f = fopen(timeline_path(), "ab")) {
       fwrite(tl.data(), 8, tl.size(), f);
       fclose(f);
     }
@@ -637,7 +629,8 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
     fprintf(stderr, "[isl] mean us per query by phase: select+adjacency %.0f, visited %.0f, rows+distance %.0f, "
             "insert %.0f\n", sum[0] / nq, sum[1] / nq, sum[2] / nq, sum[3] / nq);
   }
-  if (getenv("ISL_DEBUG")) {
+  if (!debug_on()) return ISL_OK;
+  {
     std::vector<uint64_t> pay(nq);
     ISL_HIP(hipMemcpy(pay.data(), ws.payload, nq * 8, hipMemcpyDeviceToHost));
     std::vector<double> us;
@@ -652,19 +645,15 @@ isl_status isl_lane::search_finish(const isl_index* idx, isl::SearchWorkspace& w
               us[us.size() * 9 / 10], us[us.size() * 99 / 100], us.back(), byq.back().second,
               byq[byq.size() / 2].second, ms * 1000.0);
   }
-  if (getenv("ISL_DEBUG") && (head[1] || head[3])) {
+  if (head[1] || head[3]) {
     fprintf(stderr, "[isl] %u of %llu queries re-run by the exact kernel (fast kernel %s): "
             "long-row %u, visited-overflow %u, tie-candidate overflow %u, push-log overflow %u, "
             "NaN/-0 distance %u; %u re-ordered by the replay kernel\n", head[1], (unsigned long long)nq,
             use_fast ? "on" : "off", head[9], head[10], head[11], head[8], head[12], head[3]);
   }
-  if (misses) {
-    *misses = head[13];
-    if (head[13]) return ISL_OK;  // a round of the recompute provider: statuses are not final yet
-  }
-  if (defer_statuses) return ISL_OK;
-  return search_statuses(ws, nq);
+  return ISL_OK;
 }
+}  // namespace
 
 // per-query failures -> the CoreError the reference's sequential map would have returned
 isl_status isl_lane::search_statuses(isl::SearchWorkspace& ws, uint64_t nq) {

@@ -1,6 +1,9 @@
-// What the two host units of the search path share: search.hip (lanes, launches, entry points) and
-// search_recompute.hip (the recompute provider's row cache, rounds and coalescer).  Declarations only; the
-// symbols stay inside the library.
+// What the host units of the search path share: search.hip (lanes, parameter fill, the one loop that issues
+// launches, entry points), search_group.hip (grouped launches) and search_recompute.hip (the recompute provider's
+// row cache, rounds and coalescer).  Declarations only; the symbols stay inside the library.
+// What one enqueue launches -- which kernels, in what order, with what grid, LDS, instantiation and told nq, for a
+// SearchCall, a RoundPlan and the warm flag -- is decided in search_launch_plan.hpp (plan_launches), not here and
+// not in search.hip.
 #pragma once
 
 #include "common.hpp"
