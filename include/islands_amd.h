@@ -343,6 +343,61 @@ isl_status isl_set_embeddings_fp8(isl_index* idx, const void* codes, uint64_t n,
  * pointer may be NULL.  No resident rows (none attached, or the recompute provider) -> ISL_DTYPE_F32, 0, 0. */
 isl_status isl_index_row_storage(const isl_index* idx, int32_t* dtype, int32_t* scale_exp, uint64_t* block_bytes);
 
+/* ---- row conversions on the device (extension) ----
+ * image(x) is the exact float32 value of a stored element: the float itself, the bf16 bits shifted left by 16, or
+ * e4m3(code) * 2^scale_exp.  Every conversion below is new = narrow_T(image(old)), element by element, defined bit
+ * for bit (islands_amd/csrc/row_convert_plan.hpp is the definition in C++, islands_amd.f32_to_bf16_bits and
+ * islands_amd.quantize_fp8_e4m3 in Python):
+ *   narrow_f32      the identity.
+ *   narrow_bf16     on the bit pattern b: not a NaN -> (b + 0x7FFF + ((b >> 16) & 1)) >> 16 (round to nearest, ties
+ *                   to even; past the largest finite bf16 -> infinity); a NaN -> (b >> 16) | 0x0040 (sign kept, quiet).
+ *   narrow_fp8(e)   y = min(|x| * 2^-e, 448) rounded to the nearest e4m3 value, ties to the even code, subnormal
+ *                   spacing 2^-9; the sign bit of x is kept (-0.0 and negative values that round to zero give 0x80);
+ *                   infinities saturate to +-448; a NaN is an error, not a code.
+ * The automatic exponent (ISL_FP8_SCALE_AUTO) is the smallest e in [-32, 32] with max|x| <= 448 * 2^e: all zeros
+ * give -32, anything above 448 * 2^32, infinity included, gives 32 and saturates. */
+#define ISL_FP8_SCALE_AUTO INT32_MIN
+
+/* n x d float32 -> n x d e4m3 codes (dense, no padding), host or device buffers alike (mem).
+ * scale_exp: an exponent in [-32, 32] or ISL_FP8_SCALE_AUTO.
+ * *out_scale_exp (may be NULL) receives the exponent used.
+ * Checked before any device call: NULL buffers with n * d > 0, an unknown mem, a scale_exp that is neither ->
+ * ISL_ERR_INVALID_ARGUMENT; n * d == 0 -> ISL_OK (*out_scale_exp = -32 under AUTO).  A NaN among the rows ->
+ * ISL_ERR_INVALID_ARGUMENT with a message that says so; *out_scale_exp is then not written and the codes are
+ * undefined.  Runs on `stream` and is synchronised before returning. */
+isl_status isl_quantize_fp8_e4m3(const float* rows, uint64_t n, uint64_t d, int32_t scale_exp,
+                                 uint8_t* codes, int32_t* out_scale_exp,
+                                 int32_t mem, int32_t device, void* stream);
+
+/* n x d float32 -> bf16 bit patterns by narrow_bf16.  Checks and synchronisation as above. */
+isl_status isl_round_bf16(const float* rows, uint64_t n, uint64_t d, uint16_t* bits,
+                          int32_t mem, int32_t device, void* stream);
+
+/* The index's resident rows become rows of `dtype`: narrow_dtype(image(old)), on the device.
+ * scale_exp is read only for ISL_DTYPE_FP8_E4M3 (AUTO: taken from the images).
+ * Narrowing lets an index be built in f32 and served in a quarter of the bytes; widening is lossless and gives an
+ * fp8 index its lifecycle back: widen, isl_index_insert / isl_index_remove, narrow again under the same scale.
+ * Checks and refusals in this order: NULL idx, an unknown dtype, or target fp8 with scale_exp neither AUTO nor in
+ * [-32, 32] -> ISL_ERR_INVALID_ARGUMENT; the core index of an HnswGraph -> ISL_ERR_UNSUPPORTED; a recompute
+ * provider or no resident rows -> ISL_ERR_UNSUPPORTED; a busy lane -> ISL_ERR_SEARCH; the stored type itself ->
+ * ISL_OK with nothing touched (fp8: under AUTO or the stored exponent; another exponent -> ISL_ERR_UNSUPPORTED);
+ * a NaN image with target fp8 -> ISL_ERR_INVALID_ARGUMENT.
+ * Strong guarantee: the new table is allocated and filled beside the old one and moved in at the end; on any
+ * failure the handle is unchanged (bytes, rows, seeds, search answers).  Peak extra device memory: the new block,
+ * its norms and the norm chunk buffer.  The norms of the new table are computed from its images by the routine
+ * isl_set_embeddings uses: bit for bit what isl_set_embeddings[_fp8] of the same elements gives.
+ * What the handle keeps: config, graph, host CSR, visited-table hint, prepared lanes, the heap-exact pool and PQ
+ * codes.  Target f32 or bf16: the entry seeds keep their ids and their row copies are gathered again from the
+ * converted table (as isl_index_remove does for survivors).  Target fp8: the entry seeds go. */
+isl_status isl_index_convert_rows(isl_index* idx, int32_t dtype, int32_t scale_exp);
+
+/* Rows [first, first + count) in their stored type, dense (count x d elements, no padding),
+ * to host or device memory.  The residency checks are those of the conversion (the core index of an HnswGraph
+ * may be read); first + count > the number of rows -> ISL_ERR_NODE_NOT_FOUND naming the first id that has no row.
+ * The call only reads: it needs no idle lanes. */
+isl_status isl_index_read_rows(const isl_index* idx, uint64_t first, uint64_t count,
+                               void* out, int32_t mem);
+
 /* ---- search ---- */
 /* Work counters of one search call (summed over the batch): the inputs of the roofline formula
  * (SURVEY.md section 8d). */

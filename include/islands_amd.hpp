@@ -238,6 +238,20 @@ class LeannIndex {
     check(isl_index_row_storage(h_, &s.dtype, &s.scale_exp, &s.block_bytes));
     return s;
   }
+  // The resident rows become rows of `dtype` (ISL_DTYPE_*) on the device, each element narrowed from its exact
+  // f32 image (isl_index_convert_rows); scale_exp is read for fp8 only (the default: taken from the images).
+  void convert_rows(int32_t dtype, int32_t scale_exp = ISL_FP8_SCALE_AUTO) {
+    check(isl_index_convert_rows(h_, dtype, scale_exp));
+  }
+  // Rows [first, first + count) in their stored type as bytes, dense: count x d elements of 4 (f32), 2 (bf16 bit
+  // patterns) or 1 byte (e4m3 codes) -- row_storage().dtype says which (isl_index_read_rows)
+  std::vector<uint8_t> read_rows(uint64_t first, uint64_t count) const {
+    const int32_t dtype = row_storage().dtype;
+    const uint64_t es = dtype == ISL_DTYPE_FP8_E4M3 ? 1 : dtype == ISL_DTYPE_BF16 ? 2 : 4;
+    std::vector<uint8_t> out(count * dimension().value_or(0) * es);
+    check(isl_index_read_rows(h_, first, count, out.data(), ISL_MEM_HOST));
+    return out;
+  }
   // recompute mode: EmbeddingProvider backed by the encoder (leann.rs:82-99); the embedder is
   // borrowed and must outlive the index
   void attach_recompute(isl_encoder* enc, const std::vector<uint16_t>& tokens, uint64_t n, uint64_t L,

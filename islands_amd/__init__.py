@@ -25,7 +25,7 @@ __all__ = [
     "bruteforce_topk", "merge_topk", "merge_service",
     "device_count", "HnswGraph", "SearchConfig", "Searcher", "MultiIndexSearcher",
     "mean_pool_normalize", "service_search", "BertConfig", "CandleEmbedder", "IndexMetadata",
-    "fp8_e4m3_to_f32", "quantize_fp8_e4m3",
+    "fp8_e4m3_to_f32", "quantize_fp8_e4m3", "f32_to_bf16_bits", "quantize_fp8_e4m3_device", "round_bf16_device",
 ]
 
 MEM_HOST, MEM_DEVICE = 0, 1
@@ -82,6 +82,8 @@ def _ptr(a):
 DTYPE_F32, DTYPE_BF16, DTYPE_FP8_E4M3 = 0, 1, 2  # ISL_DTYPE_*
 FP8_E4M3_MAX = 448.0
 FP8_MIN_SCALE_EXP, FP8_MAX_SCALE_EXP = -32, 32
+_ROW_DTYPES = {"f32": DTYPE_F32, "bf16": DTYPE_BF16, "fp8": DTYPE_FP8_E4M3}
+_ROW_NUMPY = {DTYPE_F32: np.float32, DTYPE_BF16: np.uint16, DTYPE_FP8_E4M3: np.uint8}
 
 
 def _fp8_e4m3_table() -> np.ndarray:
@@ -120,18 +122,33 @@ def fp8_e4m3_to_f32(codes, scale_exp: int = 0) -> np.ndarray:
     return np.ldexp(_FP8_E4M3[c], e).astype(np.float32)
 
 
-def quantize_fp8_e4m3(rows_f32):
-    """float32 values -> (codes uint8 of the same shape, scale_exp).  scale_exp is the smallest exponent in
-    [-32, 32] with max|x| * 2^-scale_exp <= 448; a code is x * 2^-scale_exp rounded to the nearest e4m3 value,
-    ties to the even code; magnitudes above 448 * 2^scale_exp saturate to +-448.  A NaN raises ValueError."""
+def f32_to_bf16_bits(rows_f32) -> np.ndarray:
+    """float32 values -> bf16 bit patterns (uint16, same shape): round to nearest, ties to even, on the bit
+    pattern b: (b + 0x7FFF + ((b >> 16) & 1)) >> 16, so what rounds past the largest finite bf16 becomes
+    infinity; a NaN gives (b >> 16) | 0x0040 (sign kept, quiet).  What isl_round_bf16 and a conversion to bf16
+    rows (LeannIndex.convert_rows) compute on the device."""
+    b = np.ascontiguousarray(rows_f32, dtype=np.float32).view(np.uint32)
+    nan = (b & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    rounded = (b.astype(np.uint64) + 0x7FFF + ((b >> 16) & 1)) >> 16
+    return np.where(nan, (b >> 16) | np.uint32(0x0040), rounded).astype(np.uint16)
+
+
+def quantize_fp8_e4m3(rows_f32, scale_exp=None):
+    """float32 values -> (codes uint8 of the same shape, scale_exp).  scale_exp None: the smallest exponent in
+    [-32, 32] with max|x| * 2^-scale_exp <= 448; given: that exponent.  A code is x * 2^-scale_exp rounded to the
+    nearest e4m3 value, ties to the even code; magnitudes above 448 * 2^scale_exp saturate to +-448.  A NaN raises
+    ValueError."""
     x = np.asarray(rows_f32, dtype=np.float32)
     if np.isnan(x).any():
         raise ValueError("quantize_fp8_e4m3: NaN in the input")
     a = np.abs(x.astype(np.float64))
-    top = float(a.max()) if a.size else 0.0
-    e = FP8_MIN_SCALE_EXP
-    while e < FP8_MAX_SCALE_EXP and top > FP8_E4M3_MAX * 2.0 ** e:  # (both sides exact in float64)
-        e += 1
+    if scale_exp is None:
+        top = float(a.max()) if a.size else 0.0
+        e = FP8_MIN_SCALE_EXP
+        while e < FP8_MAX_SCALE_EXP and top > FP8_E4M3_MAX * 2.0 ** e:  # (both sides exact in float64)
+            e += 1
+    else:
+        e = _check_scale_exp(scale_exp)
     y = np.minimum(np.ldexp(a, -e), FP8_E4M3_MAX)  # exact: a power-of-two multiple of a float32
     # the spacing of e4m3 at y: 2^(E - 3) in the binade 2^E, 2^-9 below 2^-6 (the subnormals)
     _, ex = np.frexp(y)  # y = m * 2^ex, m in [0.5, 1)
@@ -147,6 +164,41 @@ def quantize_fp8_e4m3(rows_f32):
     code = np.where(v == 0, 0, field * 8 + mant).astype(np.uint8)
     code |= (np.signbit(x).astype(np.uint8) << 7)
     return code, e
+
+
+FP8_SCALE_AUTO = -2 ** 31  # ISL_FP8_SCALE_AUTO
+
+
+def quantize_fp8_e4m3_device(rows_f32=None, scale_exp=None, device: int = 0, device_ptr: int | None = None,
+                             out_ptr: int | None = None, n: int | None = None, d: int | None = None,
+                             stream: int | None = None):
+    """quantize_fp8_e4m3 on the device (isl_quantize_fp8_e4m3): the same codes and exponent, byte for byte.  A
+    host array -> (codes, scale_exp); or (device_ptr, out_ptr, n, d) for n x d float32 already on `device` and a
+    device buffer of n x d bytes for the codes -> scale_exp.  A NaN raises CoreError (InvalidArgument)."""
+    e_in = FP8_SCALE_AUTO if scale_exp is None else int(scale_exp)
+    e_out = _ffi.i32(0)
+    if device_ptr is not None:
+        _check(_ffi.lib().isl_quantize_fp8_e4m3(C.c_void_p(device_ptr), n, d, e_in, C.c_void_p(out_ptr), C.byref(e_out),
+                                                MEM_DEVICE, device, None if stream is None else C.c_void_p(stream)))
+        return int(e_out.value)
+    x = _f32(rows_f32)
+    codes = np.empty(x.shape, dtype=np.uint8)
+    _check(_ffi.lib().isl_quantize_fp8_e4m3(_ptr(x), x.size, 1, e_in, _ptr(codes), C.byref(e_out), MEM_HOST, device, None))
+    return codes, int(e_out.value)
+
+
+def round_bf16_device(rows_f32=None, device: int = 0, device_ptr: int | None = None, out_ptr: int | None = None,
+                      n: int | None = None, d: int | None = None, stream: int | None = None):
+    """f32_to_bf16_bits on the device (isl_round_bf16).  A host array -> uint16 bit patterns of the same shape; or
+    (device_ptr, out_ptr, n, d) for buffers already on `device`."""
+    if device_ptr is not None:
+        _check(_ffi.lib().isl_round_bf16(C.c_void_p(device_ptr), n, d, C.c_void_p(out_ptr), MEM_DEVICE, device,
+                                         None if stream is None else C.c_void_p(stream)))
+        return None
+    x = _f32(rows_f32)
+    out = np.empty(x.shape, dtype=np.uint16)
+    _check(_ffi.lib().isl_round_bf16(_ptr(x), x.size, 1, _ptr(out), MEM_HOST, device, None))
+    return out
 
 
 # --------------------------------------------------------------- distance.rs
@@ -776,6 +828,29 @@ class LeannIndex:
         dt, se, nb = _ffi.i32(0), _ffi.i32(0), u64(0)
         _check(_ffi.lib().isl_index_row_storage(self._h, C.byref(dt), C.byref(se), C.byref(nb)))
         return {"dtype": int(dt.value), "scale_exp": int(se.value), "block_bytes": int(nb.value)}
+
+    def convert_rows(self, dtype, scale_exp=None) -> "LeannIndex":
+        """The resident rows become rows of "f32", "bf16" or "fp8" on the device (isl_index_convert_rows): every
+        element is narrowed from its exact f32 image -- f32_to_bf16_bits / quantize_fp8_e4m3 are the definition.
+        scale_exp (fp8 only): None takes the exponent from the images.  Narrowing serves an index built in f32
+        from a quarter of the bytes; widening is lossless and lets an fp8 index take insert / remove again."""
+        if dtype not in _ROW_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(_ROW_DTYPES)}")
+        e = FP8_SCALE_AUTO if scale_exp is None else int(scale_exp)
+        _check(_ffi.lib().isl_index_convert_rows(self._h, _ROW_DTYPES[dtype], e))
+        return self
+
+    def read_rows(self, first: int = 0, count: int | None = None) -> np.ndarray:
+        """Rows [first, first + count) as the index stores them (isl_index_read_rows): float32, uint16 (bf16 bit
+        patterns) or uint8 (e4m3 codes, see row_storage()["scale_exp"]), [count, d].  count None: up to the end."""
+        if count is None:
+            count = max(len(self) - int(first), 0)
+        d = self.dimension()
+        if d is None:
+            raise ValueError("read_rows: the index has no dimension (LeannIndex.from_csr(..., dimension=d))")
+        out = np.empty((int(count), d), dtype=_ROW_NUMPY[self.row_storage()["dtype"]])
+        _check(_ffi.lib().isl_index_read_rows(self._h, int(first), int(count), _ptr(out), MEM_HOST))
+        return out
 
     def _attach(self, provider):
         if isinstance(provider, InMemoryEmbeddingProvider):

@@ -99,6 +99,10 @@ SIGNATURES = {
     "isl_set_embeddings": (i32, [C.c_void_p, C.c_void_p, u64, u64, i32, i32]),
     "isl_set_embeddings_fp8": (i32, [C.c_void_p, C.c_void_p, u64, u64, i32, i32]),
     "isl_index_row_storage": (i32, [C.c_void_p, P(i32), P(i32), P(u64)]),
+    "isl_quantize_fp8_e4m3": (i32, [C.c_void_p, u64, u64, i32, C.c_void_p, P(i32), i32, i32, C.c_void_p]),
+    "isl_round_bf16": (i32, [C.c_void_p, u64, u64, C.c_void_p, i32, i32, C.c_void_p]),
+    "isl_index_convert_rows": (i32, [C.c_void_p, i32, i32]),
+    "isl_index_read_rows": (i32, [C.c_void_p, u64, u64, C.c_void_p, i32]),
     "isl_search_batch": (i32, [C.c_void_p, C.c_void_p, u64, u64, u64, u64, C.c_void_p,
                                C.c_void_p, C.c_void_p]),
     "isl_hnsw_from_bytes": (i32, [C.c_void_p, C.c_size_t, i32, P(C.c_void_p)]),

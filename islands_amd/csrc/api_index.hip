@@ -714,6 +714,11 @@ isl_status isl::RowTable::fill(uint64_t first, uint64_t count, const void* src, 
   const hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
   if (stride == d) ISL_HIP(hipMemcpy(at, src, (size_t)(count * d * es), kind));
   else ISL_HIP(hipMemcpy2D(at, stride * es, src, d * es, d * es, count, kind));
+  return norms(first, count);
+}
+
+isl_status isl::RowTable::norms(uint64_t first, uint64_t count) {
+  const uint64_t d = d_, stride = stride_;
   if (dtype_ == ISL_DTYPE_F32) {
     launch_row_norm2(f32() + first * stride, count, d, stride, norm2_ + first);
   } else {

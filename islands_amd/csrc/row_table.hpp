@@ -84,6 +84,10 @@ class RowTable {
   // device memory as `mem` says), their padding zeroed, and their norms; when they are the table's last rows the
   // slack is zeroed with them.  Returns once the device is done.
   isl_status fill(uint64_t first, uint64_t count, const void* src, int32_t mem);
+  // api_index.hip -- the norms of rows [first, first + count) from the rows' images as the block holds them (fill's
+  // own second half: whatever writes rows into the block itself, as the conversion does, ends with this).  Returns
+  // once the device is done.
+  isl_status norms(uint64_t first, uint64_t count);
   // ... every row, norm and the slack zero (the recompute provider's slab: nothing is uploaded)
   isl_status zero();
 
