@@ -188,6 +188,13 @@ isl_status isl_index_build_rows(const isl_leann_config* cfg, const isl_build_opt
  * failure idx is unchanged (bytes, rows, search answers) and the old rows are never modified.  Peak device
  * memory: the old index whole, plus what isl_index_build_rows over len + n_new rows holds at its peak (the rows
  * of all nodes, the (m0 + 1)-wide construction table, the CSR twice at compaction, the padded adjacency).
+ * Reserved index (isl_index_reserve) with len + n_new <= its capacity: the new rows are written in place behind
+ * the old ones and their norms computed there; no row block is allocated and no old row is copied or written, so
+ * the peak above loses "the rows of all nodes".  The steps, the kernels, the lists built beside the old graph, the
+ * refusals and what the handle keeps are the same, and so is the guarantee: rows behind len are invisible until the
+ * grown graph is moved in, and on failure they are zeroed again.  Searches on other lanes read rows below len only.
+ * len + n_new > capacity: the reservation is used up -- a new table of exactly len + n_new rows as for an index
+ * nobody reserved, and afterwards capacity == len.  Nothing grows a reservation on its own.
  * What the handle keeps: its config, the visited-table hint, its prepared lanes (none of their buffers follows
  * the node count) and its entry seeds AS THEY ARE -- ids and row copies of nodes the graph still has, so a
  * plain search is still the reference search entered at the nearest seed; they are not re-selected.  What goes:
@@ -232,6 +239,15 @@ isl_status isl_index_insert(isl_index* idx, const isl_build_options* opts, const
  * Strong guarantee: the shrunk graph is built beside the old one and moved into the handle at the end; on any
  * failure idx is unchanged (bytes, rows, search answers).  Peak device memory: the old index whole, plus the
  * (m0 + 1)-wide table over the old nodes, the shrunk CSR twice, its padded adjacency and the survivors' rows.
+ * Reserved index (isl_index_reserve): repair, remap, the new CSR and the padded adjacency are built beside the old
+ * graph as above, but no second row block is made.  Once they stand, under the handle's lock with no lane busy and
+ * as the last step that can fail, the survivors' rows and norms move down inside the block bit for bit (new row j
+ * takes old row s[j], s the ascending survivors; rows below the first removed id do not move; a destination is
+ * written only once the row that lived there has been read, through a staging buffer of 64 MiB -- at least one row --
+ * where sources and destinations of a move overlap; ISL_COMPACT_STAGE_ROWS overrides the rows per staged move) and
+ * the vacated tail is zeroed.  The capacity is kept.  Every refusal and every allocation comes before the first
+ * move, and a busy lane answers ISL_ERR_SEARCH with nothing moved; once moves have started only a device failure
+ * can interrupt them, AND THE HANDLE'S ROWS ARE THEN UNDEFINED.  The peak above loses "the survivors' rows".
  * What the handle keeps: its config, the visited-table hint and its prepared lanes (none of their buffers
  * follows the node count), and its entry seeds REDUCED to the surviving seeds, under their new ids, their row
  * copies gathered again from the shrunk table as isl_index_set_entry_seeds gathers them (no seed left, or no
@@ -339,9 +355,37 @@ isl_status isl_set_embeddings_fp8(isl_index* idx, const void* codes, uint64_t n,
                                   int32_t mem);
 
 /* What the index's in-memory rows cost: their stored type (ISL_DTYPE_*), the scale exponent (0 unless fp8) and
- * the bytes of the row block in HBM (rows at their 16-byte-aligned pitch plus 1 KiB of slack).  Any out
- * pointer may be NULL.  No resident rows (none attached, or the recompute provider) -> ISL_DTYPE_F32, 0, 0. */
+ * the bytes of the allocated row block in HBM (rows at their 16-byte-aligned pitch plus 1 KiB of slack; a reserved
+ * index: the rows of its capacity, also while it holds no row -- type and scale are then reported as for a handle
+ * without rows).  Any out pointer may be NULL.  No resident rows (none attached, or the recompute provider) -> ISL_DTYPE_F32, 0, 0. */
 isl_status isl_index_row_storage(const isl_index* idx, int32_t* dtype, int32_t* scale_exp, uint64_t* block_bytes);
+
+/* Room for rows that come and go (extension).  The row block and the norms of `idx` are allocated for `capacity`
+ * rows; isl_index_insert then appends in place while len + n_new <= capacity and isl_index_remove compacts in
+ * place, neither allocating a second row block (see there).  Every element of the block behind row len is zero, so
+ * a reserved index answers every search bit for bit as one nobody reserved.
+ * Non-empty index with resident rows (any stored type, fp8 included): d and dtype must be the stored ones.  The call
+ * allocates one block of `capacity` rows, copies rows and norms bit for bit, zeroes the rest and moves the block in.
+ * THIS IS THE ONE COPY A RESERVATION COSTS: for its length the old table and the new one both stand.  Strong
+ * guarantee: on any failure the handle is unchanged.  capacity <= the current capacity -> ISL_OK with nothing
+ * touched (a reservation never shrinks); a capacity below len is treated as len.  isl_index_convert_rows keeps the
+ * capacity (the new table is allocated for the same number of rows: widen, insert, narrow keeps its reservation);
+ * isl_set_embeddings* replaces the table and the reservation goes with it; an insert past the capacity uses it up.
+ * Empty handle: the call fixes d and dtype (f32 or bf16) of the rows to come and allocates the table on the device
+ * the handle was uploaded to, else on device 0 (isl_index_insert's rule; the handle then lives there).  new ->
+ * reserve -> insert(all rows) is a one-call build without a second table, byte for byte isl_index_build_rows'
+ * result at batch == 1; an insert of another d -> ISL_ERR_DIMENSION_MISMATCH, of another dtype ->
+ * ISL_ERR_UNSUPPORTED.
+ * Refused in this order, before any device call: NULL idx, an unknown dtype -> ISL_ERR_INVALID_ARGUMENT; the core
+ * index of an HnswGraph, a recompute provider, a non-empty index without resident rows -> ISL_ERR_UNSUPPORTED;
+ * d == 0 on an empty handle -> ISL_ERR_EMPTY_COLLECTION; capacity above the device id range -> ISL_ERR_UNSUPPORTED;
+ * d != the stored dimension -> ISL_ERR_DIMENSION_MISMATCH (expected, actual); dtype != the stored type (an empty
+ * handle: fp8) -> ISL_ERR_UNSUPPORTED; a busy lane, because the block's address changes -> ISL_ERR_SEARCH. */
+isl_status isl_index_reserve(isl_index* idx, uint64_t capacity, uint64_t d, int32_t dtype);
+/* *capacity_rows: rows the block is allocated for (len for an index nobody reserved, 0 without resident rows);
+ * *row_allocations: how often a row block has been allocated for this handle -- a call that appends into or
+ * compacts a reserved table leaves it unchanged.  A fresh handle: 0, 0.  Either pointer may be NULL. */
+isl_status isl_index_capacity(const isl_index* idx, uint64_t* capacity_rows, uint64_t* row_allocations);
 
 /* ---- row conversions on the device (extension) ----
  * image(x) is the exact float32 value of a stored element: the float itself, the bf16 bits shifted left by 16, or

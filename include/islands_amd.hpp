@@ -238,6 +238,19 @@ class LeannIndex {
     check(isl_index_row_storage(h_, &s.dtype, &s.scale_exp, &s.block_bytes));
     return s;
   }
+  // Room for `capacity` rows (isl_index_reserve): insert() then appends and remove() compacts in place, without a
+  // second row block.  A non-empty index reserves its stored d and dtype (this is the one copy a reservation costs);
+  // an empty handle fixes those of the rows to come.
+  void reserve(uint64_t capacity, uint64_t d, int32_t dtype = ISL_DTYPE_F32) {
+    check(isl_index_reserve(h_, capacity, d, dtype));
+  }
+  // rows the block is allocated for, and how often a row block has been allocated for this handle
+  struct Capacity { uint64_t rows; uint64_t row_allocations; };
+  Capacity capacity() const {
+    Capacity c{};
+    check(isl_index_capacity(h_, &c.rows, &c.row_allocations));
+    return c;
+  }
   // The resident rows become rows of `dtype` (ISL_DTYPE_*) on the device, each element narrowed from its exact
   // f32 image (isl_index_convert_rows); scale_exp is read for fp8 only (the default: taken from the images).
   void convert_rows(int32_t dtype, int32_t scale_exp = ISL_FP8_SCALE_AUTO) {

@@ -829,6 +829,30 @@ class LeannIndex:
         _check(_ffi.lib().isl_index_row_storage(self._h, C.byref(dt), C.byref(se), C.byref(nb)))
         return {"dtype": int(dt.value), "scale_exp": int(se.value), "block_bytes": int(nb.value)}
 
+    def reserve(self, capacity: int, d: int | None = None, dtype=None) -> "LeannIndex":
+        """Room for `capacity` rows (isl_index_reserve): insert() then appends in place while len + n_new <= capacity
+        and remove() compacts in place, neither making a second row block.  A non-empty index takes d and dtype from
+        its rows (this is the one copy a reservation costs); an empty handle needs d and takes dtype "f32" or "bf16"
+        (None: "f32") for the rows to come.  A reservation never shrinks; set_embeddings drops it."""
+        if dtype is not None and dtype not in _ROW_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(_ROW_DTYPES)}")
+        if len(self):
+            if d is None:
+                d = self.dimension()
+            dt = self.row_storage()["dtype"] if dtype is None else _ROW_DTYPES[dtype]
+        else:
+            dt = _ROW_DTYPES["f32" if dtype is None else dtype]
+        _check(_ffi.lib().isl_index_reserve(self._h, int(capacity), 0 if d is None else int(d), dt))
+        return self
+
+    @property
+    def capacity(self) -> dict:
+        """{"rows": rows the row block is allocated for (len for an index nobody reserved), "row_allocations": how
+        often a row block has been allocated for this handle} (isl_index_capacity)."""
+        rows, allocs = u64(0), u64(0)
+        _check(_ffi.lib().isl_index_capacity(self._h, C.byref(rows), C.byref(allocs)))
+        return {"rows": int(rows.value), "row_allocations": int(allocs.value)}
+
     def convert_rows(self, dtype, scale_exp=None) -> "LeannIndex":
         """The resident rows become rows of "f32", "bf16" or "fp8" on the device (isl_index_convert_rows): every
         element is narrowed from its exact f32 image -- f32_to_bf16_bits / quantize_fp8_e4m3 are the definition.

@@ -102,6 +102,8 @@ SIGNATURES = {
     "isl_quantize_fp8_e4m3": (i32, [C.c_void_p, u64, u64, i32, C.c_void_p, P(i32), i32, i32, C.c_void_p]),
     "isl_round_bf16": (i32, [C.c_void_p, u64, u64, C.c_void_p, i32, i32, C.c_void_p]),
     "isl_index_convert_rows": (i32, [C.c_void_p, i32, i32]),
+    "isl_index_reserve": (i32, [C.c_void_p, u64, u64, i32]),
+    "isl_index_capacity": (i32, [C.c_void_p, P(u64), P(u64)]),
     "isl_index_read_rows": (i32, [C.c_void_p, u64, u64, C.c_void_p, i32]),
     "isl_search_batch": (i32, [C.c_void_p, C.c_void_p, u64, u64, u64, u64, C.c_void_p,
                                C.c_void_p, C.c_void_p]),

@@ -708,7 +708,7 @@ static void launch_row_norm2(const float* rows, uint64_t cnt, uint64_t d, uint64
 isl_status isl::RowTable::fill(uint64_t first, uint64_t count, const void* src, int32_t mem) {
   const uint64_t es = isl_rows::elem_size(dtype_), d = d_, stride = stride_;
   unsigned char* at = block_ + first * stride * es;
-  const uint64_t slack = first + count == n_ ? isl_rows::slack(dtype_) : 0;
+  const uint64_t slack = isl_rows::fill_tail_elems(dtype_, capacity_, first, count);
   if (stride != d) ISL_HIP(hipMemset(at, 0, (size_t)((count * stride + slack) * es)));
   else if (slack) ISL_HIP(hipMemset(at + count * stride * es, 0, (size_t)(slack * es)));
   const hipMemcpyKind kind = mem == ISL_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -746,8 +746,13 @@ isl_status isl::RowTable::norms(uint64_t first, uint64_t count) {
 }
 
 isl_status isl::RowTable::zero() {
-  ISL_HIP(hipMemset(block_, 0, (size_t)(isl_rows::alloc_elems(dtype_, n_, d_) * isl_rows::elem_size(dtype_))));
-  ISL_HIP(hipMemset(norm2_, 0, (size_t)n_ * 4));
+  return zero_from(0);
+}
+
+isl_status isl::RowTable::zero_from(uint64_t first) {
+  const uint64_t es = isl_rows::elem_size(dtype_);
+  ISL_HIP(hipMemset(block_ + first * stride_ * es, 0, (size_t)(isl_rows::tail_elems(dtype_, capacity_, d_, first) * es)));
+  if (capacity_ > first) ISL_HIP(hipMemset(norm2_ + first, 0, (size_t)(capacity_ - first) * 4));
   return ISL_OK;
 }
 
@@ -773,7 +778,8 @@ static isl_status set_embeddings(isl_index* idx, const void* rows, uint64_t n, u
   idx->seeds = {};  // copies of rows that are about to go
   free_exact_pool(idx->pool);  // sized by the row count: rebuilt by the next prepare / search
   idx->recompute = false;  // back to the in-memory provider
-  ISL_TRY(idx->rows.allocate(dtype, n, d));
+  ISL_TRY(idx->rows.allocate(dtype, n, d));  // (a reservation goes with the table it was made for)
+  ++idx->row_allocations;
   idx->rows.set_scale_exp(dtype == ISL_DTYPE_FP8_E4M3 ? scale_exp : 0);  // (before the fill: the norms are the images')
   idx->nvec = n;
   return idx->rows.fill(0, n, rows, mem);
@@ -796,9 +802,83 @@ isl_status isl_index_row_storage(const isl_index* idx, int32_t* dtype, int32_t* 
   std::lock_guard<std::mutex> lock(idx->mu);
   const RowTable& t = idx->rows;
   const bool held = t.resident() && !idx->recompute;
-  if (dtype) *dtype = held ? t.dtype() : ISL_DTYPE_F32;
-  if (scale_exp) *scale_exp = held ? t.scale_exp() : 0;
-  if (block_bytes) *block_bytes = held ? isl_rows::alloc_elems(t.dtype(), t.n(), t.d()) * isl_rows::elem_size(t.dtype()) : 0;
+  // (type and scale are those of the rows stored: a reserved table that holds none, before its first insert or after
+  // the last row left, answers here as a handle without rows does)
+  const bool stored = held && t.n() > 0;
+  if (dtype) *dtype = stored ? t.dtype() : ISL_DTYPE_F32;
+  if (scale_exp) *scale_exp = stored ? t.scale_exp() : 0;
+  if (block_bytes) *block_bytes = held ? t.block_bytes() : 0;
+  return ISL_OK;
+}
+
+isl_status isl_index_capacity(const isl_index* idx, uint64_t* capacity_rows, uint64_t* row_allocations) {
+  if (!idx) return fail(ISL_ERR_INVALID_ARGUMENT, "index is NULL");
+  std::lock_guard<std::mutex> lock(idx->mu);
+  const bool held = idx->rows.resident() && !idx->recompute;
+  if (capacity_rows) *capacity_rows = held ? idx->rows.capacity() : 0;
+  if (row_allocations) *row_allocations = idx->row_allocations;
+  return ISL_OK;
+}
+
+isl_status isl_index_reserve(isl_index* idx, uint64_t capacity, uint64_t d, int32_t dtype) {
+  static const char* who = "isl_index_reserve";
+  if (!idx) return fail(ISL_ERR_INVALID_ARGUMENT, "index is NULL");
+  if (dtype != ISL_DTYPE_F32 && dtype != ISL_DTYPE_BF16 && dtype != ISL_DTYPE_FP8_E4M3)
+    return fail(ISL_ERR_INVALID_ARGUMENT, "unknown row dtype");
+  if (idx->is_hnsw)
+    return fail(ISL_ERR_UNSUPPORTED, "%s: this is the core index of an HnswGraph, whose rows are not reserved", who);
+  if (idx->recompute)
+    return fail(ISL_ERR_UNSUPPORTED, "%s: an index on the recompute provider stores no rows", who);
+  const uint64_t n0 = idx->num_nodes;
+  const RowTable& old = idx->rows;
+  if (n0 && (idx->device < 0 || !old.resident() || !old.norm2() || old.n() != n0 || idx->nvec != n0))
+    return fail(ISL_ERR_UNSUPPORTED, "%s needs the index's rows resident on the device (isl_index_upload, "
+                "isl_set_embeddings)", who);
+  if (!n0 && d == 0) return fail(ISL_ERR_EMPTY_COLLECTION, "Empty vector collection");
+  if (capacity >= kMaxDeviceId)
+    return fail(ISL_ERR_UNSUPPORTED, "%s: a capacity of %llu rows exceeds the device id range", who,
+                (unsigned long long)capacity);
+  if (n0) {
+    if (old.d() != d) return fail_dim(old.d(), d);
+    if (old.dtype() != dtype)
+      return fail(ISL_ERR_UNSUPPORTED, "%s: the index stores %s rows and reserves no other type", who,
+                  old.is_fp8() ? "fp8" : old.is_bf16() ? "bf16" : "float32");
+  } else {
+    if (d > 65536) return fail(ISL_ERR_INVALID_ARGUMENT, "dimension out of range");
+    if (dtype == ISL_DTYPE_FP8_E4M3)
+      return fail(ISL_ERR_UNSUPPORTED, "%s: an empty index takes its rows through isl_index_insert, which takes no fp8 rows",
+                  who);
+    if (idx->has_dimension && idx->dimension != d) return fail_dim(idx->dimension, d);
+  }
+  capacity = std::max(capacity, n0);
+  const bool same_shape = old.resident() && old.d() == d && old.dtype() == dtype;
+  {  // the block's address changes: not beside a search on the same handle
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if (any_lane_busy(idx))
+      return fail(ISL_ERR_SEARCH, "Search error: rows cannot be reserved while searches are in flight");
+    if (same_shape && capacity <= old.capacity()) return ISL_OK;  // a reservation never shrinks
+  }
+  // (an empty handle: where isl_index_insert would put the rows)
+  const int32_t device = idx->device >= 0 ? idx->device : 0;
+  ISL_TRY(use_device(device));
+  // the new table beside the old one, which nothing below writes: the one copy a reservation costs
+  RowTable fresh;
+  if (fresh.allocate(dtype, n0, d, capacity, true) != ISL_OK)
+    return fail(ISL_ERR_DEVICE, "%s: hipMalloc failed for %llu rows", who, (unsigned long long)capacity);
+  fresh.set_scale_exp(n0 ? old.scale_exp() : 0);
+  if (n0) {
+    ISL_HIP(hipMemcpy(fresh.as<unsigned char>(), old.data(), (size_t)(n0 * old.stride() * isl_rows::elem_size(dtype)),
+                      hipMemcpyDeviceToDevice));
+    ISL_HIP(hipMemcpy(fresh.norm2(), old.norm2(), (size_t)n0 * 4, hipMemcpyDeviceToDevice));
+  }
+  ISL_TRY(fresh.zero_from(n0));
+  ISL_HIP(hipDeviceSynchronize());
+  std::lock_guard<std::mutex> lock(idx->mu);
+  if (any_lane_busy(idx))
+    return fail(ISL_ERR_SEARCH, "Search error: rows cannot be reserved while searches are in flight");
+  idx->rows = std::move(fresh);
+  ++idx->row_allocations;
+  idx->device = device;
   return ISL_OK;
 }
 
@@ -819,6 +899,7 @@ static isl_status alloc_recompute_cache(isl_index* idx, uint64_t rows, uint64_t 
   ISL_TRY(fresh(idx->d_stamp, rows, 0));
   ISL_TRY(fresh(idx->d_slab_head, 2, 0));  // [0] clock hand, [1] slots used so far
   ISL_TRY(idx->rows.allocate(ISL_DTYPE_F32, rows, d));
+  ++idx->row_allocations;
   return idx->rows.zero();
 }
 

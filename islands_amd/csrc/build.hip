@@ -646,6 +646,27 @@ __global__ __launch_bounds__(256) void gather_survivor_rows_kernel(const T* __re
   if (threadIdx.x == 0) out_norm2[s] = norm2[id];
 }
 
+// ... and, for a reserved table that is compacted in place, one move of isl_plan::plan_row_moves: row dst_first + i
+// of `dst` takes row src_ids[i] (src_ids NULL: row src_first + i) of `src`, every element of the stride and the norm
+// copied as bits.  One wave per row at a time, 16-byte loads and stores along the row (rows are 16-byte aligned by
+// the layout rule), 64-bit indexes.  `src` and `dst` may be the same block: the plan keeps the sources of a launch
+// apart from its destinations, so neither is declared restrict.
+template <typename T>
+__global__ __launch_bounds__(256) void move_rows_kernel(const T* src, const float* src_norm2, const uint32_t* src_ids,
+                                                        uint64_t src_first, T* dst, float* dst_norm2, uint64_t dst_first,
+                                                        uint64_t count, uint64_t stride) {
+  const uint64_t vecs = stride * sizeof(T) / 16;  // per row
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t waves = (uint64_t)gridDim.x * 4;
+  for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < count; i += waves) {
+    const uint64_t from = src_ids ? (uint64_t)src_ids[i] : src_first + i, to = dst_first + i;
+    const uint4* in = reinterpret_cast<const uint4*>(src + from * stride);
+    uint4* out = reinterpret_cast<uint4*>(dst + to * stride);
+    for (uint64_t v = lane; v < vecs; v += 64) out[v] = in[v];
+    if (lane == 0) dst_norm2[to] = src_norm2[from];
+  }
+}
+
 constexpr size_t kTileBytes = (size_t)TILE_ROWS * TILE_LD * 4;
 // (bf16 rows: no tile)
 size_t sel_lds(bool bf16, uint64_t d, uint32_t nmax, uint32_t M) {
@@ -742,6 +763,100 @@ isl_status gather_survivors(const isl::RowTable& rows, const uint32_t* d_surv, u
   if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "row compaction failed");
   return ISL_OK;
 }
+
+// ISL_DEBUG: where the time of one isl_index_insert / isl_index_remove goes.  mark(name) closes the phase that began
+// at the previous mark (the device is drained first, so a phase owns its kernels); report() prints one stderr line,
+// "[isl] <call> phases: name=ms ...", which tools/build_perf.py reads.  Without ISL_DEBUG nothing is timed or drained.
+struct PhaseLog {
+  bool on = false;
+  std::chrono::steady_clock::time_point last;
+  std::vector<std::pair<const char*, double>> phases;
+  void start() {
+    on = getenv("ISL_DEBUG") != nullptr;
+    phases.clear();
+    if (on) last = std::chrono::steady_clock::now();
+  }
+  void mark(const char* name) {
+    if (!on) return;
+    (void)hipDeviceSynchronize();
+    const auto now = std::chrono::steady_clock::now();
+    phases.emplace_back(name, std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
+  }
+  void report(const char* call) {
+    if (!on) return;
+    std::string line;
+    char buf[64];
+    for (const auto& ph : phases) {
+      snprintf(buf, sizeof(buf), " %s=%.3f", ph.first, ph.second);
+      line += buf;
+    }
+    fprintf(stderr, "[isl] %s phases:%s\n", call, line.c_str());
+    on = false;
+  }
+};
+thread_local PhaseLog g_phases;
+
+// What the in-place compaction of a reserved table needs, all of it allocated before the first move: the survivor
+// list on the device, the plan and the staging buffer (rows at the table's stride, then their norms).
+struct RowCompaction {
+  std::vector<isl_plan::RowMove> moves;
+  isl::DeviceBuffer<uint32_t> d_surv;       // [n] old ids, ascending
+  isl::DeviceBuffer<unsigned char> stage;   // [stage_rows] rows, then [stage_rows] norms
+  uint64_t stage_rows = 0, n = 0, n0 = 0;
+};
+
+isl_status prepare_row_compaction(const isl::RowTable& rows, const std::vector<uint32_t>& survivors, RowCompaction& c) {
+  const uint64_t row_bytes = rows.stride() * isl_rows::elem_size(rows.dtype());
+  c.n = survivors.size();
+  c.n0 = rows.n();
+  c.stage_rows = isl_plan::compact_stage_rows(row_bytes + 4, c.n, getenv("ISL_COMPACT_STAGE_ROWS"));
+  isl_plan::plan_row_moves(survivors.data(), c.n, c.stage_rows, c.moves);
+  bool staged = false;
+  for (const isl_plan::RowMove& m : c.moves) staged = staged || m.staged;
+  if (c.moves.empty()) return ISL_OK;
+  ISL_TRY(c.d_surv.reserve(c.n));
+  if (staged) ISL_TRY(c.stage.reserve(c.stage_rows * (row_bytes + 4)));
+  if (hipMemcpy(c.d_surv, survivors.data(), c.n * 4, hipMemcpyHostToDevice) != hipSuccess)
+    return isl::fail(ISL_ERR_DEVICE, "cannot upload the survivors");
+  return ISL_OK;
+}
+
+// The moves, then the vacated tail [n, n0) zeroed; returns once the device is done.  Only a device failure
+// interrupts it, and the table's rows are then undefined.
+isl_status compact_rows_in_place(isl::RowTable& rows, const RowCompaction& c) {
+  const uint64_t row_bytes = rows.stride() * isl_rows::elem_size(rows.dtype());
+  rows.with_row_type([&](auto row) {
+    using T = decltype(row);
+    T* block = rows.as<T>();
+    T* stage = reinterpret_cast<T*>(c.stage.get());
+    float* stage_norm2 = stage ? reinterpret_cast<float*>(c.stage.get() + c.stage_rows * row_bytes) : nullptr;
+    auto launch = [&](const T* src, const float* sn, const uint32_t* ids, T* dst, float* dn, uint64_t dst_first,
+                      uint64_t count) {
+      const uint32_t grid = (uint32_t)std::min<uint64_t>((count + 3) / 4, 1u << 20);
+      hipLaunchKernelGGL(move_rows_kernel<T>, dim3(grid), dim3(256), 0, 0, src, sn, ids, (uint64_t)0, dst, dn, dst_first,
+                         count, rows.stride());
+    };
+    for (const isl_plan::RowMove& m : c.moves) {
+      const uint32_t* ids = c.d_surv.get() + m.first_new;
+      if (!m.staged) {
+        launch(block, rows.norm2(), ids, block, rows.norm2(), m.first_new, m.count);
+      } else {
+        launch(block, rows.norm2(), ids, stage, stage_norm2, 0, m.count);
+        launch(stage, stage_norm2, nullptr, block, rows.norm2(), m.first_new, m.count);
+      }
+    }
+  });
+  if (hipGetLastError() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "row compaction launch failed");
+  const uint64_t es = isl_rows::elem_size(rows.dtype());
+  if (c.n0 > c.n &&
+      (hipMemset(rows.as<unsigned char>() + c.n * rows.stride() * es, 0,
+                 (size_t)(isl_rows::vacated_elems(rows.dtype(), rows.d(), c.n, c.n0) * es)) != hipSuccess ||
+       hipMemset(rows.norm2() + c.n, 0, (size_t)(c.n0 - c.n) * 4) != hipSuccess))
+    return isl::fail(ISL_ERR_DEVICE, "hipMemset failed");
+  if (hipDeviceSynchronize() != hipSuccess) return isl::fail(ISL_ERR_DEVICE, "row compaction failed");
+  return ISL_OK;
+}
 }  // namespace
 
 namespace isl_build {
@@ -763,7 +878,8 @@ isl_status shrink_import(Scaffold& c, const std::vector<ShrinkLayer>& layers, ui
 isl_status shrink_finish(Scaffold& c, ShrinkTables& t, const isl::RowTable& old_rows, uint32_t metric,
                          const isl_build_options& opts, const std::vector<uint32_t>& remap,
                          const std::vector<uint32_t>& survivors, const std::vector<uint64_t>& levels, bool has_entry,
-                         uint64_t entry, uint64_t max_level, bool levels_name_layers, const char* call, Shrunk& out) {
+                         uint64_t entry, uint64_t max_level, bool levels_name_layers, const char* call, Shrunk& out,
+                         bool gather_rows) {
   using isl::fail;
   const uint64_t n0 = remap.size(), n = survivors.size(), layers = t.ly.size();
   std::vector<RemoveLayer>& ly = t.ly;
@@ -862,8 +978,11 @@ isl_status shrink_finish(Scaffold& c, ShrinkTables& t, const isl::RowTable& old_
                                     hipMemcpyHostToDevice) != hipSuccess) ||
       hipMemcpy(d_ly, ly.data(), layers * sizeof(RemoveLayer), hipMemcpyHostToDevice) != hipSuccess)
     return fail(ISL_ERR_DEVICE, "cannot upload the CSR offsets");
+  g_phases.mark("repair");
   ISL_TRY(compact_lists(d_ly, (uint32_t)kept_layers, d_lv, d_remap, n0, t.d_flag + 1));
-  ISL_TRY(gather_survivors(old_rows, d_surv, n, out.rows));
+  g_phases.mark("csr_export");
+  if (gather_rows) ISL_TRY(gather_survivors(old_rows, d_surv, n, out.rows));
+  g_phases.mark("rows");
   uint32_t flag = 0;
   if (hipMemcpy(&flag, t.d_flag + 1, 4, hipMemcpyDeviceToHost) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
     return fail(ISL_ERR_DEVICE, "compaction failed");
@@ -916,6 +1035,7 @@ isl_status check_row_dtype(int32_t dtype) {
 
 Scaffold::~Scaffold() {
   const isl::ErrorRecord first = isl::last_error();
+  if (appended) (void)appended->zero_from(appended->n());  // a failed append: the rows behind the count are zero again
   keep.clear();
   isl_index_free(res);
   if (g) {  // the tables and per-query arrays it searched were borrowed from tmp, which goes after this body:
@@ -940,7 +1060,7 @@ isl_status Scaffold::alloc_bytes(void** out, uint64_t bytes, bool zero, bool kep
 
 isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw_, const void* vectors,
                           int32_t dtype, uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0,
-                          uint32_t ef, const isl_index* old) {
+                          uint32_t ef, const isl_index* old, isl::RowTable* into) {
   ISL_TRY(isl_index_new(&cfg, &g));
   g->cfg.prune_ratio = 0.0f;  // construction searches do not prune (leann.rs:692-749)
   g->host_csr_valid = false;
@@ -949,7 +1069,18 @@ isl_status Scaffold::open(const isl_leann_config& cfg, const isl_build_options& 
   g->has_dimension = true;
   g->dimension = d;
   g->max_degree = m0;  // the widest row a construction search can meet: a row is back at <= m0 ids before the next search
-  if (old) ISL_TRY(isl::set_grown_embeddings(g, old, vectors, dtype, n - old->nvec, d, mem));
+  if (into) {
+    // a reserved table with room: the new rows and their norms go in behind the ones it holds, which are not written;
+    // nothing else reads rows behind into->n() until the caller raises the count (after a failure the caller zeroes
+    // them again).  The construction graph reads the table through a view of all n rows.
+    const uint64_t n0 = into->n();
+    ISL_TRY(isl::use_device(device));
+    appended = into;
+    ISL_TRY(into->fill(n0, n - n0, vectors, mem));
+    g->rows = isl::RowTable::view_of(*into, n);
+    g->nvec = n;
+  }
+  else if (old) ISL_TRY(isl::set_grown_embeddings(g, old, vectors, dtype, n - old->nvec, d, mem));
   else ISL_TRY(isl_set_embeddings(g, vectors, n, d, dtype, mem));
   // HnswGraph heap order: distance alone.  (Set once the rows are in: isl_set_embeddings refuses a caller who swaps
   // the rows of a facade's core index for another type; the builder's own graph takes the type it is given.)
@@ -1032,8 +1163,10 @@ isl_status Scaffold::table_to_csr(const Table& t, uint64_t n, bool kept, uint64_
 
 isl_index* Scaffold::release() {
   isl_index* r = res;
-  r->rows = std::move(g->rows);
+  r->rows = std::move(g->rows);  // (a view, where the rows were appended in place)
   r->nvec = g->nvec;
+  if (!r->rows.borrowed()) ++r->row_allocations;
+  appended = nullptr;
   for (auto& b : keep) r->hnsw_owned.push_back(std::move(b));
   keep.clear();
   res = nullptr;
@@ -1093,10 +1226,12 @@ isl_status check_import(const char* call, const uint32_t* d_flag, const isl_inde
 // with resident rows of `dtype`, whose CSR returns to the builder's table in its stored order and whose
 // entry_point / max_level the loop continues from; NULL: nothing, node 0 starts the graph).  One loop over the
 // plan's steps, then compaction.  `old` is only read; the graph of all n nodes leaves in `out`, built beside
-// it, with the rows of all n nodes.  `levels`: of all n nodes, or empty (all 0).
+// it, with the rows of all n nodes.  `into`: the reserved table of the handle that grows, with room for all n rows
+// (NULL: a new table of exactly n rows); the new rows are appended to it and `out` leaves with a view of it.
+// `levels`: of all n nodes, or empty (all 0).
 isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts, const isl_index* old,
                      const void* vectors, int32_t dtype, uint64_t n_new, uint64_t d, const std::vector<uint64_t>& levels,
-                     int32_t mem, int32_t device, isl_index** out) {
+                     int32_t mem, int32_t device, isl::RowTable* into, isl_index** out) {
   using isl::fail;
   const uint64_t n0 = old ? old->num_nodes : 0, n = n0 + n_new;
   ISL_TRY(isl::use_device(device));
@@ -1110,7 +1245,8 @@ isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts,
   const uint32_t m0 = (uint32_t)cfg.m0, ef = (uint32_t)cfg.ef_construction;
 
   Scaffold c;
-  ISL_TRY(c.open(cfg, opts, false, vectors, dtype, n, d, mem, device, isl_plan::largest_step(steps), m0, ef, old));
+  ISL_TRY(c.open(cfg, opts, false, vectors, dtype, n, d, mem, device, isl_plan::largest_step(steps), m0, ef, old, into));
+  g_phases.mark("rows");
   Table t{nullptr, nullptr, m0};
   ISL_TRY(c.alloc(&t.ell, n * (m0 + 1)));
   ISL_TRY(c.alloc(&t.deg, n, true));
@@ -1125,6 +1261,7 @@ isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts,
     ISL_TRY(c.csr_to_table(t, old->d_off, old->d_adj, old->nnz, n0, d_flag));
     ISL_TRY(check_import("isl_index_insert", d_flag, old));
   }
+  g_phases.mark("list_import");
   auto note_level = [&](uint64_t id) {  // :610-613
     const uint64_t lv = levels.empty() ? 0 : levels[id];
     if (!has_entry || lv > max_level) { has_entry = true; entry = id; max_level = lv; }
@@ -1149,8 +1286,11 @@ isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts,
   // flatten, :617-627
   uint64_t* d_off = nullptr;
   uint32_t* d_adj = nullptr;
+  g_phases.mark("construction");
   ISL_TRY(c.table_to_csr(t, n, false, &d_off, &d_adj));
+  g_phases.mark("csr_export");
   ISL_TRY(isl_index_from_device_csr(&cfg, device, n, d_off, d_adj, 1, entry, 1, d, &c.res));
+  g_phases.mark("padded_adjacency");
   c.res->max_level = max_level;
   c.res->levels = levels;
   *out = c.release();
@@ -1160,8 +1300,9 @@ isl_status grow_flat(const isl_leann_config& cfg, const isl_build_options& opts,
 // What isl_index_insert does to the handle once the grown graph stands beside it (under idx->mu, no lane busy):
 // every member that follows the node count takes the grown graph's value or goes.  Nothing here can fail.
 // isl_index_remove moves its shrunk graph in the same way (`grown` is then the smaller one) and deals with the
-// entry seeds itself.
-void adopt_grown(isl_index* idx, isl_index* grown) {
+// entry seeds itself.  `rows_in_place`: the rows of grown->nvec nodes already stand in the handle's reserved table
+// (appended, or compacted), which stays where it is.
+void adopt_grown(isl_index* idx, isl_index* grown, bool rows_in_place = false) {
   // host CSR (read back from the device on demand), levels, entry
   idx->host_csr_valid = grown->host_csr_valid;
   idx->node_offsets.swap(grown->node_offsets);
@@ -1180,7 +1321,12 @@ void adopt_grown(isl_index* idx, isl_index* grown) {
   idx->d_adj = std::move(grown->d_adj);
   idx->nnz = grown->nnz;
   idx->max_degree = grown->max_degree;
-  idx->rows = std::move(grown->rows);
+  if (rows_in_place) {  // the handle's own reserved table: only its count follows
+    idx->rows.set_n(grown->nvec);
+  } else {
+    idx->rows = std::move(grown->rows);
+    if (idx->rows.resident()) ++idx->row_allocations;
+  }
   idx->nvec = grown->nvec;
   // the padded adjacency of the old graph goes.  In its place comes the grown graph's, which
   // isl_index_from_device_csr has just made: the copy the next search would otherwise make again (absent when
@@ -1231,6 +1377,10 @@ extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* 
   }
   std::vector<uint32_t> remap, survivors;
   const uint64_t n = isl_plan::build_remap(n0, ids, n_ids, remap, survivors);
+  // a reserved table is compacted in place once the shrunk graph stands (below); one nobody reserved is left alone
+  // and the survivors' rows are gathered into a new table beside it
+  const bool in_place = old_rows.reserved();
+  RowCompaction compaction;
   isl_index* shrunk = nullptr;
   // every node gone: what isl_index_build_rows gives for n == 0 under the handle's config
   if (n == 0) {
@@ -1242,23 +1392,35 @@ extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* 
     ISL_TRY(isl::use_device(idx->device));
     Scaffold c;  // the staging buffers alone: no construction graph
     isl_build::ShrinkTables t;
+    g_phases.start();
     ISL_TRY(isl_build::shrink_import(c, {{idx->d_off.get(), idx->d_adj.get(), idx->nnz, m0}}, n0, t));
     ISL_TRY(check_import("isl_index_remove", t.d_flag, idx));
+    g_phases.mark("list_import");
     isl_build::Shrunk r;
     ISL_TRY(isl_build::shrink_finish(c, t, old_rows, idx->cfg.metric, opts, remap, survivors,
                                      idx->levels.size() == n0 ? idx->levels : std::vector<uint64_t>(), idx->has_entry,
-                                     idx->entry_point, idx->max_level, false, "isl_index_remove", r));
+                                     idx->entry_point, idx->max_level, false, "isl_index_remove", r, !in_place));
     if (getenv("ISL_DEBUG"))
       fprintf(stderr, "[isl] isl_index_remove: %llu of %llu nodes removed, touched %u, candidates %llu, repair kernel "
               "%.3f ms\n", (unsigned long long)(n0 - n), (unsigned long long)n0, r.counts[0], r.candidates, r.repair_ms);
     ISL_TRY(isl_index_from_device_csr(&idx->cfg, idx->device, n, r.off[0], r.adj[0], r.entry.has ? 1 : 0, r.entry.id,
                                       idx->has_dimension ? 1 : 0, idx->dimension, &c.res));
+    g_phases.mark("padded_adjacency");
     c.res->max_level = r.entry.max_level;
     c.res->levels = std::move(r.levels);
     c.res->rows = std::move(r.rows);
     c.res->nvec = n;
     shrunk = c.res;
     c.res = nullptr;
+  }
+  if (in_place) {  // every allocation of the compaction, before the first move
+    const isl_status st = n ? prepare_row_compaction(old_rows, survivors, compaction) : isl::use_device(idx->device);
+    if (st != ISL_OK) {
+      const isl::ErrorRecord keep = isl::last_error();
+      isl_index_free(shrunk);
+      isl::last_error() = keep;
+      return st;
+    }
   }
   // the entry seeds that survive, under their new ids
   std::vector<uint64_t> seeds;
@@ -1271,10 +1433,27 @@ extern "C" isl_status isl_index_remove(isl_index* idx, const isl_build_options* 
       isl_index_free(shrunk);
       return fail(ISL_ERR_SEARCH, "Search error: the index cannot shrink while searches are in flight");
     }
-    adopt_grown(idx, shrunk);
+    if (in_place) {
+      // the last step that can fail: the survivors' rows and norms move down inside the block, bit for bit, and the
+      // vacated tail is zeroed.  Nothing has been moved before this; a device failure in it leaves the rows undefined.
+      g_phases.mark("scaffold_free");
+      const isl_status st = n ? compact_rows_in_place(idx->rows, compaction) : idx->rows.zero_from(0);
+      g_phases.mark("rows_in_place");
+      if (st != ISL_OK) {
+        const isl::ErrorRecord keep = isl::last_error();
+        isl_index_free(shrunk);
+        isl::last_error() = keep;
+        return st;
+      }
+    }
+    const int32_t device = idx->device;
+    adopt_grown(idx, shrunk, in_place);
+    if (in_place) idx->device = device;  // (every node gone: the table stays where it is)
     idx->seeds = {};  // ids and row copies of the old numbering
   }
   isl_index_free(shrunk);  // what is left of it: the old graph's host vectors
+  g_phases.mark("adopt");
+  g_phases.report("isl_index_remove");
   // their rows are gathered again from the shrunk table; a table that cannot be made stays dropped, and a plain
   // search then starts at the entry point: the graph, the rows and the remap stand either way
   if (!seeds.empty() && isl_index_set_entry_seeds(idx, seeds.data(), seeds.size()) != ISL_OK) isl::last_error() = {};
@@ -1301,7 +1480,7 @@ extern "C" isl_status isl_index_build_rows(const isl_leann_config* cfg_in, const
   std::vector<uint64_t> lv;
   if (levels) lv.assign(levels, levels + n);
   isl_index* built = nullptr;
-  ISL_TRY(grow_flat(cfg, opts, nullptr, vectors, dtype, n, d, lv, mem, device, &built));  // insert into nothing
+  ISL_TRY(grow_flat(cfg, opts, nullptr, vectors, dtype, n, d, lv, mem, device, nullptr, &built));  // insert into nothing
   // ISL_ENTRY_SEEDS=N: the finished index leaves with N entry seeds selected (as isl_index_select_entry_seeds)
   const isl_status seeded = isl::env_entry_seeds(built);
   if (seeded != ISL_OK) {
@@ -1350,6 +1529,12 @@ extern "C" isl_status isl_index_insert(isl_index* idx, const isl_build_options* 
       return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index stores %s rows and takes no other type",
                   old_rows.is_bf16() ? "bf16" : "float32");
   }
+  else if (old_rows.reserved() && old_rows.n() == 0) {  // an empty handle whose rows to come isl_index_reserve fixed
+    if (old_rows.d() != d) return isl::fail_dim(old_rows.d(), d);
+    if (old_rows.dtype() != dtype)
+      return fail(ISL_ERR_UNSUPPORTED, "isl_index_insert: the index reserved %s rows and takes no other type",
+                  old_rows.is_bf16() ? "bf16" : "float32");
+  }
   const isl_leann_config cfg = idx->cfg;
   if (const char* why = isl_plan::shape_limit(cfg.m0, cfg.ef_construction, n0 + n_new))
     return fail(ISL_ERR_UNSUPPORTED, "%s", why);
@@ -1358,23 +1543,31 @@ extern "C" isl_status isl_index_insert(isl_index* idx, const isl_build_options* 
     if (isl::any_lane_busy(idx))
       return fail(ISL_ERR_SEARCH, "Search error: the index cannot grow while searches are in flight");
   }
+  // a reserved table with room takes the new rows in place; one without it is used up: a new table of exactly
+  // n0 + n_new rows, as for an index nobody reserved
+  const bool in_place = old_rows.reserved() && old_rows.resident() && old_rows.n() == n0 && old_rows.d() == d &&
+                        old_rows.dtype() == dtype && n0 + n_new <= old_rows.capacity();
   // levels of all nodes: the index's (all 0 where it keeps none), then the new nodes'
   std::vector<uint64_t> lv(n0 + n_new, 0);
   if (idx->levels.size() == n0) std::copy(idx->levels.begin(), idx->levels.end(), lv.begin());
   if (levels) std::copy(levels, levels + n_new, lv.begin() + n0);
   isl_index* grown = nullptr;
+  g_phases.start();
   ISL_TRY(grow_flat(cfg, opts, n0 ? idx : nullptr, rows, dtype, n_new, d, lv, mem,
-                    idx->device >= 0 ? idx->device : 0, &grown));
+                    idx->device >= 0 ? idx->device : 0, in_place ? &idx->rows : nullptr, &grown));
   // the move: the grown graph was built beside the old one, which nothing has touched so far
   {
     std::lock_guard<std::mutex> lock(idx->mu);
     if (isl::any_lane_busy(idx)) {
+      if (in_place) (void)idx->rows.zero_from(n0);  // the appended rows, which no search reads
       isl_index_free(grown);
       return fail(ISL_ERR_SEARCH, "Search error: the index cannot grow while searches are in flight");
     }
-    adopt_grown(idx, grown);
+    adopt_grown(idx, grown, in_place);
   }
   isl_index_free(grown);  // what is left of it: the old graph's host vectors
+  g_phases.mark("adopt");
+  g_phases.report("isl_index_insert");
   if (first_id) *first_id = n0;
   return ISL_OK;
 }

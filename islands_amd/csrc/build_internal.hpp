@@ -6,6 +6,7 @@
 #include "build_plan.hpp"
 #include "common.hpp"
 #include "remove_plan.hpp"
+#include "row_compact_plan.hpp"
 
 namespace isl_build {
 
@@ -79,6 +80,7 @@ struct Scaffold {
   uint32_t* cand_cnt = nullptr;
   BuildParams p{};            // rows, per-step buffers and rule parameters; insert() fills in the table
   bool diverse = false, hnsw = false;
+  isl::RowTable* appended = nullptr;  // the reserved table rows were appended to: zeroed behind its count on failure
 
   Scaffold() = default;
   Scaffold(const Scaffold&) = delete;
@@ -97,9 +99,11 @@ struct Scaffold {
   // With `old` (a finished graph that grows, isl_index_insert / isl_hnsw_insert) the rows come from two sources:
   // the first old->nvec of the n are old's rows and norms, copied on the device; `vectors` holds the
   // n - old->nvec new ones, of old's stored type.
+  // With `into` (old's reserved table, or that of an empty handle, with room for all n rows) nothing is allocated or
+  // copied: the new rows are filled in behind into->n() and the construction graph reads a view of the table.
   isl_status open(const isl_leann_config& cfg, const isl_build_options& opts, bool hnsw, const void* vectors,
                   int32_t dtype, uint64_t n, uint64_t d, int32_t mem, int32_t device, uint64_t B, uint32_t m0,
-                  uint32_t ef, const isl_index* old = nullptr);
+                  uint32_t ef, const isl_index* old = nullptr, isl::RowTable* into = nullptr);
   // Inserts `cnt` nodes on table `t`, their rows being in qbuf: construction search over the table, selection
   // (truncation / hub rule, or select()), links both ways.  The nodes are id0 .. id0 + cnt - 1, or node_ids[]
   // on `layer` of an HnswGraph.  Returns once the kernels are launched.
@@ -195,10 +199,12 @@ isl_status shrink_import(Scaffold& c, const std::vector<ShrinkLayer>& layers, ui
 // which node has which layer (a node has layer L iff levels[node] >= L): the kernels then read them from a device
 // copy, and the layers above the new max_level cease to exist.  Without it the kernels get no level array: every
 // node has every layer and every layer is kept -- a flat index, whose levels only name the entry point.
-// `call` names the entry point in messages.
+// `call` names the entry point in messages.  Without `gather_rows` out.rows stays empty: the caller compacts the
+// old table in place once everything else stands (isl_index_remove on a reserved index).
 isl_status shrink_finish(Scaffold& c, ShrinkTables& t, const isl::RowTable& old_rows, uint32_t metric,
                          const isl_build_options& opts, const std::vector<uint32_t>& remap,
                          const std::vector<uint32_t>& survivors, const std::vector<uint64_t>& levels, bool has_entry,
-                         uint64_t entry, uint64_t max_level, bool levels_name_layers, const char* call, Shrunk& out);
+                         uint64_t entry, uint64_t max_level, bool levels_name_layers, const char* call, Shrunk& out,
+                         bool gather_rows = true);
 
 }  // namespace isl_build

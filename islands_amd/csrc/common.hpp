@@ -262,6 +262,9 @@ struct isl_index {
   // f32 slab indexed by SLOT -- rows.n() slots, the slab_rows of recompute_plan.hpp.
   isl::RowTable rows;
   uint64_t nvec = 0;
+  // how often a row block was allocated for this handle (isl_index_capacity): a call that appends into or compacts
+  // a reserved table leaves it as it is
+  uint64_t row_allocations = 0;
 
   // entry seeds (entry_seeds.hip); empty by default
   isl::EntrySeeds seeds;

@@ -353,7 +353,7 @@ isl_status isl_index_convert_rows(isl_index* idx, int32_t dtype, int32_t scale_e
   const uint64_t n = old.n(), d = old.d();
   RowTable fresh;
   isl::DeviceBuffer<PassResult> d_res;
-  ISL_TRY(fresh.allocate(dtype, n, d));
+  ISL_TRY(fresh.allocate(dtype, n, d, old.capacity(), old.reserved()));  // (a reservation outlives the conversion)
   ISL_TRY(d_res.reserve(1));
   ISL_HIP(hipMemset(d_res, 0, sizeof(PassResult)));
   PassResult res{};
@@ -369,8 +369,7 @@ isl_status isl_index_convert_rows(isl_index* idx, int32_t dtype, int32_t scale_e
   launch_convert(old.data(), old.dtype(), old.stride(), old.scale_exp(), fresh.as<void>(), dtype, fresh.stride(), e, n, d,
                  d_res, nullptr);
   ISL_HIP(hipGetLastError());
-  const uint64_t es = isl_rows::elem_size(dtype);
-  ISL_HIP(hipMemset(fresh.as<unsigned char>() + n * fresh.stride() * es, 0, (size_t)isl_rows::kSlackBytes));
+  ISL_TRY(fresh.zero_from(n));  // (a table nobody reserved: the slack)
   ISL_HIP(hipMemcpy(&res, d_res, sizeof(res), hipMemcpyDeviceToHost));
   if (res.flags & kFlagNaN) return nan_refused(who);
   ISL_TRY(fresh.norms(0, n));
@@ -384,6 +383,7 @@ isl_status isl_index_convert_rows(isl_index* idx, int32_t dtype, int32_t scale_e
     if (!to_fp8) seeds = idx->seeds.ids;
     idx->seeds = {};
     idx->rows = std::move(fresh);
+    ++idx->row_allocations;
   }
   if (!seeds.empty() && isl_index_set_entry_seeds(idx, seeds.data(), seeds.size()) != ISL_OK) isl::last_error() = {};
   return ISL_OK;

@@ -20,11 +20,14 @@ class RowTable {
  public:
   RowTable() = default;
   RowTable(RowTable&& o) noexcept { *this = std::move(o); }
+  ~RowTable() { reset(); }  // (a view lets go of blocks that are not its own)
   RowTable& operator=(RowTable&& o) noexcept {
     if (this != &o) {
+      reset();  // (a view lets go of its blocks, it does not free them)
       block_ = std::move(o.block_);
       norm2_ = std::move(o.norm2_);
       dtype_ = o.dtype_; scale_exp_ = o.scale_exp_; n_ = o.n_; d_ = o.d_; stride_ = o.stride_;
+      capacity_ = o.capacity_; reserved_ = o.reserved_; borrowed_ = o.borrowed_;
       o.reset();
     }
     return *this;
@@ -37,7 +40,17 @@ class RowTable {
   int32_t scale_exp() const { return scale_exp_; }
   void set_scale_exp(int32_t e) { scale_exp_ = e; }
   bool resident() const { return block_.get() != nullptr; }
-  uint64_t n() const { return n_; }  // rows in the block
+  uint64_t n() const { return n_; }  // rows the table holds
+  // Rows the block and the norms are allocated for, >= n().  Outside a call every element of the block from row n()
+  // to the end of the slack is zero (code 0 is +0 for all three types), so whole-tile reads past the last row land
+  // on zeros whatever the capacity.  A table nobody reserved has capacity() == n().
+  uint64_t capacity() const { return capacity_; }
+  // made by a reservation (isl_index_reserve): inserts append into it and removals compact it in place
+  bool reserved() const { return reserved_; }
+  // a view (view_of): the blocks belong to another table and are not freed with this one
+  bool borrowed() const { return borrowed_; }
+  // bytes of the allocated block
+  uint64_t block_bytes() const { return isl_rows::alloc_elems(dtype_, capacity_, d_) * isl_rows::elem_size(dtype_); }
   uint64_t d() const { return d_; }
   uint64_t stride() const { return stride_; }  // in elements of the stored type
   const void* data() const { return block_.get(); }
@@ -62,27 +75,44 @@ class RowTable {
   // the type alone, for a table that holds no block (what the launch geometry reads)
   void set_dtype(int32_t dtype) { dtype_ = dtype; }
   void reset() {
+    if (borrowed_) { (void)block_.release(); (void)norm2_.release(); }
     block_.reset();
     norm2_.reset();
     dtype_ = ISL_DTYPE_F32;
     scale_exp_ = 0;
-    n_ = d_ = stride_ = 0;
+    n_ = d_ = stride_ = capacity_ = 0;
+    reserved_ = borrowed_ = false;
   }
   // A block and norms for n rows of d elements, contents undefined.  What the table held goes first (it may be
   // most of the card); after a failure the table is empty.
-  isl_status allocate(int32_t dtype, uint64_t n, uint64_t d) {
+  isl_status allocate(int32_t dtype, uint64_t n, uint64_t d) { return allocate(dtype, n, d, n, false); }
+  // ... with room for `capacity` >= n rows.  The caller zeroes what lies behind row n (zero_from) once the rows are in.
+  isl_status allocate(int32_t dtype, uint64_t n, uint64_t d, uint64_t capacity, bool reserved) {
     reset();
-    if (block_.reserve(isl_rows::alloc_elems(dtype, n, d) * isl_rows::elem_size(dtype)) != ISL_OK ||
-        norm2_.reserve(n) != ISL_OK) {
+    if (block_.reserve(isl_rows::alloc_elems(dtype, capacity, d) * isl_rows::elem_size(dtype)) != ISL_OK ||
+        norm2_.reserve(capacity) != ISL_OK) {
       reset();
       return ISL_ERR_DEVICE;
     }
     dtype_ = dtype; n_ = n; d_ = d; stride_ = isl_rows::stride(dtype, d);
+    capacity_ = capacity; reserved_ = reserved;
     return ISL_OK;
   }
+  // The first `n` <= t.capacity() rows of `t` as a table that owns nothing: what a construction graph reads while it
+  // appends into the reserved table of the index that grows.
+  static RowTable view_of(const RowTable& t, uint64_t n) {
+    RowTable v;
+    v.block_.adopt(t.block_.get(), t.block_.capacity());
+    v.norm2_.adopt(t.norm2_.get(), t.norm2_.capacity());
+    v.dtype_ = t.dtype_; v.scale_exp_ = t.scale_exp_; v.n_ = n; v.d_ = t.d_; v.stride_ = t.stride_;
+    v.capacity_ = t.capacity_; v.reserved_ = t.reserved_; v.borrowed_ = true;
+    return v;
+  }
+  // the row count of a table with room: rows appended in place become visible, or a compacted table ends earlier
+  void set_n(uint64_t n) { n_ = n; }
   // api_index.hip -- rows [first, first + count) from `src` (count x d elements of the table's type, host or
-  // device memory as `mem` says), their padding zeroed, and their norms; when they are the table's last rows the
-  // slack is zeroed with them.  Returns once the device is done.
+  // device memory as `mem` says), their padding zeroed, and their norms; when they end the block (row capacity())
+  // the slack is zeroed with them.  Rows filled behind n() stay invisible until set_n.  Returns once the device is done.
   isl_status fill(uint64_t first, uint64_t count, const void* src, int32_t mem);
   // api_index.hip -- the norms of rows [first, first + count) from the rows' images as the block holds them (fill's
   // own second half: whatever writes rows into the block itself, as the conversion does, ends with this).  Returns
@@ -90,12 +120,15 @@ class RowTable {
   isl_status norms(uint64_t first, uint64_t count);
   // ... every row, norm and the slack zero (the recompute provider's slab: nothing is uploaded)
   isl_status zero();
+  // ... the block from row `first` to the end of the slack, and the norms of rows [first, capacity()), zero
+  isl_status zero_from(uint64_t first);
 
  private:
   DeviceBuffer<unsigned char> block_;
   DeviceBuffer<float> norm2_;
   int32_t dtype_ = ISL_DTYPE_F32, scale_exp_ = 0;
-  uint64_t n_ = 0, d_ = 0, stride_ = 0;
+  uint64_t n_ = 0, d_ = 0, stride_ = 0, capacity_ = 0;
+  bool reserved_ = false, borrowed_ = false;
 };
 
 // Entry seeds (entry_seeds.hip): node ids and a contiguous copy of their rows and norms, of the type and at the

@@ -25,8 +25,21 @@ inline uint64_t stride(int32_t dtype, uint64_t d) {
 }
 // elements of slack behind the last row: 256 floats / 512 bf16 / 1024 fp8 codes
 inline uint64_t slack(int32_t dtype) { return kSlackBytes / elem_size(dtype); }
-// elements of a block of n rows
+// elements of a block of n rows (a table with a capacity: of `capacity` rows)
 inline uint64_t alloc_elems(int32_t dtype, uint64_t n, uint64_t d) { return n * stride(dtype, d) + slack(dtype); }
+
+// A table with room for `capacity` rows keeps every element behind its last row zero, to the end of the slack.
+// What the passes that write rows must clear to keep that:
+// ... fill of rows [first, first + count): the slack, when the rows end the block (elements behind the rows)
+inline uint64_t fill_tail_elems(int32_t dtype, uint64_t capacity, uint64_t first, uint64_t count) {
+  return first + count == capacity ? slack(dtype) : 0;
+}
+// ... the elements from row `first` to the end of the block (a fresh reservation, a failed append)
+inline uint64_t tail_elems(int32_t dtype, uint64_t capacity, uint64_t d, uint64_t first) {
+  return (capacity - first) * stride(dtype, d) + slack(dtype);
+}
+// ... the compaction of n0 rows to n: the vacated rows [n, n0) (what lies behind them is zero already)
+inline uint64_t vacated_elems(int32_t dtype, uint64_t d, uint64_t n, uint64_t n0) { return (n0 - n) * stride(dtype, d); }
 
 // The norms of bf16 and fp8 rows come from the f32 kernel over widened chunks: rows per chunk, and the floats of the
 // chunk buffer (an f32 table of that many rows).

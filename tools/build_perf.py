@@ -1,7 +1,7 @@
 """Build time and quality of the device graph builder (isl_index_build_rows) in its batched mode.
     python tools/build_perf.py [build|insert|remove] [--nodes N] [--dim D] [--batch B] [--dataset G|M] [--select reference|diverse]
                                [--alpha A] [--no-keep-pruned] [--ef 128,256] [--nq Q] [--check-truth]
-                               [--row-dtype f32|bf16[,...]]
+                               [--row-dtype f32|bf16[,...]] [--reserve ROWS]
 Prints one JSON line per leg: build seconds, peak device memory during the build, recall@10 / evaluations /
 hops per query at every ef, mean and minimum degree.  Dataset G = synth.make_rows (clustered, the headline
 rows), M = synth.make_manifold.  --row-dtype names the legs, built one after the other in this process
@@ -20,7 +20,13 @@ call; a copy of it loses them in --insert-calls calls; one more row leaves that 
 Beside them stand the one-call build of the survivors (the yardstick for time and for recall) and the same graph
 with the removed ids merely dropped from the lists.  A third copy repeats the one-call removal under ISL_DEBUG for
 the number of touched nodes, the sum of |C(p)| and the repair kernel's time, with the device's memory polled.  The
-truth is isl_bruteforce_topk over the survivors."""
+truth is isl_bruteforce_topk over the survivors.
+
+--reserve ROWS (insert, remove): every index that grows or shrinks first reserves room for ROWS rows
+(LeannIndex.reserve), so that the calls append and compact in place.  Either way the line carries, for every measured
+call, the device bytes in use before and after it and the handle's row_allocations, and for the one-row call its
+split into phases as the library times them under ISL_DEBUG (rows: fill or copy; list_import; construction or
+repair; csr_export; padded_adjacency; rows_in_place: the compaction of a reserved table; adopt), in milliseconds."""
 import argparse, json, os, sys, threading, time
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
 import numpy as np, torch
@@ -43,6 +49,7 @@ ap.add_argument("--ef", default="128,256", help="comma-separated ef values of th
 ap.add_argument("--nq", type=int, default=None, help="default 512 (build), 1024 (insert)")
 ap.add_argument("--qstart", type=int, default=0, help="dataset G: first row of the query stream (bench.py's batch b starts at 1024 b)")
 ap.add_argument("--row-dtype", default="f32", help="comma-separated legs, each f32 or bf16")
+ap.add_argument("--reserve", type=int, default=0, help="insert / remove: reserve room for this many rows first")
 ap.add_argument("--check-truth", action="store_true", help="also report how far torch's brute force agrees with the truth")
 args = ap.parse_args()
 removing = args.mode == "remove"
@@ -84,6 +91,45 @@ def recall_at_10(idx, ef):
     return round(hit / (10.0 * nq), 4)
 
 
+def used_bytes():
+    free, total = torch.cuda.mem_get_info(0)  # hipMemGetInfo: the whole device, whoever allocated
+    return total - free
+
+
+def reserved(idx):
+    return idx.reserve(args.reserve) if args.reserve else idx
+
+
+def accounted(idx, f):
+    """(f(), seconds, {device bytes before / after the call, row_allocations after it})"""
+    before = used_bytes()
+    t = time.time()
+    r = f()
+    dt = time.time() - t
+    return r, dt, {"seconds": round(dt, 4), "device_bytes_before": before, "device_bytes_after": used_bytes(),
+                   "capacity": idx.capacity}
+
+
+def phases_of(f):
+    """f() under ISL_DEBUG (read by the call itself) with stderr to a file: (f(), the stderr text, the phases in ms)"""
+    import re, tempfile
+    with tempfile.TemporaryFile() as tmp:
+        sys.stderr.flush()
+        saved = os.dup(2)
+        os.dup2(tmp.fileno(), 2)
+        os.environ["ISL_DEBUG"] = "1"
+        try:
+            r = f()
+        finally:
+            del os.environ["ISL_DEBUG"]
+            os.dup2(saved, 2)
+            os.close(saved)
+        tmp.seek(0)
+        text = tmp.read().decode(errors="replace")
+    m = re.search(r"phases:((?: \w+=[0-9.]+)*)", text)
+    return r, text, ({k: float(v) for k, v in (kv.split("=") for kv in m.group(1).split())} if m else None)
+
+
 def insert_mode():
     K, calls = args.insert_rows, args.insert_calls
     if legs != ["f32"] or not 0 < K < N or K % calls:
@@ -97,11 +143,12 @@ def insert_mode():
         return r, time.time() - t
 
     one, base_s = timed(lambda: ia.LeannIndex.build(xh[:n0], cfg, **kw))
-    _, one_s = timed(lambda: one.insert(xh[n0:], **kw))
+    reserved(one)
+    _, one_s, one_acc = accounted(one, lambda: one.insert(xh[n0:], **kw))
     assert len(one) == N
     recall_one = recall_at_10(one, ef)
     del one
-    many = ia.LeannIndex.build(xh[:n0], cfg, **kw)
+    many = reserved(ia.LeannIndex.build(xh[:n0], cfg, **kw))
     step, per_call = K // calls, []
     for c in range(calls):
         first, dt = timed(lambda: many.insert(xh[n0 + c * step:n0 + (c + 1) * step], **kw))
@@ -109,8 +156,9 @@ def insert_mode():
         per_call.append(round(dt, 3))
     recall_many = recall_at_10(many, ef)
     extra = synth.make_manifold(1, d, 977, device=dev).cpu().numpy() if args.dataset == "M" else xh[:1] * np.float32(0.5)
-    _, single_s = timed(lambda: many.insert(extra, **kw))
+    _, single_s, single_acc = accounted(many, lambda: many.insert(extra, **kw))
     assert len(many) == N + 1
+    _, _, single_phases = phases_of(lambda: many.insert(extra * np.float32(0.75), **kw))  # one more, timed inside
     del many
     whole, whole_s = timed(lambda: ia.LeannIndex.build(xh, cfg, **kw))
     print(json.dumps({
@@ -121,19 +169,16 @@ def insert_mode():
         "many_calls": {"calls": calls, "rows_per_call": step, "seconds_per_call": per_call,
                        "seconds": round(sum(per_call), 3), "rows_per_s": round(K / sum(per_call))},
         "one_row_call_s": round(single_s, 3),
+        "reserve_rows": args.reserve, "one_call_account": one_acc, "one_row_call_account": single_acc,
+        "one_row_call_phases_ms": single_phases,
         "one_call_build": {"seconds": round(whole_s, 2), "nodes_per_s": round(N / whole_s)},
         "queries": nq, "ef": ef,
         "recall_at_10": {"grown_one_call": recall_one, "grown_many_calls": recall_many,
                          "one_call_build": recall_at_10(whole, ef)}}), flush=True)
 
 
-def used_bytes():
-    free, total = torch.cuda.mem_get_info(0)  # hipMemGetInfo: the whole device, whoever allocated
-    return total - free
-
-
 def remove_mode():
-    import re, tempfile
+    import re
     global ti
     K, calls = args.insert_rows, args.insert_calls
     if legs != ["f32"] or not 0 < K < N or K % calls:
@@ -156,7 +201,7 @@ def remove_mode():
         return r, time.time() - t
 
     def copy_of(blob, rows):
-        return ia.LeannIndex.from_bytes(blob).upload(0).set_embeddings(rows)
+        return reserved(ia.LeannIndex.from_bytes(blob).upload(0).set_embeddings(rows))
 
     scratch, scratch_s = timed(lambda: ia.LeannIndex.build(xs, cfg, **kw))
     recall_scratch = recall_at_10(scratch, ef)
@@ -178,7 +223,8 @@ def remove_mode():
     dropped = ia.LeannIndex.from_csr(g, cfg, dimension=d).upload(0).set_embeddings(xs)
     recall_dropped = recall_at_10(dropped, ef)
     del dropped, lists, kept, g
-    remap, one_s = timed(lambda: one.remove(gone, **rule))
+    reserved(one)
+    remap, one_s, one_acc = accounted(one, lambda: one.remove(gone, **rule))
     assert len(one) == N - K and (remap[mask] == np.arange(N - K, dtype=np.uint64)).all()
     recall_one = recall_at_10(one, ef)
     del one
@@ -190,7 +236,8 @@ def remove_mode():
         per_call.append(round(dt, 3))
     assert len(many) == N - K
     recall_many = recall_at_10(many, ef)
-    _, single_s = timed(lambda: many.remove([(N - K) // 2], **rule))
+    _, single_s, single_acc = accounted(many, lambda: many.remove([(N - K) // 2], **rule))
+    _, _, single_phases = phases_of(lambda: many.remove([(N - K) // 3], **rule))  # one more, timed inside
     del many
     # once more under ISL_DEBUG (read by the call itself), stderr to a file, the device's memory polled
     dbg = copy_of(blob, xh)
@@ -203,21 +250,9 @@ def remove_mode():
 
     th = threading.Thread(target=poll, daemon=True)
     th.start()
-    with tempfile.TemporaryFile() as f:
-        sys.stderr.flush()
-        saved = os.dup(2)
-        os.dup2(f.fileno(), 2)
-        os.environ["ISL_DEBUG"] = "1"
-        try:
-            dbg.remove(gone, **rule)
-        finally:
-            del os.environ["ISL_DEBUG"]
-            os.dup2(saved, 2)
-            os.close(saved)
-        stop.set()
-        th.join()
-        f.seek(0)
-        text = f.read().decode(errors="replace")
+    _, text, _ = phases_of(lambda: dbg.remove(gone, **rule))
+    stop.set()
+    th.join()
     m = re.search(r"touched (\d+), candidates (\d+), repair kernel ([0-9.]+) ms", text)
     touched, cands, kernel_ms = (int(m.group(1)), int(m.group(2)), float(m.group(3))) if m else (None, None, None)
     after = used_bytes()
@@ -231,6 +266,8 @@ def remove_mode():
         "many_calls": {"calls": calls, "rows_per_call": step, "seconds_per_call": per_call,
                        "seconds": round(sum(per_call), 3), "rows_per_s": round(K / sum(per_call))},
         "one_row_call_s": round(single_s, 3),
+        "reserve_rows": args.reserve, "one_call_account": one_acc, "one_row_call_account": single_acc,
+        "one_row_call_phases_ms": single_phases,
         "one_call_build_of_survivors": {"seconds": round(scratch_s, 2), "nodes_per_s": round((N - K) / scratch_s)},
         "queries": nq, "ef": ef,
         "recall_at_10": {"repaired_one_call": recall_one, "repaired_many_calls": recall_many,
