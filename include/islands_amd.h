@@ -609,6 +609,64 @@ isl_status isl_index_entry_seeds(const isl_index* idx, uint64_t* out, uint64_t c
 isl_status isl_index_pick_entries(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d,
                                   uint64_t* out_ids, int32_t mem, void* stream);
 
+/* ---- graph reachability (extension; the reference has no such report) ----
+ * A breadth-first walk over the graph as the device holds it, and entry seeds chosen with it.
+ * The graph of a LeannIndex: nodes 0 .. len-1, list(u) = the distinct ids of isl_index_get_neighbors(u) (the device
+ * copy keeps the first occurrence of an id within a row).  The graph of layer l of an HnswGraph: the population is
+ * the nodes with level >= l, list(u) = isl_hnsw_get_neighbors(u, l) as the device holds it (the builders never
+ * repeat an id within a list; a graph handed over with a repeated id in an upper-layer list counts every occurrence).
+ * An id in list(u) that names no node of the population (>= len, or below the layer) is a DANGLING edge: counted,
+ * never followed -- the search kernels skip such ids too.  A self-loop is an ordinary edge.
+ * Given a set of sources, depth[v] = the least number of edges from any source to v (sources: 0),
+ * ISL_DEPTH_UNREACHED for a node of the population no source reaches, ISL_DEPTH_ABSENT for a node that is not on
+ * the layer (HnswGraph only).  in_degree[v] = the number of nodes u of the population, u == v included, whose list
+ * names v; 0 for absent nodes.  Every output is independent of the order in which the device runs.
+ * The walk expands every reached node once.  isl_reach_report is eight uint64_t, 64 bytes:
+ *   nodes           the population
+ *   sources         distinct sources
+ *   reached         nodes with depth != UNREACHED, sources included
+ *   levels          max depth + 1
+ *   edges           edges followed: the ids in the lists of reached nodes that name a node of the population
+ *   dangling_edges  the ids in the lists of reached nodes that do not
+ *   no_inbound      nodes of the population with in_degree 0 (wherever they are, reached or not)
+ *   max_in_degree
+ * sources is a host array, repeats accepted; NULL with n_sources == 0 selects the starts a plain search uses: for
+ * a LeannIndex the entry-seed table if it is non-empty, else entry_point; for an HnswGraph its entry point.
+ * out_depth / out_in_degree: [len] uint32_t in `mem` (host or the graph's device), either may be NULL, as may report.
+ * Only the graph has to be on the device: no rows need be attached, and f32, bf16, fp8 rows or the recompute
+ * provider make no difference.  Errors, in this order: a NULL handle, an unknown mem, sources NULL with n_sources > 0
+ * -> ISL_ERR_INVALID_ARGUMENT; layer > max_level -> ISL_ERR_INVALID_ARGUMENT; an empty graph ->
+ * ISL_ERR_EMPTY_COLLECTION; no sources given and no entry point -> ISL_ERR_INDEX_NOT_BUILT; a source >= len or not on
+ * the layer -> ISL_ERR_NODE_NOT_FOUND with the id; a graph that is not on a device -> ISL_ERR_UNSUPPORTED.
+ * The calls only read the graph, allocate their own scratch (about 16 bytes per node) and run on a stream of their
+ * own, synchronised before they return: they may run beside searches, and must not run beside a call that changes
+ * the graph (insert, remove, upload) -- the rule of isl_index_pick_entries. */
+#define ISL_DEPTH_UNREACHED 0xFFFFFFFFu
+#define ISL_DEPTH_ABSENT 0xFFFFFFFEu
+typedef struct isl_reach_report {
+  uint64_t nodes, sources, reached, levels, edges, dangling_edges, no_inbound, max_in_degree;
+} isl_reach_report;
+isl_status isl_index_reachability(const isl_index* idx, const uint64_t* sources, uint64_t n_sources,
+                                  uint32_t* out_depth, uint32_t* out_in_degree, int32_t mem, isl_reach_report* report);
+/* (isl_hnsw_reachability: with the HnswGraph calls below) */
+/* Entry seeds with a guarantee, by this loop over the walk above:
+ *   S = the current seed table if it is non-empty, else [entry_point];  R = the nodes reachable from S
+ *   while R != all nodes and |S| < max_seeds:
+ *     j = the smallest id not in R;  S += [j];  R |= the nodes reachable from j
+ * If the loop added an id, S becomes the index's table exactly as isl_index_set_entry_seeds(S) would make it (the
+ * earlier table stays as its prefix); if it added none the table is left as it was, and an index without a table
+ * stays without one.  *out_count = the table's size after the call, out_ids (may be NULL, room for max_seeds) its
+ * ids, *out_unreached = the rows the table still does not reach: non-zero only where max_seeds ended the loop.
+ * THE GUARANTEE: with *out_unreached == 0 every row is reachable from SOME seed of the table.  It does not say that
+ * the greedy search that starts at the seed PICKED for a query (the nearest one) finds a given row: a search of
+ * bounded ef may stop short of it, and the row may be reachable only from another seed.
+ * Preconditions, refusals and the "no search in flight" rule are those of isl_index_select_entry_seeds, each checked
+ * before anything is touched: max_seeds > ISL_MAX_ENTRY_SEEDS, the index of an HnswGraph, no rows resident on the
+ * device (none attached, or the recompute provider), fp8 rows -> ISL_ERR_UNSUPPORTED; an empty index ->
+ * ISL_ERR_EMPTY_COLLECTION; searches in flight -> ISL_ERR_SEARCH. */
+isl_status isl_index_cover_entry_seeds(isl_index* idx, uint64_t max_seeds, uint64_t* out_ids, uint64_t* out_count,
+                                       uint64_t* out_unreached);
+
 /* ---- distance.rs ---- */
 /* Distance::calculate, distance.rs:38-52. */
 isl_status isl_distance(int32_t metric, const float* a, uint64_t na, const float* b, uint64_t nb,
@@ -896,6 +954,9 @@ isl_status isl_hnsw_search_batch(const isl_hnsw* h, const float* queries, uint64
 /* Work counters of the most recent search on this graph (see isl_search_last_stats);
  * exact_path = queries in which two equal distances met and the heap-exact kernel decided. */
 isl_status isl_hnsw_last_stats(const isl_hnsw* h, isl_search_stats* out);
+/* The reachability report of layer `layer` (see "graph reachability" above). */
+isl_status isl_hnsw_reachability(const isl_hnsw* h, uint64_t layer, const uint64_t* sources, uint64_t n_sources,
+                                 uint32_t* out_depth, uint32_t* out_in_degree, int32_t mem, isl_reach_report* report);
 
 /* ---- HnswGraph construction on the device: HnswGraph::insert, hnsw.rs:214-329 ---- */
 typedef struct isl_hnsw_config { /* HnswConfig, hnsw.rs:15-28 */

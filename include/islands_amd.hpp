@@ -113,6 +113,17 @@ struct InMemoryEmbeddingProvider {
   uint64_t len() const { return embeddings.size() / dim; }
 };
 
+// The reachability report of a graph on the device (isl_index_reachability / isl_hnsw_reachability): the counters, and
+// the per-node arrays that were asked for ([len], ISL_DEPTH_UNREACHED / ISL_DEPTH_ABSENT as the header defines them).
+struct Reachability {
+  isl_reach_report report{};
+  std::vector<uint32_t> depth, in_degree;
+};
+struct CoveredSeeds {
+  std::vector<uint64_t> ids;  // the table after the call
+  uint64_t unreached = 0;     // rows it still does not reach (non-zero only where max_seeds ended the loop)
+};
+
 // LeannIndex, src/core/leann.rs:492-1067
 class LeannIndex {
  public:
@@ -288,6 +299,27 @@ class LeannIndex {
     check(isl_index_entry_seeds(h_, ids.data(), n, &n));
     return ids;
   }
+  // Breadth-first report of the graph on the device from `sources` (empty: the entry-seed table if there is one,
+  // else the entry point); no rows need be attached
+  Reachability reachability(const std::vector<uint64_t>& sources = {}, bool depth = false, bool in_degree = false) const {
+    Reachability r;
+    if (depth) r.depth.resize(len());
+    if (in_degree) r.in_degree.resize(len());
+    check(isl_index_reachability(h_, sources.empty() ? nullptr : sources.data(), sources.size(),
+                                 depth ? r.depth.data() : nullptr, in_degree ? r.in_degree.data() : nullptr, ISL_MEM_HOST,
+                                 &r.report));
+    return r;
+  }
+  // Extends the table (or [entry_point]) by the smallest unreached id until every row is reachable from SOME seed or
+  // the table holds max_seeds (isl_index_cover_entry_seeds)
+  CoveredSeeds cover_entry_seeds(uint64_t max_seeds = ISL_MAX_ENTRY_SEEDS) {
+    CoveredSeeds c;
+    c.ids.resize(max_seeds);
+    uint64_t n = 0;
+    check(isl_index_cover_entry_seeds(h_, max_seeds, c.ids.data(), &n, &c.unreached));
+    c.ids.resize(n < max_seeds ? n : max_seeds);
+    return c;
+  }
   // queries: nq rows of dimension() floats, row-major
   std::vector<uint64_t> pick_entries(const std::vector<float>& queries, uint64_t nq) const {
     std::vector<uint64_t> ids(nq);
@@ -454,6 +486,18 @@ class HnswGraph {
     check(isl_hnsw_remove(h_, &opts, ids.empty() ? nullptr : ids.data(), ids.size(), remap.data(), nullptr));
     if (!ids.empty()) vectors_.clear();  // the host copy of the larger graph's rows: get_vector asks the device now
     return remap;
+  }
+  // Breadth-first report of one layer from `sources` (empty: the entry point); depth holds ISL_DEPTH_ABSENT for the
+  // nodes below the layer (isl_hnsw_reachability)
+  Reachability reachability(uint64_t layer = 0, const std::vector<uint64_t>& sources = {}, bool depth = false,
+                            bool in_degree = false) const {
+    Reachability r;
+    if (depth) r.depth.resize(len());
+    if (in_degree) r.in_degree.resize(len());
+    check(isl_hnsw_reachability(h_, layer, sources.empty() ? nullptr : sources.data(), sources.size(),
+                                depth ? r.depth.data() : nullptr, in_degree ? r.in_degree.data() : nullptr, ISL_MEM_HOST,
+                                &r.report));
+    return r;
   }
   // HnswGraph::to_bytes, hnsw.rs:507-509 (nodes in ascending id)
   std::vector<uint8_t> to_bytes() const {

@@ -16,7 +16,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _ffi
-from ._ffi import BertConfigC, BuildOptionsC, IndexMetadataC, LeannConfigC, SearchStatsC, u64
+from ._ffi import BertConfigC, BuildOptionsC, IndexMetadataC, LeannConfigC, ReachReportC, SearchStatsC, u64
 
 __all__ = [
     "CoreError", "DistanceMetric", "PruningStrategy", "LeannConfig", "CsrGraph",
@@ -76,6 +76,36 @@ def _f32(a):
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+DEPTH_UNREACHED, DEPTH_ABSENT = 0xFFFFFFFF, 0xFFFFFFFE  # ISL_DEPTH_*
+
+
+def _reachability(call, n, sources, depth, in_degree, d_depth_ptr, d_in_degree_ptr):
+    """The argument handling the two reachability reports share: call(sources, count, depth, in_degree, mem, report).
+    Host arrays are returned under "depth" / "in_degree"; d_*_ptr name [len] u32 buffers on the graph's device."""
+    src = None if sources is None else np.ascontiguousarray(sources, dtype=np.uint64).ravel()
+    on_device = d_depth_ptr is not None or d_in_degree_ptr is not None
+    out = {}
+    if on_device:
+        pd = C.c_void_p(d_depth_ptr) if d_depth_ptr is not None else None
+        pi = C.c_void_p(d_in_degree_ptr) if d_in_degree_ptr is not None else None
+    else:
+        if depth:
+            out["depth"] = np.zeros(max(n, 1), dtype=np.uint32)
+        if in_degree:
+            out["in_degree"] = np.zeros(max(n, 1), dtype=np.uint32)
+        pd = _ptr(out["depth"]) if depth else None
+        pi = _ptr(out["in_degree"]) if in_degree else None
+    rep = ReachReportC()
+    if src is not None and not src.size:  # (to the library, no sources means the default starts)
+        raise ValueError("sources is empty: pass None for the default starts")
+    _check(call(None if src is None else _ptr(src), 0 if src is None else src.size, pd, pi,
+                MEM_DEVICE if on_device else MEM_HOST, C.byref(rep)))
+    res = {name: int(getattr(rep, name)) for name, _ in ReachReportC._fields_}
+    for k, v in out.items():
+        res[k] = v[:n]
+    return res
 
 
 # ------------------------------------------------------------------ fp8 rows
@@ -644,6 +674,25 @@ class LeannIndex:
         _check(_ffi.lib().isl_index_pick_entries(self._h, _ptr(q), q.shape[0], q.shape[1], _ptr(out), MEM_HOST,
                                                  None))
         return out[:q.shape[0]]
+
+    # ---- extension: graph reachability and entry seeds that reach every row ----
+    def reachability(self, sources=None, depth: bool = False, in_degree: bool = False,
+                     d_depth_ptr: int | None = None, d_in_degree_ptr: int | None = None) -> dict:
+        """isl_index_reachability: the breadth-first report of the graph on the device from `sources` (None: the
+        entry-seed table if there is one, else the entry point).  Returns the fields of isl_reach_report plus the
+        arrays asked for ("depth", "in_degree": [len] u32, DEPTH_UNREACHED where no source reaches)."""
+        l = _ffi.lib()
+        return _reachability(lambda s, ns, pd, pi, mem, rep: l.isl_index_reachability(self._h, s, ns, pd, pi, mem, rep),
+                             len(self), sources, depth, in_degree, d_depth_ptr, d_in_degree_ptr)
+
+    def cover_entry_seeds(self, max_seeds: int = 65536) -> dict:
+        """isl_index_cover_entry_seeds: extends the entry-seed table (or [entry_point]) by the smallest unreached id
+        until every row is reachable from some seed or the table holds max_seeds.  {"ids": the table after the call
+        (empty where none was needed and none existed), "unreached": rows it still does not reach}."""
+        out = np.zeros(max(int(max_seeds), 1), dtype=np.uint64)
+        n, un = C.c_uint64(), C.c_uint64()
+        _check(_ffi.lib().isl_index_cover_entry_seeds(self._h, max_seeds, _ptr(out), C.byref(n), C.byref(un)))
+        return {"ids": out[:min(n.value, out.size)].copy(), "unreached": int(un.value)}
 
     @classmethod
     def from_device_csr(cls, d_offsets_ptr: int, d_neighbors_ptr: int, num_nodes: int,
@@ -1390,6 +1439,15 @@ class HnswGraph:
             out = np.zeros(cnt.value, dtype=np.uint64)
             _check(_ffi.lib().isl_hnsw_get_neighbors(self._h, node, layer, _ptr(out), out.size, C.byref(cnt), None))
         return out[:cnt.value].tolist()
+
+    def reachability(self, layer: int = 0, sources=None, depth: bool = False, in_degree: bool = False,
+                     d_depth_ptr: int | None = None, d_in_degree_ptr: int | None = None) -> dict:
+        """isl_hnsw_reachability: the breadth-first report of one layer from `sources` (None: the entry point).
+        "depth" holds DEPTH_ABSENT for the nodes below the layer."""
+        l = _ffi.lib()
+        return _reachability(
+            lambda s, ns, pd, pi, mem, rep: l.isl_hnsw_reachability(self._h, layer, s, ns, pd, pi, mem, rep),
+            len(self), sources, depth, in_degree, d_depth_ptr, d_in_degree_ptr)
 
     def to_bytes(self) -> bytes:
         """HnswGraph::to_bytes (hnsw.rs:507-509): nodes in ascending id."""

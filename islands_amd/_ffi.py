@@ -51,6 +51,12 @@ class SearchStatsC(C.Structure):
                 ("encoded_nodes", u64), ("recompute_rounds", u64), ("allocations", u64)]
 
 
+class ReachReportC(C.Structure):
+    """isl_reach_report: eight u64, 64 bytes."""
+    _fields_ = [("nodes", u64), ("sources", u64), ("reached", u64), ("levels", u64), ("edges", u64),
+                ("dangling_edges", u64), ("no_inbound", u64), ("max_in_degree", u64)]
+
+
 class BuildOptionsC(C.Structure):
     """isl_build_options: the builder's selection rule and its parameters."""
     _fields_ = [("struct_size", u32), ("select_rule", u32), ("alpha", f32), ("keep_pruned", u32),
@@ -185,6 +191,9 @@ SIGNATURES = {
     "isl_index_set_entry_seeds": (i32, [C.c_void_p, C.c_void_p, u64]),
     "isl_index_entry_seeds": (i32, [C.c_void_p, C.c_void_p, u64, P(u64)]),
     "isl_index_pick_entries": (i32, [C.c_void_p, C.c_void_p, u64, u64, C.c_void_p, i32, C.c_void_p]),
+    "isl_index_reachability": (i32, [C.c_void_p, C.c_void_p, u64, C.c_void_p, C.c_void_p, i32, P(ReachReportC)]),
+    "isl_hnsw_reachability": (i32, [C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, C.c_void_p, i32, P(ReachReportC)]),
+    "isl_index_cover_entry_seeds": (i32, [C.c_void_p, u64, C.c_void_p, P(u64), P(u64)]),
     "isl_index_metadata_new": (None, [u64, u64, C.c_int64, P(IndexMetadataC)]),
     "isl_storage_write_metadata": (i32, [P(IndexMetadataC), P(C.c_void_p), P(C.c_size_t)]),
     "isl_storage_read_metadata": (i32, [C.c_void_p, C.c_size_t, P(IndexMetadataC), P(C.c_size_t)]),

@@ -378,6 +378,10 @@ isl_status launch_entry_pick(const isl_index* idx, const float* d_queries, uint6
                              hipStream_t st);
 // ... ISL_ENTRY_SEEDS=N after a successful build: selects N seeds for `idx` (unset or 0: nothing)
 isl_status env_entry_seeds(isl_index* idx);
+// ... what every call that makes a table asks of the handle first (`who` names the call in the message), and the
+// table itself from checked ids (under idx->mu, no search in flight): graph_reach.hip installs its cover through these
+isl_status check_seedable_index(const isl_index* idx, const char* who);
+isl_status install_entry_seeds(isl_index* idx, const std::vector<uint64_t>& ids);
 void free_workspace(SearchWorkspace& ws);
 void free_exact_pool(ExactPool& pool);
 // true while a search is in flight on any lane (call under idx->mu): provider / PQ setters and

@@ -352,6 +352,9 @@ isl_status launch_entry_pick(const isl_index* idx, const float* d_queries, uint6
   return ISL_OK;
 }
 
+isl_status check_seedable_index(const isl_index* idx, const char* who) { return check_seedable(idx, who); }
+isl_status install_entry_seeds(isl_index* idx, const std::vector<uint64_t>& ids) { return install_seeds(idx, ids); }
+
 isl_status env_entry_seeds(isl_index* idx) {
   uint64_t count = 0;
   const char* text = getenv("ISL_ENTRY_SEEDS");

@@ -11,7 +11,9 @@ One JSON line per measurement.
           window a:b is batch a // 1024 onward of bench.py's manifold batches): recall@10 against the library's
           f32 brute force, evaluations and hops per query, and the rate of device-buffer calls of 1024 queries
           (wall clock over the window, one call at a time, and the calls' HIP-event kernel time, which
-          includes the pick)."""
+          includes the pick).  Every leg -- no seeds, each k-centre seed count, and `cover`
+          (isl_index_cover_entry_seeds on the index without a table) -- also reports the seeds in use and
+          reached / len of LeannIndex.reachability from the starts that leg's searches use."""
 import argparse, json, os, sys, time
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
 import numpy as np, torch
@@ -95,6 +97,7 @@ cnt_d = torch.zeros(nq_call, dtype=torch.int32, device=dev)
 
 def measure(tag, n_seeds, select_s):
     idx.prepare(nq_call, args.ef, 10, 2)
+    reach = idx.reachability()
     for a, b in windows:
         hits = evals = hops = n = allocs = 0
         kernel_ms = 0.0
@@ -115,7 +118,8 @@ def measure(tag, n_seeds, select_s):
                 hits += len(set(ids[i, :cnt[i]].tolist()) & set(truth[s + i].tolist()))
         print(json.dumps({"what": "entry_seeds_search", "dataset": args.dataset, "nodes": N, "dim": d,
                           "select_rule": args.select, "build_s": round(build_s, 2), "leg": tag, "seeds": n_seeds,
-                          "selection_s": select_s, "ef": args.ef, "window": f"{a}:{b}", "queries": n,
+                          "selection_s": select_s, "reached": reach["reached"],
+                          "reached_of_len": round(reach["reached"] / N, 6), "ef": args.ef, "window": f"{a}:{b}", "queries": n,
                           "recall_at_10": round(hits / (10.0 * n), 4), "evals_per_query": round(evals / n, 1),
                           "hops_per_query": round(hops / n, 1),
                           "queries_per_s_wall_incl_copies": round(n / wall),
@@ -128,5 +132,9 @@ for E in seed_counts:
     t = time.time()
     got = idx.select_entry_seeds(E)
     measure("seeded", len(got), round(time.time() - t, 3))
+idx.set_entry_seeds([])
+t = time.time()
+got = idx.cover_entry_seeds()
+measure("cover", len(got["ids"]), round(time.time() - t, 3))
 idx.set_entry_seeds([])
 measure("unseeded_again", 0, None)

@@ -7,8 +7,8 @@ before left (the handle shrinks in place and cannot be copied); a count above 40
 that the largest stays the share of the graph the flat removal was measured with.  For each removal: seconds of
 the call (host clock, the call ends in a device synchronise); seconds of HnswGraph.build of the survivors in the
 same process, same rule and batch -- the yardstick for time and for quality; recall@10 at --ef of both graphs
-against isl_bruteforce_topk over the survivors; the survivors not reachable from the entry point on layer 0, for
-both; and the call's ISL_DEBUG line (removed, touched lists per layer, candidates, repair-kernel ms), which the
+against isl_bruteforce_topk over the survivors; the survivors not reachable from the entry point on layer 0
+(HnswGraph.reachability), for both; and the call's ISL_DEBUG line (removed, touched lists per layer, candidates, repair-kernel ms), which the
 library writes to stderr and this tool captures.  Prints one JSON document and writes it to --out."""
 import argparse, json, os, sys, tempfile, time
 sys.path[:0] = [os.path.dirname(os.path.dirname(os.path.abspath(__file__)))]
@@ -66,29 +66,20 @@ def recall(g, rows, q):
     return round(hit / (10.0 * len(got)), 4)
 
 
+HOST_WALK_UP_TO = 200_000  # nodes up to which the host walk (one ctypes call per node) runs beside the device's
+
+
 def unreachable(g):
-    """survivors a walk over layer 0 from the entry point does not meet"""
-    import ctypes as C
-    n = len(g)
-    if not n:
+    """survivors a walk over layer 0 from the entry point does not meet: HnswGraph.reachability on the device,
+    cross-checked against the host walk of tools/host_walk.py where that takes seconds"""
+    if not len(g):
         return 0
-    fn, buf, cnt = ia._ffi.lib().isl_hnsw_get_neighbors, np.zeros(129, dtype=np.uint64), C.c_uint64()
-    ptr, pc = C.c_void_p(buf.ctypes.data), C.byref(cnt)
-    off, adj = np.zeros(n + 1, dtype=np.int64), np.zeros(n * 32, dtype=np.int64)  # lists of up to m0 = 32 ids
-    for i in range(n):
-        fn(g._h, i, 0, ptr, 129, pc, None)
-        off[i + 1] = off[i] + cnt.value
-        adj[off[i]:off[i + 1]] = buf[:cnt.value]
-    seen = np.zeros(n, dtype=bool)
-    front = np.array([g.entry_point], dtype=np.int64)
-    seen[front] = True
-    while front.size:  # one level of the walk per turn: the lists of the frontier, gathered at once
-        lens = off[front + 1] - off[front]
-        at = np.repeat(off[front] - np.concatenate([[0], np.cumsum(lens)[:-1]]), lens) + np.arange(lens.sum())
-        nxt = np.unique(adj[at])
-        front = nxt[~seen[nxt]]
-        seen[front] = True
-    return int((~seen).sum())
+    r = g.reachability(layer=0)
+    missed = r["nodes"] - r["reached"]
+    if len(g) <= HOST_WALK_UP_TO:
+        import host_walk
+        assert host_walk.hnsw_unreachable(g) == missed
+    return missed
 
 
 x = synth.make_manifold(N, d, 42, device=dev)
