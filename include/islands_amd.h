@@ -667,6 +667,76 @@ isl_status isl_index_reachability(const isl_index* idx, const uint64_t* sources,
 isl_status isl_index_cover_entry_seeds(isl_index* idx, uint64_t max_seeds, uint64_t* out_ids, uint64_t* out_count,
                                        uint64_t* out_unreached);
 
+/* ---- refined search (extension; the reference scores every candidate against the rows it traverses) ----
+ * An index may carry a REFINE TABLE: a second table y of len x d elements, f32 or bf16 (bf16 rows count as their
+ * exact f32 images, as everywhere), independent of the provider's rows.  A refined search traverses the provider's
+ * rows -- narrow ones, fp8 or bf16, are the point -- and re-scores the `candidates` best of them against y:
+ *   isl_search_refined_batch[_device](q, k, candidates, ef)  IS  isl_search_batch_device(q, candidates, ef)
+ *   followed by the rescoring of its output rows (below); the inner search is the existing one with its entry
+ *   seeds, stored row type, per-query errors and counters, and isl_search_last_stats reports ITS counters (the
+ *   rescoring's evaluations are not in V).
+ * Rescoring one query q with candidate ids cand[0 .. c) and k:
+ *   s_i = Distance::calculate(metric, q, y[cand[i]]) in the reference's order of operations (cosine: norm_b is the
+ *   precomputed sum of squares of the row); the answer is the first min(k, c') candidates in ascending order of
+ *   (key(s_i), i), key = the search's total order of distances (-0 == +0, NaN last): among equal scores the EARLIER
+ *   position wins.  The distances written are the s_i.  c' counts the candidates with cand[i] < len: an id that
+ *   names no row is skipped, neither scored nor counted.  A repeated id is scored where it stands and may appear
+ *   twice.  Limits: c <= ISL_REFINE_MAX_CANDIDATES, k <= pitch.
+ * Placement: ISL_REFINE_DEVICE keeps y in a row table like the provider's (same pitch and slack rules);
+ * ISL_REFINE_HOST keeps it in ONE block of pinned, device-mapped host memory at the same pitch, allocated by the
+ * library, which the kernel reads across the bus through its device pointer (no XNACK, no managed memory): one
+ * query touches `candidates` rows, so the wide rows of an index need no HBM.  In both placements the sums of squares
+ * live on the device and come from the routine isl_set_embeddings uses: bit for bit the provider's norms for the
+ * same elements.
+ * The table is dropped by isl_index_insert and isl_index_remove (they change the node count) and by n == 0; it is
+ * kept by isl_set_embeddings*, isl_index_convert_rows, isl_index_reserve and the entry-seed setters -- the intended
+ * flow is build(rows), isl_index_set_refine_rows(rows, ISL_REFINE_HOST), isl_index_convert_rows(fp8).  It is not part
+ * of isl_index_to_bytes / isl_index_save, which are the reference's format. */
+enum { ISL_REFINE_DEVICE = 0, ISL_REFINE_HOST = 1 };
+#define ISL_REFINE_MAX_CANDIDATES 512u
+/* rows: n x d elements of `dtype` (ISL_DTYPE_F32 or ISL_DTYPE_BF16 bit patterns), dense, in host memory or on the
+ * index's device (mem = ISL_MEM_*).  Checks and refusals in this order, before any device call: NULL idx, or NULL
+ * rows with n > 0 -> ISL_ERR_INVALID_ARGUMENT; an unknown dtype, mem or placement -> ISL_ERR_INVALID_ARGUMENT; fp8 ->
+ * ISL_ERR_UNSUPPORTED; the core index of an HnswGraph -> ISL_ERR_UNSUPPORTED; an index that is not on a device ->
+ * ISL_ERR_UNSUPPORTED; n == 0 -> the table is dropped, ISL_OK; n != isl_index_len -> ISL_ERR_INVALID_ARGUMENT naming
+ * both; d == 0 -> ISL_ERR_EMPTY_COLLECTION; the index has a dimension and d differs -> ISL_ERR_DIMENSION_MISMATCH; a
+ * busy lane -> ISL_ERR_SEARCH.  Strong guarantee: the new table is made beside the old one and moved in at the end. */
+isl_status isl_index_set_refine_rows(isl_index* idx, const void* rows, uint64_t n, uint64_t d,
+                                     int32_t dtype, int32_t mem, int32_t placement);
+/* The refine table's stored type, placement, row count (0: no table) and the bytes of its row block (device memory
+ * for ISL_REFINE_DEVICE, pinned host memory for ISL_REFINE_HOST).  Any out pointer may be NULL. */
+isl_status isl_index_refine_storage(const isl_index* idx, int32_t* dtype, int32_t* placement,
+                                    uint64_t* rows, uint64_t* block_bytes);
+/* The rescoring alone, every buffer on the index's device.  Enqueue only: no synchronisation, no allocation; it
+ * composes behind any search via stream order or isl_search_stream_wait.  d_cand_ids: [nq][pitch] u64 of which
+ * d_cand_count[q] <= pitch are valid in row q (what lies behind them is not read); d_out_ids / d_out_dist: [nq][k],
+ * d_out_count: [nq].  Refusals as for the refined search below (pitch in the place of candidates). */
+isl_status isl_rescore_device(const isl_index* idx, const float* d_queries, uint64_t nq, uint64_t d,
+                              const uint64_t* d_cand_ids, const uint32_t* d_cand_count, uint64_t pitch,
+                              uint64_t k, uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
+                              void* stream);
+/* ... with host buffers in and out (what the C++ and Python mirrors' rescore() call): staged through the handle's
+ * scratch on the legacy default stream, synchronised before returning; slots behind out_count[q] are zero. */
+isl_status isl_rescore(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d, const uint64_t* cand_ids,
+                       const uint32_t* cand_count, uint64_t pitch, uint64_t k, uint64_t* out_ids, float* out_dist,
+                       uint32_t* out_count);
+/* The plain search with k = candidates, then the rescoring, on one stream with no host round trip in between;
+ * synchronised before returning, like isl_search_batch_device.  The scratch for the inner answers (nq x candidates
+ * ids and distances, nq counts) is the handle's and is reused; concurrent calls are safe, one set per call in
+ * flight.  A call that had to grow it adds to isl_search_stats::allocations; the next call of the same shape adds
+ * nothing.  Refusals, in this order: NULL pointers with nq > 0 -> ISL_ERR_INVALID_ARGUMENT; no refine table ->
+ * ISL_ERR_INVALID_ARGUMENT; k == 0, k > candidates or candidates > ef -> ISL_ERR_INVALID_ARGUMENT; candidates above
+ * ISL_REFINE_MAX_CANDIDATES -> ISL_ERR_UNSUPPORTED; d != the table's -> ISL_ERR_DIMENSION_MISMATCH; the recompute
+ * provider or the core index of an HnswGraph -> ISL_ERR_UNSUPPORTED.  nq == 0 -> ISL_OK. */
+isl_status isl_search_refined_batch_device(const isl_index* idx, const float* d_queries, uint64_t nq,
+                                           uint64_t d, uint64_t k, uint64_t candidates, uint64_t ef,
+                                           uint64_t* d_out_ids, float* d_out_dist, uint32_t* d_out_count,
+                                           void* stream);
+/* ... with host buffers in and out. */
+isl_status isl_search_refined_batch(const isl_index* idx, const float* queries, uint64_t nq, uint64_t d,
+                                    uint64_t k, uint64_t candidates, uint64_t ef, uint64_t* out_ids,
+                                    float* out_dist, uint32_t* out_count);
+
 /* ---- distance.rs ---- */
 /* Distance::calculate, distance.rs:38-52. */
 isl_status isl_distance(int32_t metric, const float* a, uint64_t na, const float* b, uint64_t nb,

@@ -124,6 +124,20 @@ struct CoveredSeeds {
   uint64_t unreached = 0;     // rows it still does not reach (non-zero only where max_seeds ended the loop)
 };
 
+// What the refine table costs (isl_index_refine_storage; rows == 0: no table), and the answer of a batch call:
+// row q of ids / dist ([nq][k]) holds count[q] valid entries, ascending distance.
+struct RefineStorage {
+  int32_t dtype = ISL_DTYPE_F32, placement = ISL_REFINE_DEVICE;
+  uint64_t rows = 0, block_bytes = 0;
+};
+struct BatchAnswer {
+  uint64_t k = 0;
+  std::vector<uint64_t> ids;
+  std::vector<float> dist;
+  std::vector<uint32_t> count;
+  BatchAnswer(uint64_t nq, uint64_t k_) : k(k_), ids(nq * k_ + 1), dist(nq * k_ + 1), count(nq + 1) {}
+};
+
 // LeannIndex, src/core/leann.rs:492-1067
 class LeannIndex {
  public:
@@ -359,6 +373,37 @@ class LeannIndex {
     std::vector<std::pair<uint64_t, float>> out;
     for (uint32_t i = 0; i < cnt; i++) out.emplace_back(ids[i], dist[i]);
     return out;
+  }
+  // extension: refined search.  The table a refined search re-scores its candidates against: n = len() rows of d
+  // floats (or bf16 bit patterns), kept on the device or in pinned host memory (ISL_REFINE_*); no rows drops it
+  void set_refine_rows(const std::vector<float>& rows, uint64_t n, int32_t placement = ISL_REFINE_DEVICE) {
+    check(isl_index_set_refine_rows(h_, rows.data(), n, n ? rows.size() / n : 0, ISL_DTYPE_F32, ISL_MEM_HOST, placement));
+  }
+  void set_refine_rows_bf16(const std::vector<uint16_t>& bits, uint64_t n, int32_t placement = ISL_REFINE_DEVICE) {
+    check(isl_index_set_refine_rows(h_, bits.data(), n, n ? bits.size() / n : 0, ISL_DTYPE_BF16, ISL_MEM_HOST, placement));
+  }
+  RefineStorage refine_storage() const {
+    RefineStorage s;
+    check(isl_index_refine_storage(h_, &s.dtype, &s.placement, &s.rows, &s.block_bytes));
+    return s;
+  }
+  // search_batch(queries, candidates, ef) over the stored rows, then the best k of those by their distances to the
+  // refine rows (isl_search_refined_batch); queries: nq rows of dimension() floats
+  BatchAnswer search_refined_batch(const std::vector<float>& queries, uint64_t nq, uint64_t k, uint64_t ef,
+                                   uint64_t candidates = 0) const {
+    if (!candidates) candidates = ef < ISL_REFINE_MAX_CANDIDATES ? ef : ISL_REFINE_MAX_CANDIDATES;
+    BatchAnswer a(nq, k);
+    check(isl_search_refined_batch(h_, queries.data(), nq, nq ? queries.size() / nq : 0, k, candidates, ef, a.ids.data(),
+                                   a.dist.data(), a.count.data()));
+    return a;
+  }
+  // the rescoring alone (isl_rescore): cand_ids [nq][pitch], the first cand_count[q] of row q valid
+  BatchAnswer rescore(const std::vector<float>& queries, uint64_t nq, const std::vector<uint64_t>& cand_ids,
+                      const std::vector<uint32_t>& cand_count, uint64_t k) const {
+    BatchAnswer a(nq, k);
+    check(isl_rescore(h_, queries.data(), nq, nq ? queries.size() / nq : 0, cand_ids.data(), cand_count.data(),
+                      nq ? cand_ids.size() / nq : 0, k, a.ids.data(), a.dist.data(), a.count.data()));
+    return a;
   }
   isl_index* handle() const { return h_; }
 

@@ -32,6 +32,9 @@ MEM_HOST, MEM_DEVICE = 0, 1
 SELECT_REFERENCE, SELECT_DIVERSE = 0, 1  # ISL_SELECT_*
 _SELECT_RULES = {"reference": SELECT_REFERENCE, "diverse": SELECT_DIVERSE}
 REMOVED = 0xFFFFFFFFFFFFFFFF  # ISL_REMOVED: an id LeannIndex.remove took out, in the remap it returns
+REFINE_DEVICE, REFINE_HOST = 0, 1  # ISL_REFINE_*
+REFINE_MAX_CANDIDATES = 512        # ISL_REFINE_MAX_CANDIDATES
+_REFINE_PLACEMENTS = {"device": REFINE_DEVICE, "host": REFINE_HOST}
 
 
 class CoreError(Exception):
@@ -956,6 +959,93 @@ class LeannIndex:
         _check(_ffi.lib().isl_search_batch(self._h, _ptr(q), nq, d, k, ef, _ptr(ids), _ptr(dist),
                                            _ptr(cnt)))
         return ids[:, :k], dist[:, :k], cnt
+
+    # ---- extension: refined search, candidates re-scored against a second, wider row table ----
+    def set_refine_rows(self, rows=None, placement: str = "device", device_ptr: int | None = None,
+                        n: int | None = None, d: int | None = None, dtype: str = "f32") -> "LeannIndex":
+        """isl_index_set_refine_rows: the table a refined search re-scores its candidates against, one row per
+        node.  `rows` [n, d] float32, or uint16 bf16 bit patterns (the dtype is the array's); or (device_ptr, n, d,
+        dtype "f32" | "bf16") for rows on the index's device.  placement "device" keeps the copy in HBM, "host" in
+        pinned host memory that the kernel reads across the bus.  None or an empty matrix drops the table.  The
+        table is not serialised, survives convert_rows / set_embeddings* and goes with insert / remove."""
+        if placement not in _REFINE_PLACEMENTS:
+            raise ValueError(f"placement must be one of {sorted(_REFINE_PLACEMENTS)}")
+        place = _REFINE_PLACEMENTS[placement]
+        l = _ffi.lib()
+        if device_ptr is not None:
+            if dtype not in ("f32", "bf16"):
+                raise ValueError('dtype must be "f32" or "bf16"')
+            _check(l.isl_index_set_refine_rows(self._h, C.c_void_p(device_ptr), n, d, _ROW_DTYPES[dtype], MEM_DEVICE, place))
+            return self
+        if rows is None or np.asarray(rows).size == 0:
+            _check(l.isl_index_set_refine_rows(self._h, None, 0, 0, DTYPE_F32, MEM_HOST, place))
+            return self
+        r = np.asarray(rows)
+        r = np.ascontiguousarray(r) if r.dtype == np.uint16 else _f32(r)
+        if r.ndim != 2:
+            raise ValueError("refine rows are a matrix [n, d]")
+        _check(l.isl_index_set_refine_rows(self._h, _ptr(r), r.shape[0], r.shape[1],
+                                           DTYPE_BF16 if r.dtype == np.uint16 else DTYPE_F32, MEM_HOST, place))
+        return self
+
+    def refine_storage(self) -> dict:
+        """isl_index_refine_storage: {"dtype": ISL_DTYPE_*, "placement": "device" | "host", "rows": 0 without a
+        table, "block_bytes": bytes of the row block, in HBM or in pinned host memory as the placement says}."""
+        dt, pl, n, nb = _ffi.i32(0), _ffi.i32(0), u64(0), u64(0)
+        _check(_ffi.lib().isl_index_refine_storage(self._h, C.byref(dt), C.byref(pl), C.byref(n), C.byref(nb)))
+        return {"dtype": int(dt.value), "placement": "host" if pl.value == REFINE_HOST else "device",
+                "rows": int(n.value), "block_bytes": int(nb.value)}
+
+    def search_refined_batch(self, queries, k: int, ef: int, candidates: int | None = None):
+        """isl_search_refined_batch: search_batch(queries, candidates, ef) over the stored rows, then the best k of
+        those candidates by their distances to the refine rows.  candidates None: min(ef, 512).
+        Returns (ids [nq,k] u64, dist [nq,k] f32, count [nq] u32)."""
+        if candidates is None:
+            candidates = min(int(ef), REFINE_MAX_CANDIDATES)
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, d = q.shape
+        ids = np.zeros((nq, max(k, 1)), dtype=np.uint64)
+        dist = np.zeros((nq, max(k, 1)), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        _check(_ffi.lib().isl_search_refined_batch(self._h, _ptr(q), nq, d, k, candidates, ef, _ptr(ids), _ptr(dist),
+                                                   _ptr(cnt)))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def search_refined_batch_ptr(self, d_queries_ptr: int, nq: int, d: int, k: int, ef: int, candidates: int,
+                                 d_ids_ptr: int, d_dist_ptr: int, d_count_ptr: int, stream: int = 0):
+        """isl_search_refined_batch_device: every buffer on the index's device, synchronised before returning."""
+        _check(_ffi.lib().isl_search_refined_batch_device(
+            self._h, C.c_void_p(d_queries_ptr), nq, d, k, candidates, ef, C.c_void_p(d_ids_ptr),
+            C.c_void_p(d_dist_ptr), C.c_void_p(d_count_ptr), C.c_void_p(stream)))
+
+    def rescore(self, queries, cand_ids, cand_count, k: int):
+        """isl_rescore: per query the best k of its candidate ids (cand_ids [nq, pitch] u64, the first
+        cand_count[q] of row q valid) by their distances to the refine rows; ties go to the earlier position, ids
+        >= len are skipped.  Returns (ids [nq,k] u64, dist [nq,k] f32, count [nq] u32)."""
+        q = _f32(queries)
+        if q.ndim == 1:
+            q = q.reshape(1, -1)
+        nq, d = q.shape
+        ci = np.ascontiguousarray(cand_ids, dtype=np.uint64).reshape(nq, -1)
+        cc = np.ascontiguousarray(cand_count, dtype=np.uint32).ravel()
+        if cc.size != nq:
+            raise ValueError("cand_count has one entry per query")
+        ids = np.zeros((nq, max(k, 1)), dtype=np.uint64)
+        dist = np.zeros((nq, max(k, 1)), dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        _check(_ffi.lib().isl_rescore(self._h, _ptr(q), nq, d, _ptr(ci), _ptr(cc), ci.shape[1], k, _ptr(ids),
+                                      _ptr(dist), _ptr(cnt)))
+        return ids[:, :k], dist[:, :k], cnt
+
+    def rescore_ptr(self, d_queries_ptr: int, nq: int, d: int, d_cand_ids_ptr: int, d_cand_count_ptr: int, pitch: int,
+                    k: int, d_ids_ptr: int, d_dist_ptr: int, d_count_ptr: int, stream: int = 0):
+        """isl_rescore_device: enqueue only, every buffer on the index's device; composes behind a search in
+        stream order."""
+        _check(_ffi.lib().isl_rescore_device(
+            self._h, C.c_void_p(d_queries_ptr), nq, d, C.c_void_p(d_cand_ids_ptr), C.c_void_p(d_cand_count_ptr), pitch,
+            k, C.c_void_p(d_ids_ptr), C.c_void_p(d_dist_ptr), C.c_void_p(d_count_ptr), C.c_void_p(stream)))
 
     # ---- extension: two-level search with a PQ filter (docs/leann-specification.md:223-275) ----
     def set_pq_codes(self, pq: "ProductQuantizer", codes=None, device_ptr: int | None = None,

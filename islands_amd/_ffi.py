@@ -194,6 +194,16 @@ SIGNATURES = {
     "isl_index_reachability": (i32, [C.c_void_p, C.c_void_p, u64, C.c_void_p, C.c_void_p, i32, P(ReachReportC)]),
     "isl_hnsw_reachability": (i32, [C.c_void_p, u64, C.c_void_p, u64, C.c_void_p, C.c_void_p, i32, P(ReachReportC)]),
     "isl_index_cover_entry_seeds": (i32, [C.c_void_p, u64, C.c_void_p, P(u64), P(u64)]),
+    "isl_index_set_refine_rows": (i32, [C.c_void_p, C.c_void_p, u64, u64, i32, i32, i32]),
+    "isl_index_refine_storage": (i32, [C.c_void_p, P(i32), P(i32), P(u64), P(u64)]),
+    "isl_rescore_device": (i32, [C.c_void_p, C.c_void_p, u64, u64, C.c_void_p, C.c_void_p, u64, u64, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "isl_rescore": (i32, [C.c_void_p, C.c_void_p, u64, u64, C.c_void_p, C.c_void_p, u64, u64, C.c_void_p,
+                          C.c_void_p, C.c_void_p]),
+    "isl_search_refined_batch_device": (i32, [C.c_void_p, C.c_void_p, u64, u64, u64, u64, u64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "isl_search_refined_batch": (i32, [C.c_void_p, C.c_void_p, u64, u64, u64, u64, u64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
     "isl_index_metadata_new": (None, [u64, u64, C.c_int64, P(IndexMetadataC)]),
     "isl_storage_write_metadata": (i32, [P(IndexMetadataC), P(C.c_void_p), P(C.c_size_t)]),
     "isl_storage_read_metadata": (i32, [C.c_void_p, C.c_size_t, P(IndexMetadataC), P(C.c_size_t)]),

@@ -1328,6 +1328,7 @@ void adopt_grown(isl_index* idx, isl_index* grown, bool rows_in_place = false) {
     if (idx->rows.resident()) ++idx->row_allocations;
   }
   idx->nvec = grown->nvec;
+  idx->refine.reset();  // one row per node of the old graph
   // the padded adjacency of the old graph goes.  In its place comes the grown graph's, which
   // isl_index_from_device_csr has just made: the copy the next search would otherwise make again (absent when
   // there was no memory for it; the searches then pad on demand or stay on the CSR)

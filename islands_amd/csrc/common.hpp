@@ -12,6 +12,7 @@
 #include <cstring>
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -204,6 +205,19 @@ inline GroupSwitches group_switches() {
 }
 struct GroupState;  // search_group.hip
 
+// The inner answers of one refined search in flight (search_refine.hip): [nq][candidates] ids and distances, [nq]
+// counts, and for the host-pointer form the staged queries and the final answers.
+struct RefineScratch {
+  bool busy = false;  // under isl_index::mu
+  DeviceBuffer<uint64_t> ids;
+  DeviceBuffer<float> dist;
+  DeviceBuffer<uint32_t> count;
+  DeviceBuffer<float> q_stage;
+  DeviceBuffer<uint64_t> out_ids;
+  DeviceBuffer<float> out_dist;
+  DeviceBuffer<uint32_t> out_count;
+};
+
 // Scratch of the heap-exact kernel, ONE pool per index shared by every lane: a workgroup that
 // finds work in its redo queue claims a free slot (lock word per slot), so concurrent searches
 // do not need a private copy each.
@@ -268,6 +282,11 @@ struct isl_index {
 
   // entry seeds (entry_seeds.hip); empty by default
   isl::EntrySeeds seeds;
+
+  // refine table and the scratch of the refined searches (search_refine.hip); empty by default.  One scratch set per
+  // refined call in flight, claimed and released under `mu`, kept for the next call.
+  isl::RefineTable refine;
+  mutable std::vector<std::unique_ptr<isl::RefineScratch>> refine_scratch;
 
   // graph under construction (build.hip): fixed-width adjacency rows, searched in place
   uint32_t* d_ell = nullptr;      // [num_nodes][ell_w]: the builder's rows (borrowed) or ell_copy
@@ -359,6 +378,9 @@ namespace isl {
 isl_status search_device_sync(const isl_index* idx, const float* d_queries, uint64_t nq, uint64_t d,
                               uint64_t k, uint64_t ef, uint64_t* d_ids, float* d_dist,
                               uint32_t* d_count, hipStream_t stream);
+// search.hip -- adds `events` to isl_search_stats::allocations of what isl_search_last_stats reports to this thread
+// for `idx` (the refined search: the scratch it had to grow beside the inner search's own set-up)
+void add_last_allocations(const isl_index* idx, uint64_t events);
 // shard.hip: marks the queries of call `token` that failed with ISL_SHARD_POISON_COUNT in d_counts [nq]
 isl_status poison_failed_queries(const isl_index* idx, uint64_t token, uint32_t* d_counts, uint64_t nq, hipStream_t stream);
 isl_status materialise_host_csr(const isl_index* idx);

@@ -108,6 +108,16 @@ class RowTable {
     v.capacity_ = t.capacity_; v.reserved_ = t.reserved_; v.borrowed_ = true;
     return v;
   }
+  // n rows of d elements of `dtype` in a block and norms that belong to someone else (the refine table's pinned host
+  // block, through its device pointer): laid out as allocate() lays a table out, block_elems >= alloc_elems(dtype, n, d)
+  static RowTable view_over(void* block, uint64_t block_elems, float* norm2, int32_t dtype, uint64_t n, uint64_t d) {
+    RowTable v;
+    v.block_.adopt(static_cast<unsigned char*>(block), block_elems * isl_rows::elem_size(dtype));
+    v.norm2_.adopt(norm2, n);
+    v.dtype_ = dtype; v.n_ = n; v.d_ = d; v.stride_ = isl_rows::stride(dtype, d);
+    v.capacity_ = n; v.borrowed_ = true;
+    return v;
+  }
   // the row count of a table with room: rows appended in place become visible, or a compacted table ends earlier
   void set_n(uint64_t n) { n_ = n; }
   // api_index.hip -- rows [first, first + count) from `src` (count x d elements of the table's type, host or
@@ -139,6 +149,22 @@ struct EntrySeeds {
   DeviceBuffer<uint32_t> d_ids;  // [count()]
   RowTable rows;
   uint64_t count() const { return rows.n(); }
+};
+
+// The refine table (search_refine.hip): a second table of len rows, f32 or bf16, that a refined search re-scores its
+// candidates against.  ISL_REFINE_DEVICE: `dev` is a table like the provider's.  ISL_REFINE_HOST: the rows lie in
+// `host`, one pinned, device-mapped block in the same layout, and `view` reads it through its device pointer beside
+// `host_norm2`, the norms on the device.  No table = both empty (the default).
+struct RefineTable {
+  int32_t placement = 0;  // ISL_REFINE_*
+  RowTable dev;
+  PinnedBuffer<unsigned char> host;
+  DeviceBuffer<float> host_norm2;
+  RowTable view;  // borrowed: over `host` and `host_norm2`
+  const RowTable& rows() const { return placement == 1 ? view : dev; }
+  uint64_t n() const { return rows().n(); }
+  // (the view lets go before the blocks it reads are freed)
+  void reset() { view.reset(); host.reset(); host_norm2.reset(); dev.reset(); placement = 0; }
 };
 
 }  // namespace isl

@@ -998,6 +998,10 @@ isl_status search_device_sync(const isl_index* idx, const float* d_queries, uint
   return search_sync(idx, *ws, SearchCall{d_queries, nq, d, k, ef, d_ids, d_dist, d_count, stream, StreamMode::USER});
 }
 
+void add_last_allocations(const isl_index* idx, uint64_t events) {
+  if (tl_last_stats.idx == idx) tl_last_stats.st.allocations += events;
+}
+
 }  // namespace isl
 
 extern "C" {
